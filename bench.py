@@ -4,17 +4,19 @@ Headline benchmark: frames/sec of the full PMD decomposition (BASELINE.json metr
 synthetic 512x512x10000 fp32 movie, 20x20 blocks, reference-default arguments, movie resident
 in HBM when the clock starts, results (CSR U, R, s, Vt, mean, std) on the host when it stops.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME] [--no-cpu-baseline] [--dump-outputs DIR]
 
 One "step" = one complete decomposition.  Rank 0 prints ONE JSON line carrying the metric,
 `roofline` (dominant hand-written kernel, timed with HIP events on its stream) and
 `cpu_baseline` (the CPU oracle timed on a bounded crop of the same movie, rank 0, N=1 only).
+--dump-outputs DIR writes the PMDArray of the last timed step as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
 import os
 import sys
 import time
+import zlib
 
 import numpy as np
 
@@ -39,6 +41,73 @@ CONFIGS = {
 DEFAULT_CONFIG = "512x512x10000_b20"
 FP32_MFMA_PEAK_TFLOPS = 157.3  # /opt/skills/guides/MI355X_MICROARCH.md, dense f32 matrix peak
 HBM_PEAK_GBS = 8000.0
+DUMP_ARRAY_BYTES = 6 << 20     # per dumped array; the dozen arrays of dump_outputs stay below DUMP_TOTAL_BYTES
+DUMP_TOTAL_BYTES = 64 << 20
+DUMP_FRAMES = 8
+DUMP_U_ENTRIES = 1 << 18
+
+
+def _sample_rows(name, a):
+    """``a`` whole if it fits DUMP_ARRAY_BYTES, else a fixed sample of its rows (axis 0, ascending; the generator is seeded
+    by ``name`` only, so equal shapes give equal samples) and the indices of those rows."""
+    if a.nbytes <= DUMP_ARRAY_BYTES:
+        return a, None
+    k = max(1, DUMP_ARRAY_BYTES // (a.nbytes // a.shape[0]))
+    idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(a.shape[0], size=k, replace=False))
+    return a[idx], idx
+
+
+def _frames(pmd, fidx):
+    """pmd[fidx] (the frames a caller reads back), accumulated in float64.  PMDArray.__getitem__ on the host would form
+    (R s) Vt for all frames first; this takes only the selected columns of Vt."""
+    vs = pmd.v[:, fidx].astype(np.float64) * pmd.s.astype(np.float64)[:, None]
+    temporal = np.empty((pmd.r.shape[0], len(fidx)))
+    for i in range(0, pmd.r.shape[0], 4096):
+        temporal[i:i + 4096] = pmd.r[i:i + 4096].astype(np.float64) @ vs
+    img = (pmd.u @ temporal)[pmd.row_indices]                      # (d1, d2, frames), pixel order of the PMDArray
+    img = img * pmd.var_img[..., None].astype(np.float64) + pmd.mean_img[..., None].astype(np.float64)
+    return np.ascontiguousarray(np.moveaxis(img, -1, 0), dtype=np.float32)
+
+
+def dump_outputs(pmd, out_dir):
+    """Writes what a caller of the timed path receives - the PMDArray (U as CSR, R, s, Vt, mean and noise images) and
+    frames expanded from it - as out_dir/<name>.npy, float32 (values) or float64 (indices and counts).  Arrays larger
+    than DUMP_ARRAY_BYTES are replaced by a fixed sample of their rows, with the row indices next to them
+    (<name>_rows.npy); U by its per-row entry counts and a fixed sample of its stored entries.  Returns the bytes written."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+
+    def put(name, a, float_dtype=np.float32):
+        a, idx = _sample_rows(name, np.ascontiguousarray(a, dtype=float_dtype))
+        arrays[name] = a
+        if idx is not None:
+            arrays[name + "_rows"] = idx.astype(np.float64)
+
+    u = pmd.u
+    put("s", pmd.s)
+    put("mean_img", pmd.mean_img)
+    put("var_img", pmd.var_img)   # the noise std image, under the PMDArray attribute name
+    put("u_row_nnz", np.diff(u.indptr), np.float64)
+    pos = np.arange(u.nnz)
+    if u.nnz > DUMP_U_ENTRIES:
+        pos = np.sort(np.random.default_rng(zlib.crc32(b"u_entries")).choice(u.nnz, size=DUMP_U_ENTRIES, replace=False))
+    arrays["u_entry_row"] = (np.searchsorted(u.indptr, pos, side="right") - 1).astype(np.float64)
+    arrays["u_entry_col"] = u.indices[pos].astype(np.float64)
+    arrays["u_entry_value"] = u.data[pos].astype(np.float32)
+    put("r", pmd.r)
+    put("v", pmd.v)
+    T = pmd.shape[0]
+    fidx = np.sort(np.random.default_rng(zlib.crc32(b"frames")).choice(T, size=min(T, DUMP_FRAMES), replace=False))
+    arrays["frame_index"] = fidx.astype(np.float64)
+    frames, rows = _sample_rows("frames", np.moveaxis(_frames(pmd, fidx), 1, 0))   # sampled along the image rows
+    arrays["frames"] = np.ascontiguousarray(np.moveaxis(frames, 0, 1))
+    if rows is not None:
+        arrays["frames_rows"] = rows.astype(np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_TOTAL_BYTES, total
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return total
 
 
 def cpu_baseline(cfg, movie_dev, seed):
@@ -122,7 +191,11 @@ def main():
     ap.add_argument("--config", default=DEFAULT_CONFIG, choices=sorted(CONFIGS))
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-host-input", action="store_true", help="skip the extra run that starts from a host array")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the result of the last timed step as DIR/<name>.npy (at most 64 MB, see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     import torch.distributed as dist
@@ -195,8 +268,10 @@ def main():
 
     # The timed steps run WITHOUT the library's HIP-event profiling (round-2 verdict: measurement overhead does not
     # belong in the headline number); the per-kernel times and both roofline objects come from the one extra,
-    # untimed, instrumented step below.
+    # untimed, instrumented step below.  Each step's result is dropped inside the timed region as it always was, except
+    # the last one's when --dump-outputs asks for it.
     cold_ms = None
+    result = None
     if cfg.get("one_shot"):
         # one-shot workloads (the movie fills a third of the HBM and is consumed by the step): every step gets a freshly
         # built movie, built outside the timed regions; each timed step is bracketed on its own and the times are summed
@@ -209,11 +284,13 @@ def main():
             if w == 0:
                 cold_ms = 1e3 * (time.perf_counter() - tc)   # first call of the process: every allocation is new
         elapsed = 0.0
-        for _ in range(args.steps):
+        for i in range(args.steps):
             movie = fresh_movie()
             barrier()
             t0 = time.perf_counter()
-            one_step()
+            result = one_step()
+            if not (args.dump_outputs and i == args.steps - 1):
+                result = None
             barrier()
             elapsed += time.perf_counter() - t0
     else:
@@ -221,8 +298,10 @@ def main():
             one_step()
         barrier()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
-            one_step()
+        for i in range(args.steps):
+            result = one_step()
+            if not (args.dump_outputs and i == args.steps - 1):
+                result = None
         barrier()
         elapsed = time.perf_counter() - t0
     one_shot_diag = None
@@ -233,6 +312,10 @@ def main():
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    dumped_bytes = None
+    if args.dump_outputs and rank == 0:   # the other ranks of the sharded route return None
+        dumped_bytes = dump_outputs(result, args.dump_outputs)
+    result = None
 
     # one extra, untimed, instrumented run: per-phase breakdown, tile statistics, per-kernel HIP-event times
     diag = one_shot_diag
@@ -372,6 +455,8 @@ def main():
     }
     if cold_ms is not None:
         out["cold_first_step_ms"] = cold_ms   # the first call of the process (every device / pinned allocation is new)
+    if dumped_bytes is not None:
+        out["dumped_outputs"] = {"dir": args.dump_outputs, "bytes": dumped_bytes}
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(cfg, movie, seed)
     if rank == 0:
