@@ -73,6 +73,26 @@ int pmd_stats(pmd_ctx* ctx, const float* movie, int T, long D, int frame_const, 
 int pmd_standardize_transpose(pmd_ctx* ctx, const float* movie, long D, const int* frames, int nf, const float* mean,
                               const float* std, float* out, long ld);
 
+/* Streamed ingestion (pmd_loader.py:71-108 FrameDataloader batches, :203-291 statistics pass, :316-346 projection pass):
+ * a movie longer than device memory is read in frames-first batches.  Element type of a batch: */
+enum pmd_elem { PMD_ELEM_F32 = 0, PMD_ELEM_U16 = 1, PMD_ELEM_I16 = 2 };
+#define PMD_STATS_CHUNK 1024   /* frames per Welch chunk of the streamed statistics (frame_const of pmd_stats) */
+/* Statistics of a T-frame movie from batches: accumulate frames [t0, t0 + nb) (t0 a multiple of PMD_STATS_CHUNK, nb a
+ * multiple of it unless the batch ends the movie) into a workspace that persists over the calls, then finish.  Every
+ * chunk must be accumulated once before finish.  fp32 batches give pmd_stats(frame_const = 1024) bit for bit;
+ * integer batches give pmd_stats on the fp32-converted movie bit for bit. */
+size_t pmd_stats_stream_workspace_bytes(int T, long D);
+int pmd_stats_stream_accumulate(pmd_ctx* ctx, const void* batch, int elem, int t0, int nb, int T, long D,
+                                int compute_normalizer, void* ws, size_t ws_bytes);
+int pmd_stats_stream_finish(pmd_ctx* ctx, int T, long D, int compute_normalizer, float* mean_out, float* std_out,
+                            void* ws, size_t ws_bytes);
+/* pmd_standardize_transpose on a batch of element type elem (converted to fp32 before (y - mean) / std). */
+int pmd_standardize_transpose_typed(pmd_ctx* ctx, const void* movie, int elem, long D, const int* frames, int nf,
+                                    const float* mean, const float* std, float* out, long ld);
+/* dst[dst_rows[i]] = src[src_rows[i]] for i < n: frames-first rows of D elements of type elem (device index lists). */
+int pmd_gather_frames(pmd_ctx* ctx, const void* src, int elem, long D, const int* src_rows, const int* dst_rows, int n,
+                      void* dst);
+
 /* A2: background basis = rank-K rSVD of the standardised sample (pmd_loader.py:46-68, :300-314).
  * xs: pixel-major sample with round_up(D,1024) rows allocated (rows >= D zero). basis_out[c][k]. */
 size_t pmd_background_rsvd_workspace_bytes(long D, int n, int K);

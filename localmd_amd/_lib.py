@@ -32,6 +32,11 @@ SIGNATURES = {
     "pmd_stats_workspace_bytes": (c_sz, [c_i, c_l, c_i]),
     "pmd_stats": (c_i, [c_p, c_p, c_i, c_l, c_i, c_i, c_p, c_p, c_p, c_sz]),
     "pmd_standardize_transpose": (c_i, [c_p, c_p, c_l, c_p, c_i, c_p, c_p, c_p, c_l]),
+    "pmd_stats_stream_workspace_bytes": (c_sz, [c_i, c_l]),
+    "pmd_stats_stream_accumulate": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_l, c_i, c_p, c_sz]),
+    "pmd_stats_stream_finish": (c_i, [c_p, c_i, c_l, c_i, c_p, c_p, c_p, c_sz]),
+    "pmd_standardize_transpose_typed": (c_i, [c_p, c_p, c_i, c_l, c_p, c_i, c_p, c_p, c_p, c_l]),
+    "pmd_gather_frames": (c_i, [c_p, c_p, c_i, c_l, c_p, c_p, c_i, c_p]),
     "pmd_background_rsvd_workspace_bytes": (c_sz, [c_l, c_i, c_i]),
     "pmd_background_rsvd": (c_i, [c_p, c_p, c_l, c_i, c_l, c_i, c_u64, c_p, c_p, c_sz]),
     "pmd_bg_project_workspace_bytes": (c_sz, [c_l, c_i]),

@@ -178,6 +178,30 @@ int pmd_standardize_transpose(pmd_ctx* ctx, const float* movie, long D, const in
   return pmd_launch_standardize_transpose(ctx, movie, D, frames, nf, mean, std, out, ld);
 }
 
+int pmd_stats_stream_accumulate(pmd_ctx* ctx, const void* batch, int elem, int t0, int nb, int T, long D,
+                                int compute_normalizer, void* ws, size_t ws_bytes) {
+  CTX_CHECK(ctx);
+  return pmd_launch_stats_stream_accumulate(ctx, batch, elem, t0, nb, T, D, compute_normalizer, ws, ws_bytes);
+}
+
+int pmd_stats_stream_finish(pmd_ctx* ctx, int T, long D, int compute_normalizer, float* mean_out, float* std_out,
+                            void* ws, size_t ws_bytes) {
+  CTX_CHECK(ctx);
+  return pmd_launch_stats_stream_finish(ctx, T, D, compute_normalizer, mean_out, std_out, ws, ws_bytes);
+}
+
+int pmd_standardize_transpose_typed(pmd_ctx* ctx, const void* movie, int elem, long D, const int* frames, int nf,
+                                    const float* mean, const float* std, float* out, long ld) {
+  CTX_CHECK(ctx);
+  return pmd_launch_standardize_transpose_typed(ctx, movie, elem, D, frames, nf, mean, std, out, ld);
+}
+
+int pmd_gather_frames(pmd_ctx* ctx, const void* src, int elem, long D, const int* src_rows, const int* dst_rows, int n,
+                      void* dst) {
+  CTX_CHECK(ctx);
+  return pmd_launch_gather_frames(ctx, src, elem, D, src_rows, dst_rows, n, dst);
+}
+
 size_t pmd_background_rsvd_workspace_bytes(long D, int n, int K) { return pmd_bg_workspace_bytes_impl(D, n, K); }
 int pmd_background_rsvd(pmd_ctx* ctx, const float* xs, long D, int n, long ld, int K, uint64_t seed, float* basis_out,
                         void* ws, size_t ws_bytes) {

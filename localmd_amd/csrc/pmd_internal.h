@@ -7,6 +7,7 @@ extern "C" {
 int pmd_tile_dpad(int d);
 long pmd_time_ld(long t);
 size_t pmd_stats_workspace_bytes(int T, long D, int frame_const);
+size_t pmd_stats_stream_workspace_bytes(int T, long D);
 }
 
 // rng.hip
@@ -18,6 +19,15 @@ int pmd_launch_stats(pmd_ctx* ctx, const float* movie, int T, long D, int frame_
                      float* std_out, void* ws, size_t ws_bytes);
 int pmd_launch_standardize_transpose(pmd_ctx* ctx, const float* movie, long D, const int* frames, int nf,
                                      const float* mean, const float* stdv, float* out, long ld);
+// streamed ingestion (elem: PMD_ELEM_* of include/pmd_hip.h)
+int pmd_launch_stats_stream_accumulate(pmd_ctx* ctx, const void* batch, int elem, int t0, int nb, int T, long D,
+                                       int do_noise, void* ws, size_t ws_bytes);
+int pmd_launch_stats_stream_finish(pmd_ctx* ctx, int T, long D, int do_noise, float* mean_out, float* std_out, void* ws,
+                                   size_t ws_bytes);
+int pmd_launch_standardize_transpose_typed(pmd_ctx* ctx, const void* movie, int elem, long D, const int* frames, int nf,
+                                           const float* mean, const float* stdv, float* out, long ld);
+int pmd_launch_gather_frames(pmd_ctx* ctx, const void* src, int elem, long D, const int* src_rows, const int* dst_rows,
+                             int n, void* dst);
 int pmd_launch_filter(pmd_ctx* ctx, const float* in, float* out, long D, int nf, long ld, const float* basis, int K,
                       const float* pj, long ldp);
 int pmd_launch_scale_rows(pmd_ctx* ctx, float* x, long D, int nf, long ld, const float* w);

@@ -9,6 +9,7 @@
 // 128-B line whatever the tile origin is.
 #include "pmd_internal.h"
 #include "fft_tables.h"
+#include "../../include/pmd_hip.h"
 
 // ---- tables: [0,256) Hann window (periodic); [256,320) cos, [320,384) sin of 2*pi*k/128;
 //              [384,513) cos, [513,642) sin of 2*pi*k/256 (k = 0..128)
@@ -51,9 +52,12 @@ __device__ __forceinline__ constexpr int bitrev7c(int x) {
   return r;
 }
 
+// Y holds T frames whose first frame starts chunk `chunk_off` of the whole movie: the streamed statistics hand over one
+// chunk-aligned batch at a time and the per-chunk partials land at their place in a workspace that outlives the batch.
 __global__ __launch_bounds__(64) void stats_chunk_kernel(const float* __restrict__ Y, int T, long D, int frame_const,
                                                          int do_noise, const float* __restrict__ tab,
-                                                         double* __restrict__ chunk_sum, float* __restrict__ chunk_noise) {
+                                                         double* __restrict__ chunk_sum, float* __restrict__ chunk_noise,
+                                                         int chunk_off) {
   (void)tab;
   const int lane = threadIdx.x;
   const long c = (long)blockIdx.x * 64 + lane;
@@ -145,11 +149,12 @@ __global__ __launch_bounds__(64) void stats_chunk_kernel(const float* __restrict
     for (int u = 0; u < 32; ++u) part += (t + u < t1) ? (double)v[u] : 0.0;
     s += part;
   }
-  if (valid) chunk_sum[(long)chunk * D + c] = s;
+  const long slot = (long)(chunk_off + chunk) * D + c;
+  if (valid) chunk_sum[slot] = s;
   if (!do_noise) return;
   // density scaling 1/(fs*sum w^2) = 1/96; mean over segments; 0.5 * Pxx averaged over 64 bins
   const float val = noise ? sqrtf(acc * (1.0f / 96.0f) / (float)nseg * 0.5f / 64.0f) : 0.f;
-  if (valid) chunk_noise[(long)chunk * D + c] = val;
+  if (valid) chunk_noise[slot] = val;
 }
 
 __global__ void stats_finalize_kernel(const double* __restrict__ chunk_sum, const float* __restrict__ chunk_noise,
@@ -170,6 +175,20 @@ __global__ void stats_finalize_kernel(const double* __restrict__ chunk_sum, cons
   }
 }
 
+static int stats_finalize(pmd_ctx* ctx, const double* csum, const float* cnoise, int T, long D, int frame_const,
+                          int do_noise, float* mean_out, float* std_out) {
+  const int nchunks = (T + frame_const - 1) / frame_const;
+  int ncounted = 0;
+  for (int k = 0; k < nchunks; ++k) {
+    const int n = (k + 1 == nchunks) ? T - k * frame_const : frame_const;
+    if (n >= 256) ncounted++;
+  }
+  hipLaunchKernelGGL(stats_finalize_kernel, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, ctx->stream, csum, cnoise,
+                     nchunks, ncounted, D, T, do_noise, mean_out, std_out);
+  PMD_LAUNCH_CHECK(ctx, "stats_finalize_kernel");
+  return PMD_OK;
+}
+
 size_t pmd_stats_workspace_bytes(int T, long D, int frame_const) {
   const int nchunks = (T + frame_const - 1) / frame_const;
   return (size_t)nchunks * D * (sizeof(double) + sizeof(float)) + 1024;
@@ -184,24 +203,93 @@ int pmd_launch_stats(pmd_ctx* ctx, const float* movie, int T, long D, int frame_
   float* cnoise = ar.take_n<float>((size_t)nchunks * D);
   if (ar.overflow) return pmd_fail(ctx, PMD_ERR_WORKSPACE, "pmd_stats", "workspace too small");
   if (T < 256) do_noise = 0;  // pmd_loader.py:213-214
-  int ncounted = 0;
-  for (int k = 0; k < nchunks; ++k) {
-    const int n = (k + 1 == nchunks) ? T - k * frame_const : frame_const;
-    if (n >= 256) ncounted++;
-  }
-  hipLaunchKernelGGL(stats_chunk_kernel, dim3((unsigned)((D + 63) / 64), nchunks), dim3(64), 0, ctx->stream, movie, T,
-                     D, frame_const, do_noise, ctx->tables, csum, cnoise);
+  hipLaunchKernelGGL(stats_chunk_kernel, dim3((unsigned)((D + 63) / 64), nchunks), dim3(64), 0, ctx->stream, movie,
+                     T, D, frame_const, do_noise, ctx->tables, csum, cnoise, 0);
   PMD_LAUNCH_CHECK(ctx, "stats_chunk_kernel");
-  hipLaunchKernelGGL(stats_finalize_kernel, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, ctx->stream, csum, cnoise,
-                     nchunks, ncounted, D, T, do_noise, mean_out, std_out);
-  PMD_LAUNCH_CHECK(ctx, "stats_finalize_kernel");
+  return stats_finalize(ctx, csum, cnoise, T, D, frame_const, do_noise, mean_out, std_out);
+}
+
+// ---- streamed statistics: the same chunk partials, one chunk-aligned batch of frames at a time ----------------------
+// Chunk k of the movie is computed from the same frames by the same kernel whichever batch carries it, and the finish
+// step is the finalize kernel of pmd_stats: for fp32 input the result is bit-identical to pmd_stats on the whole movie.
+// Integer batches are widened to fp32 one chunk at a time into the tail of the workspace and go through the fp32 kernel:
+// the Welch pass compiled for 16-bit loads contracts its multiply-adds differently (last-bit differences in sigma seen),
+// and the promise is the bits of pmd_stats on the converted movie.  The extra fp32 write + read of a chunk is HBM
+// traffic, far below the host link that bounds the streamed passes.
+size_t pmd_stats_stream_workspace_bytes(int T, long D) {
+  return pmd_stats_workspace_bytes(T, D, PMD_STATS_CHUNK) + (size_t)PMD_STATS_CHUNK * D * sizeof(float) + 256;
+}
+
+template <typename E>
+__global__ __launch_bounds__(256) void widen_f32_kernel(const E* __restrict__ in, long n, float* __restrict__ out) {
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) out[i] = (float)in[i];
+}
+
+template <typename E>
+static int stats_chunks_widened(pmd_ctx* ctx, const E* batch, int nb, long D, int do_noise, double* csum, float* cnoise,
+                                int c0, float* wide) {
+  const unsigned grid_w = (unsigned)(((long)PMD_STATS_CHUNK * D + 255) / 256 < 8192 ? ((long)PMD_STATS_CHUNK * D + 255) / 256 : 8192);
+  for (int k = 0; k * PMD_STATS_CHUNK < nb; ++k) {
+    const int n = (nb - k * PMD_STATS_CHUNK < PMD_STATS_CHUNK) ? nb - k * PMD_STATS_CHUNK : PMD_STATS_CHUNK;
+    hipLaunchKernelGGL(widen_f32_kernel<E>, dim3(grid_w), dim3(256), 0, ctx->stream, batch + (long)k * PMD_STATS_CHUNK * D,
+                       (long)n * D, wide);
+    PMD_LAUNCH_CHECK(ctx, "widen_f32_kernel");
+    hipLaunchKernelGGL(stats_chunk_kernel, dim3((unsigned)((D + 63) / 64), 1), dim3(64), 0, ctx->stream, wide, n, D,
+                       PMD_STATS_CHUNK, do_noise, ctx->tables, csum, cnoise, c0 + k);
+    PMD_LAUNCH_CHECK(ctx, "stats_chunk_kernel");
+  }
   return PMD_OK;
+}
+
+int pmd_launch_stats_stream_accumulate(pmd_ctx* ctx, const void* batch, int elem, int t0, int nb, int T, long D,
+                                       int do_noise, void* ws, size_t ws_bytes) {
+  pmd_prof_scope prof__(ctx, "stats_welch");
+  if (T < 1 || D < 1 || nb < 1 || t0 < 0 || t0 % PMD_STATS_CHUNK != 0 || (long)t0 + nb > T ||
+      (t0 + nb < T && nb % PMD_STATS_CHUNK != 0))
+    return pmd_fail(ctx, PMD_ERR_ARG, "pmd_stats_stream_accumulate",
+                    "a batch must start on a 1024-frame chunk and hold whole chunks (only the last batch may be ragged)");
+  const int nchunks = (T + PMD_STATS_CHUNK - 1) / PMD_STATS_CHUNK;
+  pmd_arena ar(ws, ws_bytes);
+  double* csum = ar.take_n<double>((size_t)nchunks * D);
+  float* cnoise = ar.take_n<float>((size_t)nchunks * D);
+  float* wide = ar.take_n<float>((size_t)PMD_STATS_CHUNK * D);
+  if (ar.overflow) return pmd_fail(ctx, PMD_ERR_WORKSPACE, "pmd_stats_stream_accumulate", "workspace too small");
+  if (T < 256) do_noise = 0;  // decided by the whole movie, as in pmd_stats
+  const int c0 = t0 / PMD_STATS_CHUNK;
+  switch (elem) {
+    case PMD_ELEM_F32:
+      hipLaunchKernelGGL(stats_chunk_kernel, dim3((unsigned)((D + 63) / 64), (unsigned)((nb + PMD_STATS_CHUNK - 1) / PMD_STATS_CHUNK)),
+                         dim3(64), 0, ctx->stream, (const float*)batch, nb, D, PMD_STATS_CHUNK, do_noise, ctx->tables, csum,
+                         cnoise, c0);
+      PMD_LAUNCH_CHECK(ctx, "stats_chunk_kernel");
+      return PMD_OK;
+    case PMD_ELEM_U16:
+      return stats_chunks_widened(ctx, (const uint16_t*)batch, nb, D, do_noise, csum, cnoise, c0, wide);
+    case PMD_ELEM_I16:
+      return stats_chunks_widened(ctx, (const int16_t*)batch, nb, D, do_noise, csum, cnoise, c0, wide);
+    default:
+      return pmd_fail(ctx, PMD_ERR_ARG, "pmd_stats_stream_accumulate", "unknown element type");
+  }
+}
+
+int pmd_launch_stats_stream_finish(pmd_ctx* ctx, int T, long D, int do_noise, float* mean_out, float* std_out, void* ws,
+                                   size_t ws_bytes) {
+  pmd_prof_scope prof__(ctx, "stats_welch");
+  if (T < 1 || D < 1) return pmd_fail(ctx, PMD_ERR_ARG, "pmd_stats_stream_finish", "empty movie");
+  const int nchunks = (T + PMD_STATS_CHUNK - 1) / PMD_STATS_CHUNK;
+  pmd_arena ar(ws, ws_bytes);
+  double* csum = ar.take_n<double>((size_t)nchunks * D);
+  float* cnoise = ar.take_n<float>((size_t)nchunks * D);
+  if (ar.overflow) return pmd_fail(ctx, PMD_ERR_WORKSPACE, "pmd_stats_stream_finish", "workspace too small");
+  if (T < 256) do_noise = 0;
+  return stats_finalize(ctx, csum, cnoise, T, D, PMD_STATS_CHUNK, do_noise, mean_out, std_out);
 }
 
 // ---- standardise + transpose: out[c][f] = (Y[frames[f]][c] - mean[c]) / std[c] ------------
 // 64 pixels x 64 frames per workgroup through a padded LDS tile; columns f in [nf, ld) are
 // written as zeros so that consumers may read whole padded rows.
-__global__ __launch_bounds__(256) void standardize_transpose_kernel(const float* __restrict__ Y, long D,
+template <typename E>
+__global__ __launch_bounds__(256) void standardize_transpose_kernel(const E* __restrict__ Y, long D,
                                                                     const int* __restrict__ frames, int nf,
                                                                     const float* __restrict__ mean,
                                                                     const float* __restrict__ stdv,
@@ -221,7 +309,7 @@ __global__ __launch_bounds__(256) void standardize_transpose_kernel(const float*
   for (int u = 0; u < 16; ++u) {
     const int f = min(f0 + ty + 4 * u, nf - 1);
     const long t = frames ? (long)frames[f] : (long)f;
-    y[u] = Y[t * D + cc];
+    y[u] = (float)Y[t * D + cc];   // integer input: converted before (y - mean) / std
   }
 #pragma unroll
   for (int u = 0; u < 16; ++u) {
@@ -240,9 +328,80 @@ int pmd_launch_standardize_transpose(pmd_ctx* ctx, const float* movie, long D, c
                                      const float* mean, const float* stdv, float* out, long ld) {
   pmd_prof_scope prof__(ctx, "standardize_transpose");
   dim3 grid((unsigned)((D + 63) / 64), (unsigned)((ld + 63) / 64));
-  hipLaunchKernelGGL(standardize_transpose_kernel, grid, dim3(256), 0, ctx->stream, movie, D, frames, nf, mean, stdv,
-                     out, ld);
+  hipLaunchKernelGGL(standardize_transpose_kernel<float>, grid, dim3(256), 0, ctx->stream, movie, D, frames, nf, mean,
+                     stdv, out, ld);
   PMD_LAUNCH_CHECK(ctx, "standardize_transpose_kernel");
+  return PMD_OK;
+}
+
+int pmd_launch_standardize_transpose_typed(pmd_ctx* ctx, const void* movie, int elem, long D, const int* frames, int nf,
+                                           const float* mean, const float* stdv, float* out, long ld) {
+  pmd_prof_scope prof__(ctx, "standardize_transpose");
+  if (D < 1 || nf < 1 || ld < nf)
+    return pmd_fail(ctx, PMD_ERR_ARG, "pmd_standardize_transpose_typed", "empty input or leading dimension too small");
+  dim3 grid((unsigned)((D + 63) / 64), (unsigned)((ld + 63) / 64));
+  switch (elem) {
+    case PMD_ELEM_F32:
+      hipLaunchKernelGGL(standardize_transpose_kernel<float>, grid, dim3(256), 0, ctx->stream, (const float*)movie, D,
+                         frames, nf, mean, stdv, out, ld);
+      break;
+    case PMD_ELEM_U16:
+      hipLaunchKernelGGL(standardize_transpose_kernel<uint16_t>, grid, dim3(256), 0, ctx->stream, (const uint16_t*)movie,
+                         D, frames, nf, mean, stdv, out, ld);
+      break;
+    case PMD_ELEM_I16:
+      hipLaunchKernelGGL(standardize_transpose_kernel<int16_t>, grid, dim3(256), 0, ctx->stream, (const int16_t*)movie, D,
+                         frames, nf, mean, stdv, out, ld);
+      break;
+    default:
+      return pmd_fail(ctx, PMD_ERR_ARG, "pmd_standardize_transpose_typed", "unknown element type");
+  }
+  PMD_LAUNCH_CHECK(ctx, "standardize_transpose_kernel");
+  return PMD_OK;
+}
+
+// ---- frame gather: dst[dst_rows[i]][:] = src[src_rows[i]][:], rows of D elements (frames-first) -------------------
+// The streamed decomposition copies the fit frames and the background sample of each batch into buffers of their own,
+// in the element type of the source.  A kernel rather than hipMemcpy2DAsync / per-frame copies: the sample frames are
+// scattered over the movie (a strided 2-D copy does not describe them, per-frame copies would be up to a thousand
+// calls per pass), and one launch serves any pair of index maps.
+template <typename E>
+__global__ __launch_bounds__(256) void gather_frames_kernel(const E* __restrict__ src, long D,
+                                                            const int* __restrict__ src_rows,
+                                                            const int* __restrict__ dst_rows, E* __restrict__ dst) {
+  const int i = blockIdx.y;
+  const E* s = src + (long)src_rows[i] * D;
+  E* o = dst + (long)dst_rows[i] * D;
+  for (long c = (long)blockIdx.x * 256 + threadIdx.x; c < D; c += (long)gridDim.x * 256) o[c] = s[c];
+}
+
+int pmd_launch_gather_frames(pmd_ctx* ctx, const void* src, int elem, long D, const int* src_rows, const int* dst_rows,
+                             int n, void* dst) {
+  pmd_prof_scope prof__(ctx, "gather_frames");
+  if (n <= 0) return PMD_OK;
+  if (D < 1) return pmd_fail(ctx, PMD_ERR_ARG, "pmd_gather_frames", "empty frame");
+  const long bx = ((D + 255) / 256 < 64) ? (D + 255) / 256 : 64;
+  for (int i0 = 0; i0 < n; i0 += 65535) {
+    const int in = (n - i0 < 65535) ? n - i0 : 65535;
+    const dim3 grid((unsigned)bx, (unsigned)in);
+    switch (elem) {
+      case PMD_ELEM_F32:
+        hipLaunchKernelGGL(gather_frames_kernel<float>, grid, dim3(256), 0, ctx->stream, (const float*)src, D,
+                           src_rows + i0, dst_rows + i0, (float*)dst);
+        break;
+      case PMD_ELEM_U16:
+        hipLaunchKernelGGL(gather_frames_kernel<uint16_t>, grid, dim3(256), 0, ctx->stream, (const uint16_t*)src, D,
+                           src_rows + i0, dst_rows + i0, (uint16_t*)dst);
+        break;
+      case PMD_ELEM_I16:
+        hipLaunchKernelGGL(gather_frames_kernel<int16_t>, grid, dim3(256), 0, ctx->stream, (const int16_t*)src, D,
+                           src_rows + i0, dst_rows + i0, (int16_t*)dst);
+        break;
+      default:
+        return pmd_fail(ctx, PMD_ERR_ARG, "pmd_gather_frames", "unknown element type");
+    }
+    PMD_LAUNCH_CHECK(ctx, "gather_frames_kernel");
+  }
   return PMD_OK;
 }
 

@@ -19,6 +19,11 @@ projection run on the slab); sums over pixels (background projection) and over c
 Gram matrices of the Cholesky route) are all-reduced, per-tile results are gathered, R is collected on rank 0.
 Rank 0 returns the PMDArray; on the row-sharded route the other ranks return None.  Random draws (seed,
 frame sample, frame windows) are rank 0's.
+``stream``: True reads the movie from its host source in ``frame_batch_size`` batches (rounded down to whole
+1024-frame chunks) instead of holding it in HBM - pass 1 computes the statistics and gathers the fit frames and the
+background sample, pass 2 projects every batch on the spatial basis (pmd_loader.py:203-291, :316-346); uint16 / int16
+sources travel in their own dtype.  False: the resident path.  None (default): streams only when the resident plan's
+raw + standardised movie copies do not fit in the free device memory.  Single GPU, host sources only.
 """
 import datetime
 import math
@@ -130,7 +135,27 @@ class _Movie:
     # recorded behind its transfer has completed.
     STAGE_BUFFERS = 3
     STAGE_BYTES = 64 << 20
-    _stage_cache = {}     # (frames per buffer, D, pinned) -> ring of staging buffers, kept between calls (page-locking is slow)
+    _stage_cache = {}     # (frames per buffer, D, pinned, dtype) -> ring of staging buffers, kept between calls (page-locking is slow)
+
+    @staticmethod
+    def _reader_threads(dataset_obj, is_array, num_workers):
+        # num_workers = 0 is in-process, single-threaded loading in the reference (pmd_loader.py:161-168; workers > 0 are
+        # separate processes with a dataset copy each).  A user's lazy_data_loader may share a file handle or a decoder
+        # that is not re-entrant, so its __getitem__ is called from ONE reader thread unless num_workers > 0 is passed,
+        # which then promises a thread-safe __getitem__ (as does a true `thread_safe` attribute of the loader, which the
+        # built-in TiffArray has).  Slicing a NumPy array is thread-safe: many copy threads.
+        if num_workers and num_workers > 0:
+            return int(num_workers)
+        return min(32, os.cpu_count() or 1) if (is_array or getattr(dataset_obj, "thread_safe", False)) else 1
+
+    @staticmethod
+    def _stage_ring(step, D, on_gpu, dtype):
+        torch = _torch()
+        key = (step, D, on_gpu, dtype)
+        if key not in _Movie._stage_cache:
+            _Movie._stage_cache.clear()
+            _Movie._stage_cache[key] = [torch.empty((step, D), dtype=dtype, pin_memory=on_gpu) for _ in range(_Movie.STAGE_BUFFERS)]
+        return _Movie._stage_cache[key]
 
     def _stream_in(self, dataset_obj, frame_batch_size, i_lo, i_hi, num_workers):
         torch = _torch()
@@ -140,21 +165,9 @@ class _Movie:
         frame_bytes = 4 * self.D
         step = max(1, min(int(frame_batch_size), self.STAGE_BYTES // max(frame_bytes, 1), self.T))
         is_array = isinstance(dataset_obj, np.ndarray)
-        # num_workers = 0 is in-process, single-threaded loading in the reference (pmd_loader.py:161-168; workers > 0 are
-        # separate processes with a dataset copy each).  A user's lazy_data_loader may share a file handle or a decoder
-        # that is not re-entrant, so its __getitem__ is called from ONE reader thread unless num_workers > 0 is passed,
-        # which then promises a thread-safe __getitem__ (as does a true `thread_safe` attribute of the loader, which the
-        # built-in TiffArray has).  Slicing a NumPy array is thread-safe: many copy threads.
-        if num_workers and num_workers > 0:
-            n_threads = int(num_workers)
-        else:
-            n_threads = min(32, os.cpu_count() or 1) if (is_array or getattr(dataset_obj, "thread_safe", False)) else 1
+        n_threads = self._reader_threads(dataset_obj, is_array, num_workers)
         full_rows = (i_lo == 0 and i_hi == self.d1)
-        key = (step, self.D, on_gpu)
-        if key not in _Movie._stage_cache:
-            _Movie._stage_cache.clear()
-            _Movie._stage_cache[key] = [torch.empty((step, self.D), dtype=torch.float32, pin_memory=on_gpu) for _ in range(self.STAGE_BUFFERS)]
-        stage = _Movie._stage_cache[key]
+        stage = self._stage_ring(step, self.D, on_gpu, torch.float32)
         stage_np = [b.numpy() for b in stage]
         done = [None] * self.STAGE_BUFFERS
         copy_stream = _side_stream(self.ctx.device) if on_gpu else None
@@ -213,6 +226,261 @@ class _Movie:
         fr = None if frames is None else _i32(ctx, frames)
         ctx.call("pmd_standardize_transpose", ptr(self.dev), self.D, ptr(fr), nf, ptr(mean), ptr(std), ptr(out), ld)
         return out, ld
+
+
+# ---- streamed mode: movies longer than device memory (reference: lazy_data_loader / FrameDataloader batches,
+# pmd_loader.py:71-108; statistics pass :203-291; projection pass :316-346).  Only the fit frames, the background
+# sample, two frame batches, the per-pixel statistics and Z live on the device; the movie is read twice from its source.
+STREAM_CHUNK = 1024          # frames per Welch chunk (PMD_STATS_CHUNK): batch boundaries fall on chunk boundaries
+STREAM_PROJECT_FRAMES = 2048  # frames per standardise + project step of pass 2 (bounds its pixel-major scratch)
+_ELEM = {np.dtype(np.float32): 0, np.dtype(np.uint16): 1, np.dtype(np.int16): 2}   # PMD_ELEM_F32 / _U16 / _I16
+
+
+def _stream_batch_frames(frame_batch_size):
+    """frame_batch_size rounded down to whole 1024-frame chunks, at least one chunk."""
+    return max(STREAM_CHUNK, int(frame_batch_size) // STREAM_CHUNK * STREAM_CHUNK)
+
+
+def _stream_batches(T, frame_batch_size):
+    """[(t0, t1)] frame batches of the streamed passes: every boundary but the last is a multiple of 1024."""
+    nb = _stream_batch_frames(frame_batch_size)
+    return [(t0, min(T, t0 + nb)) for t0 in range(0, int(T), nb)]
+
+
+def _gather_maps(frames, batches):
+    """For each batch (t0, t1): (rows of the batch, rows of the destination) of the listed frames it carries.
+    Destination row j holds frames[j], so a position of `frames` is covered exactly once (repeats included)."""
+    fr = np.asarray(frames, dtype=np.int64).reshape(-1)
+    maps = []
+    for t0, t1 in batches:
+        dst = np.nonzero((fr >= t0) & (fr < t1))[0]
+        maps.append(((fr[dst] - t0).astype(np.int32), dst.astype(np.int32)))
+    return maps
+
+
+def _stream_source_problem(dataset_obj, distributed):
+    """Why dataset_obj cannot be streamed (None: it can)."""
+    if distributed:
+        return "stream=True is single-GPU only (distributed=True is not supported)"
+    if hasattr(dataset_obj, "slab"):
+        return "stream=True does not support sources that build their frames on the device (.slab)"
+    try:
+        import torch
+    except ImportError:     # pragma: no cover - torch is a dependency
+        return None
+    if isinstance(dataset_obj, torch.Tensor) and dataset_obj.device.type != "cpu":
+        return "stream=True needs a host source (NumPy array / memmap, lazy_data_loader or CPU tensor), not a device tensor"
+    return None
+
+
+def _plan_mode(stream, T, D, free_bytes, streamable=True):
+    """'resident' or 'stream'.  stream=None (auto) streams only when the resident plan cannot fit: it holds the raw
+    fp32 movie and a standardised copy of it at the same time, twice the 4 D T bytes the single_copy rule estimates,
+    so every movie that decomposes resident today stays resident."""
+    if stream is None:
+        return "stream" if streamable and 2.0 * 4.0 * D * T > free_bytes else "resident"
+    return "stream" if stream else "resident"
+
+
+def _usable_free_bytes(free, reserved, allocated):
+    """Device memory a new allocation can get: what the driver reports free plus the blocks PyTorch's caching allocator
+    holds reserved but unused (an earlier large call leaves them cached; the allocator reuses them, and releases them to
+    retry before it reports out of memory)."""
+    return int(free) + max(0, int(reserved) - int(allocated))
+
+
+def _device_free_bytes(device):
+    torch = _torch()
+    return _usable_free_bytes(torch.cuda.mem_get_info(device)[0], torch.cuda.memory_reserved(device),
+                              torch.cuda.memory_allocated(device))
+
+
+def _stream_tile_bytes(n_tiles, rpad, dpad, ld_fit, ld_proj, tile_batch_bytes):
+    """Device bytes of the tile stage and of the projection blocks of pass 2: the per-tile bases U and U W (kept for
+    every tile) plus the per-tile traces and kernel temporaries - the per_tile_bytes estimate of the driver, which are
+    held for all tiles at once or, above tile_batch_bytes, for one batch of tiles at a time."""
+    per_tile = 3 * rpad * max(ld_fit, ld_proj) * 4 + 8 * rpad * dpad * 4 + (6 * rpad * rpad * 8 if rpad > 64 else 0)
+    return n_tiles * 2 * rpad * dpad * 4 + min(n_tiles * per_tile, max(int(tile_batch_bytes), 8 * per_tile))
+
+
+def _stream_fit_bytes(esize, D, rows_alloc, ld_fit, n_fit, n_sample, nb, tile_bytes):
+    """Device bytes the streamed mode needs around the fit frames: raw fit frames and sample (source dtype), the two
+    batch buffers, the standardised / filtered fit frames (fp32, pixel-major) plus one more array of that size for the
+    background-filter and pooling temporaries, and the tile stage (tile_bytes).  An estimate: small tables and the
+    workspaces of single kernels are left out."""
+    return esize * D * (n_fit + n_sample + 2 * nb) + 2 * 4 * rows_alloc * ld_fit + tile_bytes
+
+
+def _stream_dtype(src):
+    """Element type a source is staged and uploaded in: its own for uint16 / int16, fp32 otherwise."""
+    dt = getattr(src, "dtype", None)
+    try:
+        dt = np.dtype(dt) if dt is not None else np.dtype(np.float32)
+    except TypeError:
+        dt = np.dtype(np.float32)
+    return dt if dt in (np.dtype(np.uint16), np.dtype(np.int16)) else np.dtype(np.float32)
+
+
+class _StreamedMovie:
+    """The movie left at its source and read in frame batches: pass 1 (statistics, gathering the fit frames and the
+    background sample), pass 2 (standardise + project every batch, in build_z).  Same pinned staging ring and reader
+    threads as _Movie._stream_in; a batch is uploaded into one of two device buffers while the other one's kernels run."""
+
+    def __init__(self, ctx, dataset_obj, frame_batch_size, num_workers=0):
+        torch = _torch()
+        self.ctx = ctx
+        if isinstance(dataset_obj, torch.Tensor):
+            dataset_obj = dataset_obj.detach().numpy()
+        self.src = dataset_obj
+        self.T, self.d1, self.d2 = (int(x) for x in dataset_obj.shape)
+        self.D = self.d1 * self.d2
+        self.rows_alloc = _round_up(self.D, 1024) + 1024
+        self.np_dtype = _stream_dtype(dataset_obj)
+        self.elem = _ELEM[self.np_dtype]
+        self.tdtype = torch.from_numpy(np.zeros(1, dtype=self.np_dtype)).dtype
+        self.batches = _stream_batches(self.T, frame_batch_size)
+        self.nb = self.batches[0][1] - self.batches[0][0]
+        self.project_frames = min(self.nb, STREAM_PROJECT_FRAMES)
+        self.num_workers = num_workers
+        self.bytes_uploaded = 0
+        self.fit = self.sample = None     # gathered raw frames (device, frames-first)
+
+    def check_fit_frames(self, n_fit, n_sample, tile_bytes):
+        """Raise a ValueError (instead of a device out-of-memory error later) when the fit frames and the arrays of the
+        tile stage built on them cannot fit next to the two batch buffers (_stream_fit_bytes)."""
+        need = _stream_fit_bytes(self.np_dtype.itemsize, self.D, self.rows_alloc, int(self.ctx.lib.pmd_time_ld(n_fit)), n_fit,
+                                 n_sample, self.nb, tile_bytes)
+        free = _device_free_bytes(self.ctx.device)
+        if need > free:
+            raise ValueError("stream=True: fitting on {} frames of {} pixels needs about {:.1f} GB of device memory, {:.1f} GB "
+                             "are free; lower frame_range (or frame_batch_size)".format(n_fit, self.D, need / 1e9, free / 1e9))
+
+    def run_pass(self, consume):
+        """Read the whole movie once; consume(batch, t0, n) enqueues the work on batch (device, (n, D), raw dtype)
+        on the current stream.  Returns after the last batch is enqueued."""
+        torch = _torch()
+        from concurrent.futures import ThreadPoolExecutor
+
+        ctx, D = self.ctx, self.D
+        esize = self.np_dtype.itemsize
+        step = max(1, min(self.nb, _Movie.STAGE_BYTES // max(esize * D, 1)))
+        stage = _Movie._stage_ring(step, D, True, self.tdtype)
+        stage_np = [b.numpy() for b in stage]
+        n_stage = len(stage)
+        done = [None] * n_stage
+        is_array = isinstance(self.src, np.ndarray)
+        n_threads = _Movie._reader_threads(self.src, is_array, self.num_workers)
+        main = torch.cuda.current_stream(ctx.device)
+        copy_stream = _side_stream(ctx.device)
+        copy_stream.synchronize()            # the staging ring is kept between calls
+        copy_stream.wait_stream(main)        # the batch buffers may reuse blocks still in use on the main stream
+        dev = [torch.empty((self.nb, D), dtype=self.tdtype, device=ctx.device) for _ in range(min(2, len(self.batches)))]
+        free = [None] * len(dev)             # event behind the kernels that last read a batch buffer
+        src, d1, d2 = self.src, self.d1, self.d2
+
+        def fill(buf, t0, t1, base):
+            if is_array:
+                part = src[t0:t1]
+            else:
+                part = np.asarray(src[list(range(t0, t1))]).reshape(t1 - t0, d1, d2)
+            np.copyto(stage_np[buf][t0 - base:t1 - base].reshape(t1 - t0, d1, d2), part, casting="unsafe")
+
+        k_stage = 0
+        with ThreadPoolExecutor(max_workers=n_threads) as pool:
+            for k, (b0, b1) in enumerate(self.batches):
+                j = k % len(dev)
+                if free[j] is not None:
+                    copy_stream.wait_event(free[j])
+                for base in range(b0, b1, step):
+                    n = min(step, b1 - base)
+                    buf = k_stage % n_stage
+                    k_stage += 1
+                    if done[buf] is not None:
+                        done[buf].synchronize()
+                    parts = max(1, min(n_threads, n))
+                    edges = [base + (n * p) // parts for p in range(parts + 1)]
+                    for f in [pool.submit(fill, buf, edges[p], edges[p + 1], base) for p in range(parts)]:
+                        f.result()
+                    with torch.cuda.stream(copy_stream):
+                        dev[j][base - b0:base - b0 + n].copy_(stage[buf][:n], non_blocking=True)
+                        done[buf] = torch.cuda.Event()
+                        done[buf].record(copy_stream)
+                    self.bytes_uploaded += n * D * esize
+                main.wait_event(done[(k_stage - 1) % n_stage])     # the batch's last piece (copies are in order)
+                consume(dev[j][:b1 - b0], b0, b1 - b0)
+                free[j] = torch.cuda.Event()
+                free[j].record(main)
+        main.wait_stream(copy_stream)
+
+    def first_pass(self, compute_normalizer, frames, sample, mean, std):
+        """Pass 1: chunk statistics of every batch, and the fit frames / background sample gathered in the source
+        dtype.  Finishes mean / std."""
+        torch = _torch()
+        ctx, lib, T, D = self.ctx, self.ctx.lib, self.T, self.D
+        ws = torch.empty(int(lib.pmd_stats_stream_workspace_bytes(T, D)), dtype=torch.uint8, device=ctx.device)
+        self.fit = torch.empty((len(frames), D), dtype=self.tdtype, device=ctx.device)
+        self.sample = torch.empty((len(sample), D), dtype=self.tdtype, device=ctx.device) if sample else None
+        maps = [(m, _gather_maps(lst, self.batches), buf) for m, lst, buf in
+                (("fit", frames, self.fit), ("sample", sample or [], self.sample)) if buf is not None]
+        # the index maps of every batch go up in one table
+        tables = []
+        for _, per_batch, _ in maps:
+            for src_rows, dst_rows in per_batch:
+                tables += [src_rows, dst_rows]
+        offs = np.concatenate([[0], np.cumsum([len(t) for t in tables])]).astype(np.int64)
+        idx_dev = _i32(ctx, np.concatenate(tables) if tables else np.zeros(1, np.int32))
+        k_batch = {t0: k for k, (t0, _) in enumerate(self.batches)}
+
+        def consume(batch, t0, n):
+            ctx.call("pmd_stats_stream_accumulate", ptr(batch), self.elem, t0, n, T, D, 1 if compute_normalizer else 0,
+                     ptr(ws), ws.numel())
+            k = k_batch[t0]
+            for i, (_, per_batch, buf) in enumerate(maps):
+                slot = 2 * (i * len(self.batches) + k)
+                cnt = len(per_batch[k][0])
+                if cnt:
+                    ctx.call("pmd_gather_frames", ptr(batch), self.elem, D, ptr(idx_dev[int(offs[slot]):]),
+                             ptr(idx_dev[int(offs[slot + 1]):]), cnt, ptr(buf))
+
+        self.run_pass(consume)
+        ctx.call("pmd_stats_stream_finish", T, D, 1 if compute_normalizer else 0, ptr(mean), ptr(std), ptr(ws), ws.numel())
+        ctx.sync()     # the index table and the workspace are released on return
+
+    def standardized(self, which, mean, std):
+        """Pixel-major (rows_alloc x ld) standardised copy of the gathered 'fit' or 'sample' frames (in list order)."""
+        torch = _torch()
+        ctx = self.ctx
+        raw = self.fit if which == "fit" else self.sample
+        nf = raw.shape[0]
+        ld = ctx.lib.pmd_time_ld(nf)
+        out = torch.empty((self.rows_alloc, ld), dtype=torch.float32, device=ctx.device)
+        out[self.D:].zero_()
+        ctx.call("pmd_standardize_transpose_typed", ptr(raw), self.elem, self.D, None, nf, ptr(mean), ptr(std), ptr(out), ld)
+        return out, ld
+
+    def release(self):
+        """The standardised fit frames are written: the raw gathered frames are not read again."""
+        self.fit = self.sample = None
+
+    def project(self, mean, std, on_block):
+        """Pass 2: every frame block of at most STREAM_PROJECT_FRAMES frames standardised into a pixel-major scratch
+        (rows_alloc x pmd_time_ld(block)); on_block(xs, ld, t0, n) enqueues its projections."""
+        torch = _torch()
+        ctx, D = self.ctx, self.D
+        nblk = self.project_frames
+        ld = int(ctx.lib.pmd_time_ld(nblk))
+        xs = torch.empty((self.rows_alloc, ld), dtype=torch.float32, device=ctx.device)
+        xs[D:].zero_()
+        esize = self.np_dtype.itemsize
+
+        def consume(batch, t0, n):
+            for s0 in range(0, n, nblk):
+                sn = min(nblk, n - s0)
+                ctx.call("pmd_standardize_transpose_typed", C.c_void_p(batch.data_ptr() + s0 * D * esize), self.elem, D,
+                         None, sn, ptr(mean), ptr(std), ptr(xs), ld)
+                on_block(xs, ld, t0 + s0, sn)
+
+        self.run_pass(consume)
 
 
 def _to_host(t):
@@ -435,6 +703,7 @@ def localmd_decomposition(
     distributed: bool = False,
     return_diagnostics: bool = False,
     ctx: Optional[Context] = None,
+    stream: Optional[bool] = None,
 ):
     torch = _torch()
     if np.dtype(dtype) != np.float32:
@@ -448,6 +717,10 @@ def localmd_decomposition(
         raise ValueError("orthogonalizer must be 'auto', 'eigh' or 'cholesky'")
     if null_directions not in ("keep", "drop"):
         raise ValueError("null_directions must be 'keep' (the reference's rule) or 'drop'")
+    if stream:
+        problem = _stream_source_problem(dataset_obj, distributed)
+        if problem is not None:
+            raise ValueError(problem)
     timings = {}
     t_start = time.perf_counter()
 
@@ -493,8 +766,35 @@ def localmd_decomposition(
         O_lo, O_hi = owned[dist.rank] if dist.enabled else (0, D)
 
         # ---- PMDLoader.__init__ (pmd_loader.py:112-173): movie to HBM, statistics, background basis
+        # Streamed mode (stream=True, or stream=None when the resident plan cannot fit): the movie stays at its source
+        # and is read twice, pass 1 here (statistics, the fit frames and the background sample), pass 2 in build_z.
+        streamable = _stream_source_problem(dataset_obj, distributed) is None
+        free_bytes = _device_free_bytes(ctx.device) if (stream is None and streamable) else 0
+        streamed = _plan_mode(stream, T, D, free_bytes, streamable) == "stream"
+        K = int(background_rank)
+
+        def select_frames(frame_range, window_chunks):
+            # frames to fit on (decomposition.py:678-693)
+            if window_chunks is None:
+                window_chunks = frame_range
+            if T < frame_range:
+                display("WARNING: Specified using more frames than there are in the dataset.")
+                frame_range = T
+                frames = list(range(T))
+                if frame_range <= window_chunks:
+                    window_chunks = frame_range
+            else:
+                if frame_range <= window_chunks:
+                    window_chunks = frame_range
+                frames = dist.broadcast_object(grid.identify_window_chunks(frame_range, T, window_chunks, display=display))
+            display("We are initializing on a total of {} frames".format(len(frames)))
+            return frames, frame_range, window_chunks
+
         t0 = time.perf_counter()
-        movie = _Movie(ctx, dataset_obj, frame_batch_size, rows=(i_lo, i_hi) if dist.enabled else None, num_workers=num_workers)
+        if streamed:
+            movie = _StreamedMovie(ctx, dataset_obj, frame_batch_size, num_workers=num_workers)
+        else:
+            movie = _Movie(ctx, dataset_obj, frame_batch_size, rows=(i_lo, i_hi) if dist.enabled else None, num_workers=num_workers)
         Dl = movie.D   # resident pixels (= D unless distributed)
         lap("upload", t0)
         display("Computing Video Statistics")
@@ -506,18 +806,33 @@ def localmd_decomposition(
         t0 = time.perf_counter()
         mean_dev = torch.empty(Dl, dtype=torch.float32, device=ctx.device)
         std_dev = torch.empty(Dl, dtype=torch.float32, device=ctx.device)
-        ws = ctx.workspace(lib.pmd_stats_workspace_bytes(T, Dl, 1024))
-        ctx.call("pmd_stats", ptr(movie.dev), T, Dl, 1024, 1 if compute_normalizer else 0, ptr(mean_dev), ptr(std_dev),
-                 ptr(ws), ws.numel())
+        if streamed:
+            # the resident path's two np.random draws in its order (background sample, then the fit windows), made
+            # before pass 1 gathers those frames: a seeded call fits the same frames in both modes
+            sample = np.random.choice(list(range(T)), replace=False, size=min(1000, T)).tolist() if K > 0 else None
+            frames, frame_range, window_chunks = select_frames(frame_range, window_chunks)
+            r_fit = max(1, min(int(max_components), len(frames) // int(temporal_avg_factor)))
+            rpad_fit = int(lib.pmd_tile_rpad(r_fit))
+            dpad_fit = max(int(lib.pmd_tile_dpad(int(geo_blocks[0]) * int(geo_blocks[1]))), int(geo_blocks[0]) * int(geo_blocks[1]))
+            tile_bytes = _stream_tile_bytes(n1_geo * n2_geo, rpad_fit, dpad_fit, int(lib.pmd_time_ld(len(frames))),
+                                            int(lib.pmd_time_ld(movie.project_frames)), tile_batch_bytes)
+            movie.check_fit_frames(len(frames), len(sample or []), tile_bytes)
+            movie.first_pass(compute_normalizer, frames, sample, mean_dev, std_dev)
+        else:
+            ws = ctx.workspace(lib.pmd_stats_workspace_bytes(T, Dl, 1024))
+            ctx.call("pmd_stats", ptr(movie.dev), T, Dl, 1024, 1 if compute_normalizer else 0, ptr(mean_dev), ptr(std_dev),
+                     ptr(ws), ws.numel())
         display("Finished mean and noise variance")
-        lap("stats", t0)
+        lap("stream_stats" if streamed else "stats", t0)
 
         t0 = time.perf_counter()
-        K = int(background_rank)
         basis_dev = None
         if K > 0:
-            sample = dist.broadcast_object(np.random.choice(list(range(T)), replace=False, size=min(1000, T)).tolist())
-            xs_s, ld_s = movie.standardized(sample, mean_dev, std_dev)
+            if streamed:
+                xs_s, ld_s = movie.standardized("sample", mean_dev, std_dev)
+            else:
+                sample = dist.broadcast_object(np.random.choice(list(range(T)), replace=False, size=min(1000, T)).tolist())
+                xs_s, ld_s = movie.standardized(sample, mean_dev, std_dev)
             if dist.enabled:
                 # the (<= 1000 frame) sample is small: every rank contributes its owned pixels, all get the whole
                 # sample and compute the same basis (same counter-based test matrix)
@@ -531,20 +846,8 @@ def localmd_decomposition(
             del xs_s
         lap("background", t0)
 
-        # ---- frames to fit on (decomposition.py:678-693)
-        if window_chunks is None:
-            window_chunks = frame_range
-        if T < frame_range:
-            display("WARNING: Specified using more frames than there are in the dataset.")
-            frame_range = T
-            frames = list(range(T))
-            if frame_range <= window_chunks:
-                window_chunks = frame_range
-        else:
-            if frame_range <= window_chunks:
-                window_chunks = frame_range
-            frames = dist.broadcast_object(grid.identify_window_chunks(frame_range, T, window_chunks, display=display))
-        display("We are initializing on a total of {} frames".format(len(frames)))
+        if not streamed:
+            frames, frame_range, window_chunks = select_frames(frame_range, window_chunks)
         Tf = len(frames)
 
         block_sizes = grid.update_block_sizes(block_sizes, (d1, d2), display=display)
@@ -575,11 +878,16 @@ def localmd_decomposition(
         display("Loading Data")
         t0 = time.perf_counter()
         all_frames = frames == list(range(T))
-        xs_full, ld_T = movie.standardized(None, mean_dev, std_dev)
-        if all_frames:
-            xs_init, ld_f = xs_full, ld_T
+        if streamed:
+            # no full-movie copy: Z is formed from pass 2, in blocks whose leading dimension is ld_T
+            xs_full, ld_T = None, int(lib.pmd_time_ld(movie.project_frames))
+            xs_init, ld_f = movie.standardized("fit", mean_dev, std_dev)
         else:
-            xs_init, ld_f = movie.standardized(frames, mean_dev, std_dev)
+            xs_full, ld_T = movie.standardized(None, mean_dev, std_dev)
+            if all_frames:
+                xs_init, ld_f = xs_full, ld_T
+            else:
+                xs_init, ld_f = movie.standardized(frames, mean_dev, std_dev)
         pj_dev = None
         movie.release()      # the standardised copies are written: the raw frames are not read again
         # Memory plan for movies that fill the HBM (BASELINE configs 4 / 5: 84 GB): with every frame fitted the filtered
@@ -590,7 +898,9 @@ def localmd_decomposition(
         Tf_, Ta_ = len(frames), (len(frames) // int(temporal_avg_factor)) * int(temporal_avg_factor)
         if single_copy is None:
             single_copy = 4.0 * Dl * T > torch.cuda.get_device_properties(ctx.device).total_memory / 8.0
-        single_copy = bool(single_copy) and all_frames and K > 0 and pixel_weighting is None and Ta_ == Tf_
+        single_copy = bool(single_copy) and all_frames and K > 0 and pixel_weighting is None and Ta_ == Tf_ and not streamed
+        # streamed: nothing but the filter reads the standardised fit frames (Z comes from pass 2), so it filters in place
+        in_place = single_copy or streamed
         if K > 0:
             pj_dev = torch.zeros((K, ld_f), dtype=torch.float32, device=ctx.device)
             # projection on the background basis: a sum over pixels - owned pixels here, summed over the ranks
@@ -598,7 +908,7 @@ def localmd_decomposition(
             ctx.call("pmd_bg_project", ptr(xs_init[O_lo - P_lo:]), O_hi - O_lo, Tf, ld_f, ptr(basis_dev[O_lo:]), K, ptr(pj_dev),
                      ld_f, ptr(ws), ws.numel())
             dist.all_reduce(pj_dev)
-            if single_copy:
+            if in_place:
                 xf = xs_init                     # filtered in place (the kernel is element-wise)
                 xs_full = None
             else:
@@ -606,10 +916,12 @@ def localmd_decomposition(
                 if xf.shape[0] > Dl:
                     xf[Dl:].zero_()
             ctx.call("pmd_bg_filter", ptr(xs_init), ptr(xf), Dl, Tf, ld_f, ptr(basis_dev[P_lo:]), K, ptr(pj_dev), ld_f)
-            if single_copy:
+            if in_place:
                 xs_init = None
         else:
-            xf = xs_init.clone() if pixel_weighting is not None else xs_init
+            xf = xs_init.clone() if (pixel_weighting is not None and not streamed) else xs_init
+        if streamed:
+            xs_init = None
         if pixel_weighting is not None:
             pw = _f32(ctx, np.asarray(pixel_weighting, dtype=np.float32).reshape(-1)[P_lo:P_hi])
             ctx.call("pmd_scale_rows", ptr(xf), Dl, Tf, ld_f, ptr(pw))
@@ -769,6 +1081,8 @@ def localmd_decomposition(
         inv_cumw_host = np.ascontiguousarray(1.0 / cumw.reshape(-1))
         ctx.sync()
         lap("tiles", t0)
+        if streamed:
+            xf = None     # the filtered fit frames are read by the tile stage only (Z comes from pass 2)
         _dbg("ut", ut_dev); _dbg("tile_lambda", lam_dev)
 
         # ---- sparse assembly (decomposition.py:752-857): CSR arrays built on the device
@@ -921,6 +1235,8 @@ def localmd_decomposition(
             of its own run (it holds no other pixels); everywhere=True then collects all rows on every rank (the
             replicated global stage), otherwise a rank keeps only its own rows (row-sharded stage).  The K
             background rows are filled on every rank."""
+            if streamed:
+                return build_z_streamed()
             src = xf if xs_full is None else xs_full   # single-copy plan: the filtered movie + the rank-K term below
             z = torch.zeros((Rc, T), dtype=torch.float32, device=ctx.device)
             if n_loc > 0 and batched:
@@ -958,6 +1274,34 @@ def localmd_decomposition(
                              ptr(pj_full), ld_T, ptr(ws_), ws_.numel())
                     dist.all_reduce(pj_full)
                     z[Rt:Rt + K, :] = pj_full[:, :T]
+            return z
+
+        def build_z_streamed():
+            """Pass 2 of the streamed mode: Z[:, t0:t0+n] = (U W)^T X and B^T X of every block of frames, standardised
+            from the source as it is read again (single process: every tile, every pixel)."""
+            t_z = time.perf_counter()
+            z = torch.zeros((Rc, T), dtype=torch.float32, device=ctx.device)
+            tile_runs = (batches if batched else [(0, n_loc)]) if n_loc > 0 else []
+            ld_b = int(lib.pmd_time_ld(movie.project_frames))
+            proj = torch.empty((max([b - a for a, b in tile_runs] + [1]), 64, ld_b), dtype=torch.float32, device=ctx.device)
+            pj_b = torch.zeros((K, ld_b), dtype=torch.float32, device=ctx.device) if K > 0 else None
+            ws_ = ctx.workspace(lib.pmd_bg_project_workspace_bytes(D, movie.project_frames)) if K > 0 else None
+
+            def on_block(xs, ld, f0, n):
+                zc = z.view(-1)[f0:]         # column f0 of Z (leading dimension T)
+                for b0, b1_ in tile_runs:
+                    nb_ = b1_ - b0
+                    ctx.call("pmd_tiles_project_ranked", ptr(xs), ld, n, ptr(pix_loc_dev[b0:]), nb_, d, ptr(uw_dev[b0:]), dpad,
+                             ptr(proj), ld, 2, ptr(ranks_dev[b0:]))
+                    ctx.call("pmd_compact_rows", ptr(proj), ld, ptr(col_off_dev[b0:]), ptr(ranks_dev[b0:]), n, ptr(zc), T, nb_)
+                if K > 0:
+                    ctx.call("pmd_bg_project", ptr(xs), D, n, ld, ptr(basis_dev), K, ptr(pj_b), ld_b, ptr(ws_), ws_.numel())
+                    z[Rt:Rt + K, f0:f0 + n] = pj_b[:, :n]
+
+            movie.project(mean_dev, std_dev, on_block)
+            if return_diagnostics:
+                ctx.sync()
+            timings["stream_projection"] = timings.get("stream_projection", 0.0) + time.perf_counter() - t_z
             return z
 
         if use_right:
@@ -1133,7 +1477,7 @@ def localmd_decomposition(
             ctx.call("pmd_gram_u", ptr(uw_dev), dpad, b1, b2, ptr(pix_dev), ptr(pairs_dev), pairs.shape[0], ptr(origins_dev),
                      ptr(col_off_dev), ptr(ranks_dev), n_tiles, Rt, ptr(basis_dev), D, max(K, 0), ptr(G), Rc)
             _dbg("G", G)
-            if K > 0 and xs_full is None:
+            if K > 0 and single_copy:
                 bg_strip = G[Rt:Rt + K, :].clone()   # G is overwritten by the eigendecomposition
             P_dev, rp = _orthogonalize(ctx, G, Rc, None, m_cols, m_cols)
             del G
@@ -1360,6 +1704,7 @@ def localmd_decomposition(
             "orthogonalizer": ("cholesky" if (use_right and chol_ok) else "eigh"),
             "crop": crop, "dpad": dpad, "v_proj": Vp.cpu().numpy(), "eig_order": min(rp, T), "col_sigma": col_sigma, "n_tile_cols": Rt,
             "null_direction": dict(null_info, split_off=bool(null_tail)),
+            "streamed": bool(streamed), "stream_bytes_uploaded": int(movie.bytes_uploaded) if streamed else 0,
         }
         return final_movie, diag
     finally:
