@@ -93,6 +93,20 @@ int pmd_standardize_transpose_typed(pmd_ctx* ctx, const void* movie, int elem, l
 int pmd_gather_frames(pmd_ctx* ctx, const void* src, int elem, long D, const int* src_rows, const int* dst_rows, int n,
                       void* dst);
 
+/* Projection of raw frames on a stored spatial basis (pmd_loader.py:316-346, :393-414; localmd_amd/projection.py):
+ * Z[row][f] = sum_q A_g[row][q] * (Y[f][pix[pix_off + q]] - mean) / std for every group g and row < r_g, frames f < n
+ * of the frames-first batch Y (n x D, element type elem; converted to fp32 before (y - mean) / std).
+ * groups: device int64[n_groups][6] = {pix_off, p_g, a_off, out_row, r_g, to_ws}; pix: C-order pixel ids < D;
+ * A_g: round_up(r_g, 16) rows x round_up(p_g, 64) fp32 at A + a_off, row-major, zero padded.  to_ws = 0: the group
+ * writes rows out_row + row of Z (ld ldz >= n); 1: rows of the partial-sum workspace (n_partial_rows x n fp32), which
+ * the call then reduces: wide: device int64[n_wide_rows][4] = {z_row, ws_row0, parts, stride},
+ * Z[z_row][f] = sum_{c < parts} ws[ws_row0 + c stride][f] in order c = 0, 1, ...  The tables are trusted (the caller
+ * validates them); rows of Z outside every group are not written.  No synchronisation, no allocation. */
+size_t pmd_group_project_workspace_bytes(long n_partial_rows, int n);
+int pmd_group_project(pmd_ctx* ctx, const void* Y, int elem, int n, long D, const float* mean, const float* std,
+                      int n_groups, const long* groups, const int* pix, const float* A, long n_partial_rows,
+                      int n_wide_rows, const long* wide, float* Z, long ldz, void* ws, size_t ws_bytes);
+
 /* A2: background basis = rank-K rSVD of the standardised sample (pmd_loader.py:46-68, :300-314).
  * xs: pixel-major sample with round_up(D,1024) rows allocated (rows >= D zero). basis_out[c][k]. */
 size_t pmd_background_rsvd_workspace_bytes(long D, int n, int K);

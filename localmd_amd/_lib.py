@@ -37,6 +37,8 @@ SIGNATURES = {
     "pmd_stats_stream_finish": (c_i, [c_p, c_i, c_l, c_i, c_p, c_p, c_p, c_sz]),
     "pmd_standardize_transpose_typed": (c_i, [c_p, c_p, c_i, c_l, c_p, c_i, c_p, c_p, c_p, c_l]),
     "pmd_gather_frames": (c_i, [c_p, c_p, c_i, c_l, c_p, c_p, c_i, c_p]),
+    "pmd_group_project_workspace_bytes": (c_sz, [c_l, c_i]),
+    "pmd_group_project": (c_i, [c_p, c_p, c_i, c_i, c_l, c_p, c_p, c_i, c_p, c_p, c_p, c_l, c_i, c_p, c_p, c_l, c_p, c_sz]),
     "pmd_background_rsvd_workspace_bytes": (c_sz, [c_l, c_i, c_i]),
     "pmd_background_rsvd": (c_i, [c_p, c_p, c_l, c_i, c_l, c_i, c_u64, c_p, c_p, c_sz]),
     "pmd_bg_project_workspace_bytes": (c_sz, [c_l, c_i]),

@@ -25,6 +25,7 @@ class PMDArray:
         self._s = s
         self._v = v
         self._combined = None
+        self._groups = None    # group tables of U for project_frames (projection.py), built on first use
         self._dev = None
         self.mean_img = mean_img
         self.var_img = std_img  # NB: a noise *std* estimate, stored under the reference's name
@@ -127,6 +128,14 @@ class PMDArray:
             ctx.sync()
             out[f0:f0 + fn] = outc[:fn].cpu().numpy()
         return out.reshape((nf,) + fov).squeeze()
+
+    def project_frames(self, frames, *, frame_batch_size=10000, num_workers=0, device=None, ctx=None):
+        """(U R)^T ((frames - mean_img) / std_img): (rank, n) float32 for frames shaped (n, d1, d2) or (d1, d2), on the
+        GPU (projection.project_frames).  For the movie this decomposition was fitted on it is diag(s) Vt."""
+        from .projection import project_frames
+
+        return project_frames(self, frames, frame_batch_size=frame_batch_size, num_workers=num_workers, device=device,
+                              ctx=ctx)
 
     @property
     def _combined_temporal(self):
