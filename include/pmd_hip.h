@@ -317,6 +317,22 @@ int pmd_lag_moments(pmd_ctx* ctx, const float* A, const float* ref, long T, long
                     void* ws, size_t ws_bytes);
 int pmd_neighbour_image(pmd_ctx* ctx, const double* num, const double* den, long T, int d1, int d2, int kind, int mode, double* out);
 int pmd_lag_image(pmd_ctx* ctx, const double* moments, long D, long n, double* out);
+/* One-pass fit diagnostics (localmd_amd.diagnostic_images.make_pmd_diagnostic_images): the moments behind all four
+ * images of diagnostic_plots.py and the residual statistics from one read of the movie.  Per call, frames [c0, c0 + n)
+ * of a frames-first batch Y (element type elem, row 0 = frame ybase <= c0; converted to fp32) and of W (n x D fp32,
+ * row 0 = frame c0), the reconstruction std * (U R diag(s) Vt) without the mean; mean[D] = the decomposition's mean
+ * image.  With the residual r = (y - mean) - w: moments[35][D] += {neighbour moments of y (10), of w (10), of r (10),
+ * in the layout of pmd_neighbour_moments; lag moments of y (5) in the layout of pmd_lag_moments}, frame_ss[c0 + f] =
+ * sum over the pixels of r^2 (frame_ss has T entries).  Traces are shifted by their values in frame 0: ref[3][D] is
+ * written by the call with c0 = 0, which must come first.  c0 is a multiple of 512 and the calls come in frame order,
+ * so the fp64 sums are bitwise independent of the batching.  A lag pair whose earlier frame is before ybase reads it
+ * from ring (lag x D, element type elem, slot = frame mod lag), which the caller fills from the earlier batches.
+ * Finish with pmd_neighbour_image (kind 0 on moments, kind 1 on moments + 10 D / + 20 D with den = moments) and
+ * pmd_lag_image(moments + 30 D, n = T - lag).  No synchronisation, no allocation. */
+size_t pmd_diag_fused_workspace_bytes(int n, long D);
+int pmd_diag_fused_accumulate(pmd_ctx* ctx, const void* Y, int elem, long ybase, const float* W, const void* ring, int lag,
+                              long c0, int n, long T, int d1, int d2, const float* mean, float* ref, double* moments,
+                              double* frame_ss, void* ws, size_t ws_bytes);
 int pmd_transpose_affine(pmd_ctx* ctx, const float* src, long lds_, long rows, int cols, const float* scale,
                          const float* shift, float* dst, long ldd);
 

@@ -58,6 +58,8 @@ SIGNATURES = {
     "pmd_lag_moments": (c_i, [c_p, c_p, c_p, c_l, c_l, c_i, c_i, c_p, c_p, c_sz]),
     "pmd_neighbour_image": (c_i, [c_p, c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_p]),
     "pmd_lag_image": (c_i, [c_p, c_p, c_l, c_l, c_p]),
+    "pmd_diag_fused_workspace_bytes": (c_sz, [c_i, c_l]),
+    "pmd_diag_fused_accumulate": (c_i, [c_p, c_p, c_i, c_l, c_p, c_p, c_i, c_l, c_i, c_l, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_sz]),
     "pmd_transpose_affine": (c_i, [c_p, c_p, c_l, c_l, c_i, c_p, c_p, c_p, c_l]),
     "pmd_tiles_hook_offsets": (c_i, [c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_l, c_l, c_p, c_p]),
     "pmd_tiles_residual_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i, c_i, c_i, c_l]),

@@ -8,7 +8,12 @@ are not reproduced.  The reference loops over the pixels in Python and calls a j
 pair; here the frames stream through HBM once and two kernels (csrc/diag.hip) form every first and second moment, from
 which all four images follow.  Movies: anything that slices like a (T, d1, d2) array - NumPy arrays, torch tensors (host
 or device), a localmd_amd.PMDArray (expanded chunk by chunk).  Results: float64 (d1, d2) NumPy arrays, like the reference.
+
+make_pmd_diagnostic_images(movie, pmd) computes all four images of a decomposition at once, plus the residual statistics,
+reading the movie once in frame batches and reconstructing each batch on the device (csrc/diag_fused.hip).
 """
+from typing import NamedTuple
+
 import numpy as np
 
 from ._lib import Context, ptr
@@ -134,3 +139,247 @@ def make_autocorrelation_image(ctx, movie, lag: int = 1):
     ctx.call("pmd_lag_image", ptr(mom), D, T - lag, ptr(out))
     ctx.sync()
     return out.cpu().numpy().reshape(d1, d2)
+
+
+# ---- one-pass diagnostics of a decomposition against its movie ------------------------------------------------------
+DIAG_RECON_FRAMES = 2048    # frames per reconstruction block: bounds (R s) Vt, U (R s) Vt and its frames-first copy
+DIAG_FRAME_BLOCK = 512      # frames per fp64 partial of pmd_diag_fused_accumulate: blocks start on multiples of it
+DIAG_MOMENTS = 35           # 10 raw + 10 reconstruction + 10 residual neighbour moments, 5 raw lag moments
+
+
+class PMDDiagnostics(NamedTuple):
+    """Result of make_pmd_diagnostic_images.  The first four fields are in the argument order of the reference's
+    make_pmd_corr_diagnostic_plot (diagnostic_plots.py), so ``make_pmd_corr_diagnostic_plot(*d[:4])`` works."""
+    correlation: np.ndarray             # (d1, d2) make_correlation_image(movie, mode)
+    autocorrelation: np.ndarray         # (d1, d2) make_autocorrelation_image(movie, lag)
+    pmd_correlation: np.ndarray         # (d1, d2) make_pmd_correlation_image(movie, pmd_movie, mode)
+    residual_correlation: np.ndarray    # (d1, d2) make_residual_correlation_image(movie, pmd_movie, mode)
+    residual_std: np.ndarray            # (d1, d2) std over time (ddof 0) of movie - pmd_movie
+    explained_variance: np.ndarray      # (d1, d2) 1 - var(movie - pmd_movie) / var(movie); NaN where var(movie) = 0
+    frame_residual_rms: np.ndarray      # (T,) sqrt(mean over the pixels of (movie_t - pmd_movie_t)^2)
+
+
+def diag_plan(T, frame_batch_size):
+    """[(b0, b1, [(c0, c1), ...])]: the frame batches the movie is read in (those of the streamed decomposition, whole
+    1024-frame chunks) and the reconstruction blocks of each, at most DIAG_RECON_FRAMES frames, starting on multiples of
+    DIAG_FRAME_BLOCK."""
+    from .decomposition import _stream_batches, _stream_batch_frames
+
+    rb = min(_stream_batch_frames(frame_batch_size), DIAG_RECON_FRAMES)
+    return [(b0, b1, [(c0, min(b1, c0 + rb)) for c0 in range(b0, b1, rb)]) for b0, b1 in _stream_batches(T, frame_batch_size)]
+
+
+def _fused_workspace_bytes(n, D):
+    """pmd_diag_fused_workspace_bytes: the fp64 partials of the frame blocks and the per-frame residual sums."""
+    blocks = -(-int(n) // DIAG_FRAME_BLOCK)
+    return blocks * DIAG_MOMENTS * D * 8 + (-(-int(D) // 256)) * int(n) * 8
+
+
+def _diag_device_bytes(D, nb, esize, n_cols, rank, nnz, lag, n_batches, host_source, factors_on_device):
+    """(bytes, ring bytes) of device memory make_pmd_diagnostic_images holds for a movie of D pixels read in batches of
+    nb frames, besides the T doubles of frame_residual_rms: no term grows with the movie's length.  Batch buffers (two
+    for a host source, a converted copy at most for a device tensor), the Vt columns of one batch, one reconstruction
+    block ((R s) Vt, U (R s) Vt and its frames-first copy), the kernel workspace, the moments and the per-pixel
+    vectors, U and R s unless the PMDArray already holds them on the device, and the ring of `lag` raw frames for the
+    lag pairs that cross a batch boundary."""
+    rb = min(nb, DIAG_RECON_FRAMES)
+    ldc = (rb + 3) // 4 * 4
+    need = (2 if host_source and n_batches > 1 else 1) * nb * D * esize
+    need += 4 * (n_cols * ldc + D * ldc + rb * D)
+    need += _fused_workspace_bytes(rb, D) + DIAG_MOMENTS * D * 8 + 4 * D * 8 + (3 + 2 + 1) * D * 4
+    if not factors_on_device:
+        need += 4 * rank * nb + 8 * (D + 1) + 8 * nnz + 4 * n_cols * rank
+    ring = lag * D * esize if n_batches > 1 else 0
+    return need + ring, ring
+
+
+def _check_fit(need, ring, free, lag):
+    """ValueError before any allocation when the plan cannot fit; it names `lag` when the lag ring is what does not."""
+    if need <= free:
+        return
+    if need - ring <= free:
+        raise ValueError("make_pmd_diagnostic_images: the ring of lag = {} raw frames needs {:.2f} GB of device memory and "
+                         "does not fit ({:.2f} GB free besides the batches); use a smaller lag".format(lag, ring / 1e9,
+                                                                                                    (free - need + ring) / 1e9))
+    raise ValueError("make_pmd_diagnostic_images needs about {:.2f} GB of device memory, {:.2f} GB are free; lower "
+                     "frame_batch_size".format(need / 1e9, free / 1e9))
+
+
+def _check_args(original_movie, pmd, mode, lag):
+    from .pmdarray import PMDArray
+
+    if not isinstance(pmd, PMDArray):
+        raise TypeError("pmd must be a localmd_amd.PMDArray, got {}".format(type(pmd).__name__))
+    shape = tuple(int(x) for x in original_movie.shape)
+    if shape != tuple(pmd.shape):
+        raise ValueError("the movie has shape {}, the decomposition {}".format(shape, tuple(pmd.shape)))
+    if mode not in ("max", "mean"):
+        raise ValueError(f"mode {mode} not supported")
+    if isinstance(lag, bool) or int(lag) != lag:
+        raise ValueError("lag must be an integer, got {!r}".format(lag))
+    lag = int(lag)
+    if lag < 1 or lag >= shape[0]:
+        raise ValueError("lag must be in [1, frames): lag = {}, {} frames".format(lag, shape[0]))
+    return shape, lag
+
+
+def make_pmd_diagnostic_images(original_movie, pmd, *, mode="max", lag=1, frame_batch_size=10000, num_workers=0,
+                               device=None, ctx=None):
+    """All four diagnostic images of a decomposition (make_correlation_image, make_autocorrelation_image,
+    make_pmd_correlation_image and make_residual_correlation_image with pmd_movie = pmd[:]) plus the residual
+    statistics, from ONE read of ``original_movie``.  Returns a PMDDiagnostics.
+
+    ``pmd`` is a PMDArray; after ``pmd.to_device()`` its context and uploaded factors are reused.  Sources: NumPy arrays
+    and memmaps, any lazy_data_loader (TiffArray included) and CPU tensors, read in ``frame_batch_size`` batches (rounded
+    down to whole 1024-frame chunks) through the pinned staging ring of the streamed decomposition, uint16 / int16 in their
+    own dtype; device tensors are sliced in place with the same batches.  Each batch is reconstructed on the device
+    ((R s) Vt[:, batch] with pmd_gemm, then U and the noise image with the expansion kernels) and one fused kernel forms
+    the moments of the movie, the reconstruction and the residual; device memory does not grow with the movie's length
+    except for the T doubles of frame_residual_rms."""
+    import torch
+    from ._lib import Context
+    from .decomposition import _device_free_bytes, _stream_dtype
+    from .projection import _device_elem
+
+    (T, d1, d2), lag = _check_args(original_movie, pmd, mode, lag)
+    D = d1 * d2
+    plan = diag_plan(T, frame_batch_size)
+    nb = plan[0][1] - plan[0][0]
+    rb = min(nb, DIAG_RECON_FRAMES)
+    ldc = (rb + 3) // 4 * 4
+    n_cols, rank = (int(x) for x in pmd.r.shape)
+    on_device = isinstance(original_movie, torch.Tensor) and original_movie.device.type != "cpu"
+    if on_device:
+        esize = original_movie.element_size() if _device_elem(original_movie[:0]) is not None else 4
+    else:
+        esize = _stream_dtype(original_movie.detach().numpy() if isinstance(original_movie, torch.Tensor)
+                              else original_movie).itemsize
+    dv = getattr(pmd, "_dev", None)
+    own = False
+    if dv is not None:
+        ctx = dv["ctx"]
+    elif ctx is None:
+        ctx = Context(0 if device is None else int(device))
+        own = True
+    try:
+        need, ring_bytes = _diag_device_bytes(D, nb, esize, n_cols, rank, int(pmd.u.nnz), lag, len(plan), not on_device,
+                                              dv is not None)
+        _check_fit(need + 8 * T, ring_bytes, _device_free_bytes(ctx.device), lag)
+        return _diagnostics(ctx, original_movie, pmd, dv, plan, T, d1, d2, mode, lag, rb, ldc, n_cols, rank,
+                            frame_batch_size, num_workers, on_device)
+    finally:
+        if own:
+            ctx.close()
+
+
+def _diagnostics(ctx, movie, pmd, dv, plan, T, d1, d2, mode, lag, rb, ldc, n_cols, rank, frame_batch_size, num_workers,
+                 on_device):
+    import ctypes as C
+
+    import torch
+    from ._lib import ptr
+    from .decomposition import _StreamedMovie
+    from .projection import _device_elem
+
+    dev = ctx.device
+    D = d1 * d2
+    f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)   # noqa: E731
+    mean = f32(np.asarray(pmd.mean_img).reshape(-1))
+    std = f32(np.asarray(pmd.var_img).reshape(-1))
+    # U row of C-order pixel c (the decomposition's pixel order), as PMDArray._getitem_device selects them
+    sel = torch.from_numpy(np.ascontiguousarray(pmd.row_indices.reshape(-1), dtype=np.int32)).to(dev)
+    if dv is not None:
+        indptr, indices, data, rs, vt_all = dv["indptr"], dv["indices"], dv["data"], dv["rs"], dv["v"]
+    else:
+        u = pmd.u
+        indptr = torch.from_numpy(u.indptr.astype(np.int64)).to(dev)
+        indices = torch.from_numpy(u.indices.astype(np.int32)).to(dev)
+        data = f32(u.data)
+        rs = f32(pmd.r * pmd.s[None, :])
+        vt_all = None
+    expand = rank > 0 and n_cols > 0
+    ct = torch.zeros((n_cols, ldc), dtype=torch.float32, device=dev) if expand else None
+    acc = torch.empty((D, ldc), dtype=torch.float32, device=dev) if expand else None
+    W = torch.empty((rb, D), dtype=torch.float32, device=dev)
+    ws = torch.empty(int(ctx.lib.pmd_diag_fused_workspace_bytes(rb, D)), dtype=torch.uint8, device=dev)
+    mom = torch.zeros((DIAG_MOMENTS, D), dtype=torch.float64, device=dev)
+    ref = torch.empty((3, D), dtype=torch.float32, device=dev)
+    fss = torch.empty(T, dtype=torch.float64, device=dev)
+    st = {"ring": None, "vt": None, "pin": [None, None], "ev": [None, None], "k": 0}
+    last_b0 = plan[-1][0]
+    blocks = {b0: cb for b0, _, cb in plan}
+
+    def vt_batch(b0, n):
+        """(device pointer of Vt[:, b0], leading dimension): the whole Vt of a to_device() PMDArray, else the batch's
+        columns uploaded through two page-locked buffers."""
+        if vt_all is not None:
+            return vt_all[:, b0:].data_ptr(), T
+        j = st["k"] % 2
+        st["k"] += 1
+        if st["pin"][j] is None or st["pin"][j].numel() < rank * n:
+            st["pin"][j] = torch.empty(rank * n, dtype=torch.float32, pin_memory=True)
+        elif st["ev"][j] is not None:
+            st["ev"][j].synchronize()           # the upload that last read this buffer has finished
+        np.copyto(st["pin"][j][:rank * n].numpy().reshape(rank, n), pmd.v[:, b0:b0 + n], casting="unsafe")
+        if st["vt"] is None or st["vt"].numel() < rank * n:
+            st["vt"] = torch.empty(rank * n, dtype=torch.float32, device=dev)
+        st["vt"][:rank * n].copy_(st["pin"][j][:rank * n], non_blocking=True)
+        st["ev"][j] = torch.cuda.Event()
+        st["ev"][j].record(torch.cuda.current_stream(dev))
+        return st["vt"].data_ptr(), n
+
+    def consume(batch, elem, b0, n):
+        esize = batch.element_size()
+        if expand:
+            vp, ldv = vt_batch(b0, n)
+        for c0, c1 in blocks[b0]:
+            m = c1 - c0
+            if expand:
+                m4 = min((m + 3) // 4 * 4, ldc)
+                ctx.call("pmd_gemm", 0, 0, n_cols, m, rank, 1.0, ptr(rs), rank, C.c_void_p(vp + 4 * (c0 - b0)), ldv, 0.0,
+                         ptr(ct), ldc)
+                ctx.call("pmd_csr_rows_spmm", ptr(indptr), ptr(indices), ptr(data), ptr(sel), D, ptr(ct), ldc, m4, ptr(acc),
+                         ldc)
+                ctx.call("pmd_transpose_affine", ptr(acc), ldc, D, m, ptr(std), None, ptr(W), D)
+            else:
+                W[:m].zero_()
+            ctx.call("pmd_diag_fused_accumulate", ptr(batch), int(elem), b0, ptr(W), ptr(st["ring"]), lag, c0, m, T, d1, d2,
+                     ptr(mean), ptr(ref), ptr(mom), ptr(fss), ptr(ws), ws.numel())
+        if b0 != last_b0:
+            # the last `lag` frames read so far go to ring slot (frame mod lag) for the pairs of the next batches
+            if st["ring"] is None:
+                st["ring"] = torch.empty((lag, D), dtype=batch.dtype, device=dev)
+            rb8, bb8 = st["ring"].view(torch.uint8), batch.reshape(n, D).view(torch.uint8)
+            t = max(b0, b0 + n - lag)
+            while t < b0 + n:
+                s = t % lag
+                k = min(b0 + n - t, lag - s)
+                rb8[s:s + k].copy_(bb8[t - b0:t - b0 + k])
+                t += k
+
+    if on_device:
+        for b0, b1, _ in plan:
+            b = movie[b0:b1].to(dev).reshape(b1 - b0, D)
+            elem = _device_elem(b)
+            if elem is None:
+                b, elem = b.to(torch.float32), 0
+            consume(b.contiguous(), elem, b0, b1 - b0)
+    else:
+        src = _StreamedMovie(ctx, movie, frame_batch_size, num_workers=num_workers)
+        src.run_pass(lambda batch, b0, n: consume(batch, src.elem, b0, n))
+
+    img = torch.empty((4, D), dtype=torch.float64, device=dev)
+    m_code = 0 if mode == "max" else 1
+    ctx.call("pmd_neighbour_image", ptr(mom[0]), None, T, d1, d2, 0, m_code, ptr(img[0]))
+    ctx.call("pmd_lag_image", ptr(mom[30]), D, T - lag, ptr(img[1]))
+    ctx.call("pmd_neighbour_image", ptr(mom[10]), ptr(mom[0]), T, d1, d2, 1, m_code, ptr(img[2]))
+    ctx.call("pmd_neighbour_image", ptr(mom[20]), ptr(mom[0]), T, d1, d2, 1, m_code, ptr(img[3]))
+    # residual statistics from the shifted residual sums (shift invariant); the per-frame sums are unshifted
+    var_y = ((mom[1] - mom[0] * mom[0] / T) / T).clamp_min(0.0)
+    var_r = ((mom[21] - mom[20] * mom[20] / T) / T).clamp_min(0.0)
+    ev = torch.where(var_y > 0, 1.0 - var_r / torch.where(var_y > 0, var_y, 1.0), torch.full_like(var_y, float("nan")))
+    rms = torch.sqrt(fss / D)
+    res = torch.stack([var_r.sqrt(), ev])
+    ctx.sync()
+    img, res, rms = img.cpu().numpy(), res.cpu().numpy(), rms.cpu().numpy()
+    return PMDDiagnostics(*(img[k].reshape(d1, d2) for k in range(4)), res[0].reshape(d1, d2), res[1].reshape(d1, d2), rms)
