@@ -107,6 +107,22 @@ int pmd_group_project(pmd_ctx* ctx, const void* Y, int elem, int n, long D, cons
                       int n_groups, const long* groups, const int* pix, const float* A, long n_partial_rows,
                       int n_wide_rows, const long* wide, float* Z, long ldz, void* ws, size_t ws_bytes);
 
+/* Fused expansion of a decomposition into output frames (localmd_amd/export.py): for the n frames of one call,
+ *   x[f][c] = mean[c] + std[c] * sum_e sum_{k < r_e} A[a_off_e + k p64_e + qmap[64 e + c mod 64]] * C[c_row0_e + k][f]
+ * over the entries e of patch c / 64 (patch_ptr[patch] <= e < patch_ptr[patch + 1], n_patches = ceil(d1 d2 / 64)),
+ * entries: device int64[n_entries][4] = {a_off, p64, r (1..64), c_row0}; qmap: int32[n_entries][64] with -1 for a
+ * pixel outside the entry's group; A: the group blocks of pmd_group_project (rows padded to 16).  C: rows x ldc fp32,
+ * column f = frame f of the call.  Y: the raw frames-first batch (element type y_elem, ldy >= d1 d2 elements per frame,
+ * frame f of the call at Y + f ldy), read only when a panel needs it.  Panel p (< n_panels <= 3) is
+ * (panels >> 2p) & 3: 0 raw y, 1 denoised x, 2 residual y - x (from the rounded x); out (element type out_elem,
+ * frame f at out + f d1 n_panels d2 elements) gets out[f][i][p d2 + j] for pixel c = i d2 + j.  Integer outputs round
+ * half to even and saturate, NaN -> 0.  The tables are trusted (the caller validates them).  Frame f's bits do not
+ * depend on n or on the call it comes in.  No synchronisation, no allocation, no workspace. */
+int pmd_group_expand(pmd_ctx* ctx, const float* C, long ldc, int n, int d1, int d2, const float* mean, const float* std,
+                     long n_patches, const long* patch_ptr, long n_entries, const long* entries, const int* qmap,
+                     const float* A, const void* Y, int y_elem, long ldy, int n_panels, int panels, void* out,
+                     int out_elem);
+
 /* A2: background basis = rank-K rSVD of the standardised sample (pmd_loader.py:46-68, :300-314).
  * xs: pixel-major sample with round_up(D,1024) rows allocated (rows >= D zero). basis_out[c][k]. */
 size_t pmd_background_rsvd_workspace_bytes(long D, int n, int K);

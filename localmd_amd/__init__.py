@@ -8,11 +8,12 @@ from .pmdarray import PMDArray, save_npz, load_npz
 from .dataset import TiffArray, lazy_data_loader, ArrayDataset
 from .projection import project_movie
 from .diagnostic_images import make_pmd_diagnostic_images
+from .export import export_movie
 
 PMDDataset = lazy_data_loader  # the name the reference's README uses (README.md:67)
 
 __all__ = [
     "localmd_decomposition", "compute_lowrank_factorized_svd", "projected_svd", "PMDArray", "TiffArray",
     "lazy_data_loader", "PMDDataset", "ArrayDataset", "save_npz", "load_npz",
-    "project_movie", "make_pmd_diagnostic_images",
+    "project_movie", "make_pmd_diagnostic_images", "export_movie",
 ]

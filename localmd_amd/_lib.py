@@ -39,6 +39,8 @@ SIGNATURES = {
     "pmd_gather_frames": (c_i, [c_p, c_p, c_i, c_l, c_p, c_p, c_i, c_p]),
     "pmd_group_project_workspace_bytes": (c_sz, [c_l, c_i]),
     "pmd_group_project": (c_i, [c_p, c_p, c_i, c_i, c_l, c_p, c_p, c_i, c_p, c_p, c_p, c_l, c_i, c_p, c_p, c_l, c_p, c_sz]),
+    "pmd_group_expand": (c_i, [c_p, c_p, c_l, c_i, c_i, c_i, c_p, c_p, c_l, c_p, c_l, c_p, c_p, c_p, c_p, c_i, c_l, c_i, c_i,
+                               c_p, c_i]),
     "pmd_background_rsvd_workspace_bytes": (c_sz, [c_l, c_i, c_i]),
     "pmd_background_rsvd": (c_i, [c_p, c_p, c_l, c_i, c_l, c_i, c_u64, c_p, c_p, c_sz]),
     "pmd_bg_project_workspace_bytes": (c_sz, [c_l, c_i]),

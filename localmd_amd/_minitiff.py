@@ -270,47 +270,131 @@ class MiniTiff:
         return out
 
 
+_TIFF_TAGS = 10     # entries of every IFD written here
+
+
+def tiff_needs_bigtiff(n_frames, h, w, itemsize):
+    """True when an uncompressed one-strip-per-page file of these frames does not fit in classic TIFF (the rule
+    write_tiff has always used: 256 bytes of headroom per page and 1 MiB below the 4 GiB offset limit)."""
+    return int(n_frames) * (int(h) * int(w) * int(itemsize) + 256) > (1 << 32) - (1 << 20)
+
+
+class TiffWriter:
+    """Streaming writer of an uncompressed little-endian multipage TIFF, one strip per page.  The total shape and the
+    dtype are given up front; ``write(frames)`` then takes the frames in order, ``(k, h, w)`` (or one ``(h, w)`` frame)
+    per call, any k.  For the same frames and BigTIFF choice the file is byte-identical to write_tiff's.
+
+    ``bigtiff``: None chooses as write_tiff does (tiff_needs_bigtiff); False on frames that do not fit raises ValueError
+    before the file is created.  ``close()`` checks that every frame arrived; ``abort()`` (also on an exception inside
+    a ``with`` block) closes and removes the file."""
+
+    def __init__(self, filename, shape, dtype, bigtiff=None):
+        dtype = np.dtype(dtype)
+        if dtype.kind not in "uif":
+            raise ValueError("TiffWriter: unsupported dtype {}".format(dtype))
+        if len(shape) != 3:
+            raise ValueError("TiffWriter: expected a (T, h, w) shape, got {}".format(tuple(shape)))
+        T, h, w = (int(x) for x in shape)
+        need = tiff_needs_bigtiff(T, h, w, dtype.itemsize)
+        if bigtiff is None:
+            bigtiff = need
+        elif not bigtiff and need:
+            raise ValueError("{} frames of {} x {} {} do not fit in a classic TIFF (4 GiB); use bigtiff=True or "
+                             "bigtiff=None".format(T, h, w, dtype))
+        self.filename = filename
+        self.shape = (T, h, w)
+        self.big = bool(bigtiff)
+        self._le = dtype.newbyteorder("<")
+        self._kind = {"u": 1, "i": 2, "f": 3}[dtype.kind]
+        self._bits = dtype.itemsize * 8
+        self._page_bytes = h * w * dtype.itemsize
+        self._ifd_size = (8 + _TIFF_TAGS * 20 + 8) if self.big else (2 + _TIFF_TAGS * 12 + 4)
+        self._t = 0
+        self._f = open(filename, "wb")
+        if self.big:
+            self._f.write(struct.pack("<2sHHHQ", b"II", 43, 8, 0, 16))
+        else:
+            self._f.write(struct.pack("<2sHI", b"II", 42, 8))
+        self._pos = self._f.tell()
+
+    def _ifd(self, t):
+        big, T, h, w = self.big, *self.shape
+        entries = [
+            (256, 4, w), (257, 4, h), (258, 3, self._bits), (259, 3, 1), (262, 3, 1),
+            (273, 16 if big else 4, None), (277, 3, 1), (278, 4, h),
+            (279, 16 if big else 4, self._page_bytes), (339, 3, self._kind),
+        ]
+        data_off = self._pos + self._ifd_size
+        next_ifd = data_off + self._page_bytes if t + 1 < T else 0
+        out = [struct.pack("<Q", len(entries)) if big else struct.pack("<H", len(entries))]
+        for tag, typ, val in entries:
+            if val is None:
+                val = data_off
+            if big:
+                out.append(struct.pack("<HHQ", tag, typ, 1) + struct.pack("<" + {3: "H6x", 4: "I4x", 16: "Q"}[typ], val))
+            else:
+                out.append(struct.pack("<HHI", tag, typ, 1) + struct.pack("<" + {3: "H2x", 4: "I"}[typ], val))
+        out.append(struct.pack("<Q" if big else "<I", next_ifd))
+        self._pos = data_off + self._page_bytes
+        return b"".join(out)
+
+    def write(self, frames):
+        """Append frames (k, h, w), or one (h, w) frame, after those already written."""
+        frames = np.asarray(frames)
+        if frames.ndim == 2:
+            frames = frames[None]
+        T, h, w = self.shape
+        if frames.ndim != 3 or frames.shape[1:] != (h, w):
+            raise ValueError("TiffWriter: frames of shape {} do not match pages of {} x {}".format(frames.shape, h, w))
+        k = frames.shape[0]
+        if self._t + k > T:
+            raise ValueError("TiffWriter: {} frames past the {} declared".format(self._t + k - T, T))
+        data = np.ascontiguousarray(frames.astype(self._le, copy=False))
+        f = self._f
+        for u in range(k):
+            f.write(self._ifd(self._t + u))
+            f.write(memoryview(data[u]).cast("B"))
+        self._t += k
+
+    def close(self):
+        """Finish the file; ValueError (and the file removed) unless every declared frame was written."""
+        if self._f is None:
+            return
+        if self._t != self.shape[0]:
+            missing = self.shape[0] - self._t
+            self.abort()
+            raise ValueError("TiffWriter: closed with {} of {} frames missing".format(missing, self.shape[0]))
+        self._f.close()
+        self._f = None
+
+    def abort(self):
+        """Close and remove the file (an export that failed midway leaves nothing behind)."""
+        import os
+
+        if self._f is not None:
+            self._f.close()
+            self._f = None
+        try:
+            os.remove(self.filename)
+        except FileNotFoundError:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is not None:
+            self.abort()
+        else:
+            self.close()
+        return False
+
+
 def write_tiff(filename, frames: np.ndarray):
     """Write a (T, h, w) array as an uncompressed little-endian multipage TIFF (BigTIFF when
     the data exceed 4 GiB).  One strip per page."""
     frames = np.ascontiguousarray(frames)
     if frames.ndim != 3:
         raise ValueError("expected (T, h, w)")
-    kind = {"u": 1, "i": 2, "f": 3}[frames.dtype.kind]
-    bits = frames.dtype.itemsize * 8
-    T, h, w = frames.shape
-    page_bytes = h * w * frames.dtype.itemsize
-    big = T * (page_bytes + 256) > (1 << 32) - (1 << 20)
-    data = frames.astype(frames.dtype.newbyteorder("<"), copy=False)
-    with open(filename, "wb") as f:
-        if big:
-            f.write(struct.pack("<2sHHHQ", b"II", 43, 8, 0, 16))
-        else:
-            f.write(struct.pack("<2sHI", b"II", 42, 8))
-        pos = f.tell()
-        for t in range(T):
-            entries = [
-                (256, 4, w), (257, 4, h), (258, 3, bits), (259, 3, 1), (262, 3, 1),
-                (273, 16 if big else 4, None), (277, 3, 1), (278, 4, h),
-                (279, 16 if big else 4, page_bytes), (339, 3, kind),
-            ]
-            n = len(entries)
-            ifd_size = (8 + n * 20 + 8) if big else (2 + n * 12 + 4)
-            data_off = pos + ifd_size
-            next_ifd = data_off + page_bytes if t + 1 < T else 0
-            if big:
-                f.write(struct.pack("<Q", n))
-            else:
-                f.write(struct.pack("<H", n))
-            for tag, typ, val in entries:
-                if val is None:
-                    val = data_off
-                if big:
-                    f.write(struct.pack("<HHQ", tag, typ, 1))
-                    f.write(struct.pack("<" + {3: "H6x", 4: "I4x", 16: "Q"}[typ], val))
-                else:
-                    f.write(struct.pack("<HHI", tag, typ, 1))
-                    f.write(struct.pack("<" + {3: "H2x", 4: "I"}[typ], val))
-            f.write(struct.pack("<Q" if big else "<I", next_ifd))
-            f.write(data[t].tobytes())
-            pos = data_off + page_bytes
+    with TiffWriter(filename, frames.shape, frames.dtype) as tw:
+        tw.write(frames)

@@ -137,6 +137,13 @@ class PMDArray:
         return project_frames(self, frames, frame_batch_size=frame_batch_size, num_workers=num_workers, device=device,
                               ctx=ctx)
 
+    def export(self, out, movie=None, **kw):
+        """Write the denoised movie (or raw / denoised / residual panels side by side) to a file or array, streamed
+        through the GPU (export.export_movie; same keywords)."""
+        from .export import export_movie
+
+        return export_movie(self, out, movie, **kw)
+
     @property
     def _combined_temporal(self):
         """(R * s) V, built on first use and cached: __getitem__ is then one sparse-dense product
