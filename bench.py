@@ -4,12 +4,16 @@ Headline benchmark: frames/sec of the full PMD decomposition (BASELINE.json metr
 synthetic 512x512x10000 fp32 movie, 20x20 blocks, reference-default arguments, movie resident
 in HBM when the clock starts, results (CSR U, R, s, Vt, mean, std) on the host when it stops.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME] [--no-cpu-baseline] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-host-input]]
 
-One "step" = one complete decomposition.  Rank 0 prints ONE JSON line carrying the metric,
-`roofline` (dominant hand-written kernel, timed with HIP events on its stream) and
-`cpu_baseline` (the CPU oracle timed on a bounded crop of the same movie, rank 0, N=1 only).
+One "step" = one complete decomposition.  Rank 0 prints ONE JSON line carrying the metric.  A plain run does only what
+that needs: set-up, warm-up, the timed steps, the dump if asked for, the line.
 --dump-outputs DIR writes the PMDArray of the last timed step as DIR/<name>.npy (see dump_outputs).
+--full adds, after the timed steps and outside them: one instrumented step (per-phase and per-kernel times, tile
+statistics, `roofline` / `roofline_mfma` of the two dominant hand-written kernels, timed with HIP events on their stream),
+the same decomposition handed a host array (`frames_per_s_from_host_array`, N=1 only) and `cpu_baseline` (the CPU oracle
+timed on a bounded crop of the same movie, rank 0, N=1 only).
 """
 import argparse
 import json
@@ -39,7 +43,7 @@ CONFIGS = {
     "2048x2048x5000_b16": dict(T=5000, d1=2048, d2=2048, block=16, frames=5000, max_components=50, one_shot=True),
 }
 DEFAULT_CONFIG = "512x512x10000_b20"
-FP32_MFMA_PEAK_TFLOPS = 157.3  # /opt/skills/guides/MI355X_MICROARCH.md, dense f32 matrix peak
+FP32_MFMA_PEAK_TFLOPS = 157.3  # MI355X dense f32 matrix peak
 HBM_PEAK_GBS = 8000.0
 DUMP_ARRAY_BYTES = 6 << 20     # per dumped array; the dozen arrays of dump_outputs stay below DUMP_TOTAL_BYTES
 DUMP_TOTAL_BYTES = 64 << 20
@@ -183,14 +187,103 @@ def cpu_baseline(cfg, movie_dev, seed):
             "cpu_seconds_estimated_full_workload": total}
 
 
+def rooflines(workload, cfg, diag, prof):
+    """The two roofline objects of a --full bench line, from the diagnostics and the per-kernel HIP-event times of the
+    instrumented step: (`roofline` = the dominant kernel by time, `roofline_mfma` = tile_atx)."""
+    # roofline of the dominant hand-written kernel: tile_atx (four launches per step: V_ds = U_ds^T X,
+    # W = U0^T X, the sketch Q^T A and the full-movie projection U^T X).  Algorithmic work per launch
+    # (DESIGN.md): flops = 2 * r * d * T per tile with r = max_components (not the padded 64 rows).
+    n_tiles = len(diag["tile_ranks"])
+    d = cfg["block"] ** 2
+    r = diag["max_components"]
+    crop = diag["crop"]
+    # "tile_atx_main" = the d x T launches only (V_ds, W, and the two projections U^T X of the fit and of the
+    # whole movie); the small sketch / simulation / background launches are timed under "tile_atx".
+    atx_ms, atx_n = prof.get("tile_atx_main", (0.0, 0))
+    flops_per_launch = 2.0 * r * d * crop * n_tiles
+    bytes_per_launch = 4.0 * d * crop * n_tiles
+    avg_ms = atx_ms / max(atx_n, 1)
+    achieved = flops_per_launch / (avg_ms * 1e-3) / 1e12 if avg_ms > 0 else 0.0
+    roofline = {
+        "kernel": "tile_atx (v_mfma_f32_16x16x4_f32)", "bound": "mfma", "achieved": achieved,
+        "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": achieved / FP32_MFMA_PEAK_TFLOPS, "traffic": None,
+        "avg_launch_ms": avg_ms, "launches_timed": atx_n, "algorithmic_gflop_per_launch": flops_per_launch / 1e9,
+        "algorithmic_gb_per_launch": bytes_per_launch / 1e9,
+        "hbm_gbs_equiv": bytes_per_launch / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0,
+    }
+    # HBM-side traffic of the same launch from the committed counter pass; valid for the workload it was taken on and while
+    # the kernel source is unchanged (SHA-256 recorded with the pass)
+    try:
+        import hashlib
+
+        root = os.path.dirname(os.path.abspath(__file__))
+        pmc = json.load(open(os.path.join(root, "profiles", "r03_pmc_tile_atx.json")))
+        sha = hashlib.sha256(open(os.path.join(root, pmc["kernel_source"]), "rb").read()).hexdigest()
+        if workload != DEFAULT_CONFIG:
+            roofline["traffic_note"] = "no counter pass for this workload"
+        elif sha != pmc["kernel_source_sha256"]:
+            roofline["traffic_note"] = "stale: the kernel source changed since the counter pass (profiles/r03_pmc_tile_atx.json)"
+        else:
+            roofline["traffic"] = pmc["fetch_bytes_per_launch"] / 1e9
+            roofline["traffic_unit"] = "GB per launch (L2 -> fabric reads, Infinity Cache hits included)"
+            roofline["traffic_source"] = "profiles/r03_pmc_tile_atx.json (separate rocprofv3 --pmc FETCH_SIZE pass, gfx950 x2 correction)"
+    except (OSError, KeyError, ValueError):
+        roofline["traffic_note"] = "no committed counter pass found"
+    roofline_mfma = roofline
+    # Dominant kernel by time: sytrd_symv (triangle matrix-vector product of the tridiagonalisation behind the
+    # final SVD, one launch per column of the min(R', T)-sized Gram matrix).  Algorithmic bytes per launch =
+    # 4 B x the n'(n'+1)/2 entries of the trailing triangle (n' = n - j - 1); with profiling on, the library
+    # times every 64th launch (j = 32, 96, ...) on its stream: average bytes / average duration of that sample.
+    sv_ms, sv_n = prof.get("sytrd_symv_sample", (0.0, 0))
+    n_eig = int(diag["eig_order"])
+    if sv_n > 0:
+        js = np.arange(32, n_eig - 1, 64, dtype=np.float64)
+        npr = n_eig - js - 1
+        avg_bytes = float(np.mean(4.0 * npr * (npr + 1) / 2))
+        avg_sv_ms = sv_ms / sv_n
+        ach = avg_bytes / (avg_sv_ms * 1e-3) / 1e9
+        roofline = {
+            "kernel": "sytrd_symv (triangle symv of the Householder tridiagonalisation, fp32)", "bound": "hbm",
+            "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS, "traffic": None,
+            "avg_launch_ms": avg_sv_ms, "launches_timed": sv_n, "launches_per_step": n_eig - 1,
+            "algorithmic_mb_per_launch": avg_bytes / 1e6, "matrix_order": n_eig,
+        }
+        # fabric-side traffic of the same launches from the committed PMC pass (profiles/r03_pmc_sytrd_n10000.json:
+        # separate rocprofv3 --pmc FETCH_SIZE run over one n = 10^4 tridiagonalisation, gfx950 x2 correction applied,
+        # mean over the launches j = 32, 96, ... that are timed here); only valid for a matrix of that order
+        # A counter pass cannot run inside this process (rocprofv3 wraps the program), so the figure is the committed
+        # one - valid only for a matrix of that order AND while the kernel's source is the file it was measured on
+        # (SHA-256 recorded with the pass); otherwise `traffic` stays null and says why.
+        try:
+            import hashlib
+
+            root = os.path.dirname(os.path.abspath(__file__))
+            pmc = json.load(open(os.path.join(root, "profiles", "r03_pmc_sytrd_n10000.json")))
+            sha = hashlib.sha256(open(os.path.join(root, pmc["kernel_source"]), "rb").read()).hexdigest()
+            if abs(n_eig - pmc["matrix_order"]) > 1:
+                roofline["traffic_note"] = "no counter pass for a matrix of this order"
+            elif sha != pmc["kernel_source_sha256"]:
+                roofline["traffic_note"] = "stale: the kernel source changed since the counter pass (profiles/r03_pmc_sytrd_n10000.json)"
+            else:
+                roofline["traffic"] = pmc["traffic_bytes_per_launch_sample_mean"] / 1e9
+                roofline["traffic_unit"] = "GB per launch (L2 -> fabric reads, Infinity Cache hits included)"
+                roofline["traffic_over_algorithmic"] = pmc["traffic_over_algorithmic_sample"]
+                roofline["traffic_source"] = "profiles/r03_pmc_sytrd_n10000.json (separate rocprofv3 --pmc FETCH_SIZE pass, gfx950 x2 correction)"
+        except (OSError, KeyError, ValueError):
+            roofline["traffic_note"] = "no committed counter pass found"
+    return roofline, roofline_mfma
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default=DEFAULT_CONFIG, choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-input", action="store_true", help="skip the extra run that starts from a host array")
+    ap.add_argument("--full", action="store_true",
+                    help="also the instrumented step (phases, kernel times, rooflines), the host-array run and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-host-input", action="store_true", help="with --full: skip the extra run that starts from a host array")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the result of the last timed step as DIR/<name>.npy (at most 64 MB, see dump_outputs)")
     args = ap.parse_args()
@@ -267,7 +360,7 @@ def main():
         torch.cuda.synchronize()
 
     # The timed steps run WITHOUT the library's HIP-event profiling (round-2 verdict: measurement overhead does not
-    # belong in the headline number); the per-kernel times and both roofline objects come from the one extra,
+    # belong in the headline number); with --full, the per-kernel times and both roofline objects come from the one extra,
     # untimed, instrumented step below.  Each step's result is dropped inside the timed region as it always was, except
     # the last one's when --dump-outputs asks for it.
     cold_ms = None
@@ -304,8 +397,6 @@ def main():
                 result = None
         barrier()
         elapsed = time.perf_counter() - t0
-    one_shot_diag = None
-    prof = None
     if cfg.get("one_shot") and movie is not None and getattr(movie, "_t", None) is None:
         movie = None
     if world > 1:
@@ -316,137 +407,20 @@ def main():
     if args.dump_outputs and rank == 0:   # the other ranks of the sharded route return None
         dumped_bytes = dump_outputs(result, args.dump_outputs)
     result = None
-
-    # one extra, untimed, instrumented run: per-phase breakdown, tile statistics, per-kernel HIP-event times
-    diag = one_shot_diag
-    if diag is None:
-        if cfg.get("one_shot"):
-            movie = fresh_movie()
-        ctx.profile_enable(True)
-        _, diag = one_step(diag=True)
-        barrier()
-        prof = ctx.profile_summary()
-        ctx.profile_enable(False)
-    # PCIe-inclusive figure (never `value`): the same decomposition handed a HOST array (pageable NumPy memory), i.e.
-    # including the staging through pinned buffers and the H2D transfer (localmd_amd/decomposition.py: _Movie._stream_in)
-    host_rate = None
-    if world == 1 and not args.no_host_input and not cfg.get("one_shot"):
-        host_movie = movie.cpu().numpy()
-        # two runs, the second one timed: the first also page-locks the ring of staging buffers, which the library keeps
-        # between calls (0.25 s of a cold 1.19 s at config 3; the steady state of a process that decomposes movie after movie)
-        for rep in range(2):
-            np.random.seed(0)
-            torch.cuda.synchronize()
-            th = time.perf_counter()
-            localmd_amd.localmd_decomposition(host_movie, (cfg["block"], cfg["block"]), cfg["frames"], max_components=cfg["max_components"],
-                                              seed=seed, ctx=ctx)
-            torch.cuda.synchronize()
-            host_rate = cfg["T"] / (time.perf_counter() - th)
-        del host_movie
     ms_per_step = 1e3 * elapsed / args.steps
     # N ranks decompose ONE movie together (tile grid sharded, results gathered): total work is fixed
     value = cfg["T"] * args.steps / elapsed
 
-    # roofline of the dominant hand-written kernel: tile_atx (four launches per step: V_ds = U_ds^T X,
-    # W = U0^T X, the sketch Q^T A and the full-movie projection U^T X).  Algorithmic work per launch
-    # (DESIGN.md): flops = 2 * r * d * T per tile with r = max_components (not the padded 64 rows).
-    n_tiles = len(diag["tile_ranks"])
-    d = cfg["block"] ** 2
-    r = diag["max_components"]
-    crop = diag["crop"]
-    # "tile_atx_main" = the d x T launches only (V_ds, W, and the two projections U^T X of the fit and of the
-    # whole movie); the small sketch / simulation / background launches are timed under "tile_atx".
-    atx_ms, atx_n = prof.get("tile_atx_main", (0.0, 0))
-    flops_per_launch = 2.0 * r * d * crop * n_tiles
-    bytes_per_launch = 4.0 * d * crop * n_tiles
-    avg_ms = atx_ms / max(atx_n, 1)
-    achieved = flops_per_launch / (avg_ms * 1e-3) / 1e12 if avg_ms > 0 else 0.0
-    roofline = {
-        "kernel": "tile_atx (v_mfma_f32_16x16x4_f32)", "bound": "mfma", "achieved": achieved,
-        "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": achieved / FP32_MFMA_PEAK_TFLOPS, "traffic": None,
-        "avg_launch_ms": avg_ms, "launches_timed": atx_n, "algorithmic_gflop_per_launch": flops_per_launch / 1e9,
-        "algorithmic_gb_per_launch": bytes_per_launch / 1e9,
-        "hbm_gbs_equiv": bytes_per_launch / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0,
-    }
-    # HBM-side traffic of the same launch from the committed counter pass; valid for the workload it was taken on and while
-    # the kernel source is unchanged (SHA-256 recorded with the pass)
-    try:
-        import hashlib
-
-        root = os.path.dirname(os.path.abspath(__file__))
-        pmc = json.load(open(os.path.join(root, "profiles", "r03_pmc_tile_atx.json")))
-        sha = hashlib.sha256(open(os.path.join(root, pmc["kernel_source"]), "rb").read()).hexdigest()
-        if args.config != DEFAULT_CONFIG:
-            roofline["traffic_note"] = "no counter pass for this workload"
-        elif sha != pmc["kernel_source_sha256"]:
-            roofline["traffic_note"] = "stale: the kernel source changed since the counter pass (profiles/r03_pmc_tile_atx.json)"
-        else:
-            roofline["traffic"] = pmc["fetch_bytes_per_launch"] / 1e9
-            roofline["traffic_unit"] = "GB per launch (L2 -> fabric reads, Infinity Cache hits included)"
-            roofline["traffic_source"] = "profiles/r03_pmc_tile_atx.json (separate rocprofv3 --pmc FETCH_SIZE pass, gfx950 x2 correction)"
-    except (OSError, KeyError, ValueError):
-        roofline["traffic_note"] = "no committed counter pass found"
-    roofline_mfma = roofline
-    # Dominant kernel by time: sytrd_symv (triangle matrix-vector product of the tridiagonalisation behind the
-    # final SVD, one launch per column of the min(R', T)-sized Gram matrix).  Algorithmic bytes per launch =
-    # 4 B x the n'(n'+1)/2 entries of the trailing triangle (n' = n - j - 1); with profiling on, the library
-    # times every 64th launch (j = 32, 96, ...) on its stream: average bytes / average duration of that sample.
-    sv_ms, sv_n = prof.get("sytrd_symv_sample", (0.0, 0))
-    n_eig = int(diag["eig_order"])
-    if sv_n > 0:
-        js = np.arange(32, n_eig - 1, 64, dtype=np.float64)
-        npr = n_eig - js - 1
-        avg_bytes = float(np.mean(4.0 * npr * (npr + 1) / 2))
-        avg_sv_ms = sv_ms / sv_n
-        ach = avg_bytes / (avg_sv_ms * 1e-3) / 1e9
-        roofline = {
-            "kernel": "sytrd_symv (triangle symv of the Householder tridiagonalisation, fp32)", "bound": "hbm",
-            "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS, "traffic": None,
-            "avg_launch_ms": avg_sv_ms, "launches_timed": sv_n, "launches_per_step": n_eig - 1,
-            "algorithmic_mb_per_launch": avg_bytes / 1e6, "matrix_order": n_eig,
-        }
-        # fabric-side traffic of the same launches from the committed PMC pass (profiles/r01_pmc_sytrd_n10000.json:
-        # separate rocprofv3 --pmc FETCH_SIZE run over one n = 10^4 tridiagonalisation, gfx950 x2 correction applied,
-        # mean over the launches j = 32, 96, ... that are timed here); only valid for a matrix of that order
-        # A counter pass cannot run inside this process (rocprofv3 wraps the program), so the figure is the committed
-        # one - valid only for a matrix of that order AND while the kernel's source is the file it was measured on
-        # (SHA-256 recorded with the pass); otherwise `traffic` stays null and says why.
-        try:
-            import hashlib
-
-            root = os.path.dirname(os.path.abspath(__file__))
-            pmc = json.load(open(os.path.join(root, "profiles", "r03_pmc_sytrd_n10000.json")))
-            sha = hashlib.sha256(open(os.path.join(root, pmc["kernel_source"]), "rb").read()).hexdigest()
-            if abs(n_eig - pmc["matrix_order"]) > 1:
-                roofline["traffic_note"] = "no counter pass for a matrix of this order"
-            elif sha != pmc["kernel_source_sha256"]:
-                roofline["traffic_note"] = "stale: the kernel source changed since the counter pass (profiles/r03_pmc_sytrd_n10000.json)"
-            else:
-                roofline["traffic"] = pmc["traffic_bytes_per_launch_sample_mean"] / 1e9
-                roofline["traffic_unit"] = "GB per launch (L2 -> fabric reads, Infinity Cache hits included)"
-                roofline["traffic_over_algorithmic"] = pmc["traffic_over_algorithmic_sample"]
-                roofline["traffic_source"] = "profiles/r03_pmc_sytrd_n10000.json (separate rocprofv3 --pmc FETCH_SIZE pass, gfx950 x2 correction)"
-        except (OSError, KeyError, ValueError):
-            roofline["traffic_note"] = "no committed counter pass found"
     out = {
         "metric": "frames/sec PMD decomposition", "value": value, "unit": "frames/s", "n_gpus": world,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
         "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
         "config": {"workload": args.config, "fov": [cfg["d1"], cfg["d2"]], "frames": cfg["T"], "block": cfg["block"],
-                   "frames_to_init": cfg["frames"], "max_components": cfg["max_components"], "tiles": n_tiles,
-                   "rank_before": diag["rank_before"], "rank_after": diag["rank_after"],
-                   "mean_tile_rank": float(np.mean(diag["tile_ranks"])),
+                   "frames_to_init": cfg["frames"], "max_components": cfg["max_components"],
                    "parallelism": "1 process per GPU" + (
                        f", bands of tile rows / pixel slabs and the rows of the global stage sharded over {world} ranks "
                        "(tile results gathered, background projection and the two frames x frames Gram matrices "
                        "all-reduced, R collected on rank 0; the m x m Cholesky / eigen stage replicated)" if world > 1 else "")},
-        "roofline": roofline,
-        "roofline_mfma": roofline_mfma,
-        "frames_per_s_from_host_array": host_rate,
-        "phases_ms": {k: 1e3 * v for k, v in diag["timings"].items()},
-        "hbm_peak_allocated_gb": torch.cuda.max_memory_allocated(device) / 2 ** 30,
-        "kernel_ms_per_step": {k: v[0] for k, v in sorted(prof.items(), key=lambda kv: -kv[1][0])},
-        "kernel_ms_source": "HIP events on the launch stream during one untimed instrumented step",
         "arithmetic": "fp32 operands, results and accumulation; products of >= 100 GFLOP outside the tile stage run as three "
                       "fp16-piece matrix-core products per product (two fp16 pieces per operand, power-of-two scaling, measured "
                       "error below the sgemm path's: DESIGN 4a, tests/test_gpu_kernels.py::test_gemm_fp16_pieces); M^T G M "
@@ -457,7 +431,45 @@ def main():
         out["cold_first_step_ms"] = cold_ms   # the first call of the process (every device / pinned allocation is new)
     if dumped_bytes is not None:
         out["dumped_outputs"] = {"dir": args.dump_outputs, "bytes": dumped_bytes}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+
+    if args.full:
+        # one extra, untimed, instrumented run: per-phase breakdown, tile statistics, per-kernel HIP-event times
+        if cfg.get("one_shot"):
+            movie = fresh_movie()
+        ctx.profile_enable(True)
+        _, diag = one_step(diag=True)
+        barrier()
+        prof = ctx.profile_summary()
+        ctx.profile_enable(False)
+        # PCIe-inclusive figure (never `value`): the same decomposition handed a HOST array (pageable NumPy memory), i.e.
+        # including the staging through pinned buffers and the H2D transfer (localmd_amd/decomposition.py: _Movie._stream_in)
+        host_rate = None
+        if world == 1 and not args.no_host_input and not cfg.get("one_shot"):
+            host_movie = movie.cpu().numpy()
+            # two runs, the second one timed: the first also page-locks the ring of staging buffers, which the library keeps
+            # between calls (0.25 s of a cold 1.19 s at config 3; the steady state of a process that decomposes movie after movie)
+            for rep in range(2):
+                np.random.seed(0)
+                torch.cuda.synchronize()
+                th = time.perf_counter()
+                localmd_amd.localmd_decomposition(host_movie, (cfg["block"], cfg["block"]), cfg["frames"], max_components=cfg["max_components"],
+                                                  seed=seed, ctx=ctx)
+                torch.cuda.synchronize()
+                host_rate = cfg["T"] / (time.perf_counter() - th)
+            del host_movie
+        roofline, roofline_mfma = rooflines(args.config, cfg, diag, prof)
+        out["config"].update({"tiles": len(diag["tile_ranks"]), "rank_before": diag["rank_before"],
+                              "rank_after": diag["rank_after"], "mean_tile_rank": float(np.mean(diag["tile_ranks"]))})
+        out.update({
+            "roofline": roofline,
+            "roofline_mfma": roofline_mfma,
+            "frames_per_s_from_host_array": host_rate,
+            "phases_ms": {k: 1e3 * v for k, v in diag["timings"].items()},
+            "kernel_ms_per_step": {k: v[0] for k, v in sorted(prof.items(), key=lambda kv: -kv[1][0])},
+            "kernel_ms_source": "HIP events on the launch stream during one untimed instrumented step",
+        })
+    out["hbm_peak_allocated_gb"] = torch.cuda.max_memory_allocated(device) / 2 ** 30
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(cfg, movie, seed)
     if rank == 0:
         print(json.dumps(out))

@@ -6,7 +6,7 @@ OUT=gpurun_out/bench_$TAG
 mkdir -p $OUT
 run() {  # name, args...
   local name=$1; shift
-  timeout -k 10 900 python bench.py "$@" > $OUT/$name.log 2> $OUT/$name.err || { echo "$name FAILED"; tail -3 $OUT/$name.err; return 1; }
+  timeout -k 10 900 python bench.py --full "$@" > $OUT/$name.log 2> $OUT/$name.err || { echo "$name FAILED"; tail -3 $OUT/$name.err; return 1; }
   tail -1 $OUT/$name.log > $OUT/$name.json
   python - "$OUT/$name.json" <<'PY'
 import json, sys

@@ -1,5 +1,5 @@
 """Idle gaps of the GPU inside one decomposition, from a rocprofv3 --kernel-trace CSV:
-    python scripts/gap_trace.py <kernel_trace.csv> [min_gap_ms]   [index]   (default index -2: the last timed decomposition of a bench.py run)"""
+    python scripts/gap_trace.py <kernel_trace.csv> [min_gap_ms]   [index]   (default index -2: the last timed decomposition of a bench.py --full run)"""
 import csv, sys
 rows = list(csv.DictReader(open(sys.argv[1])))
 min_gap = float(sys.argv[2]) if len(sys.argv) > 2 else 1.0
@@ -7,7 +7,7 @@ ev = sorted(((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name
 # decompositions start with the statistics kernel
 starts = [i for i, e in enumerate(ev) if "stats_chunk" in e[2]]
 first = [s for k, s in enumerate(starts) if k == 0 or ev[s][0] - ev[starts[k - 1]][0] > 50e6]
-which = int(sys.argv[3]) if len(sys.argv) > 3 else -2      # default: the last TIMED decomposition (bench.py ends with an instrumented one)
+which = int(sys.argv[3]) if len(sys.argv) > 3 else -2      # default: the last TIMED decomposition (bench.py --full ends with an instrumented one)
 lo = first[which]
 hi = first[which + 1] if which + 1 < 0 and which + 1 + len(first) < len(first) else len(ev)
 if which != -1:

@@ -18,7 +18,7 @@ def short(name):
 
 tag = re.search(r"(r\d+)_", sys.argv[1]).group(1)
 print(f"# rocprofv3 --kernel-trace --stats summary, round {int(tag[1:])} (MI355X, 1 GPU)\n")
-print("Command (scripts/profile_round.sh, run from /tmp on the GPU box): `rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o bench -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-host-input`")
+print("Command (scripts/profile_round.sh): `rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o bench -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-host-input`")
 print(f"(workload {line['config']['workload']}, final kernel sources of the round; the run holds {runs} decompositions: 1 warm-up, 3 timed, 1 instrumented; the columns below are per decomposition).")
 print(f"Raw stats: `{sys.argv[1]}`.  Bench line of the same run (under the profiler: {line['ms_per_step']:.0f} ms per step): `{sys.argv[3]}`.  Table written by `scripts/kernel_stats_md.py`.\n")
 print(f"Total kernel time {total:.1f} ms per decomposition (kernels of the second stream - Cholesky next to the M^T Z product, result downloads - included).\n")
