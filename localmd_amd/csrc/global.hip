@@ -1552,8 +1552,11 @@ int pmd_gram_mtgm_impl(pmd_ctx* ctx, const float* M, int rows, int m, long ldm, 
       if (done) continue;
       pieces = false;   // (the product below may reuse the scratch that held the pieces)
     }
+    // the fp32 product: no piece route above produced this block, and pmd_gemm_rm's own fp16-piece product (two pieces in ONE
+    // chain over all of `rows`, gemm_f16x2.hip) is the arithmetic that breaks this product (the many-tile workloads, where
+    // the concatenated route is gated off, have row blocks above its size gate: 4x the fp32 error at 1000 x 309 827)
     const int keep = ctx->gemm_split;
-    if (!mtgm_pieces) ctx->gemm_split = 0;
+    ctx->gemm_split = 0;
     const int rc = pmd_gemm_rm(ctx, 0, 0, nr, i0 + nr, rows, 1.f, Mt + (long)i0 * ldt, ldt, GM, ldgm, 0.f, C + (long)i0 * ldc, ldc);
     ctx->gemm_split = keep;
     RUN(rc);
