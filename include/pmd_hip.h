@@ -123,6 +123,27 @@ int pmd_group_expand(pmd_ctx* ctx, const float* C, long ldc, int n, int d1, int 
                      const float* A, const void* Y, int y_elem, long ldy, int n_panels, int panels, void* out,
                      int out_elem);
 
+/* ROI traces (localmd_amd/traces.py).  pmd_roi_gather: out[k][f] = sum_q w[q] * (float) Y[f][pix[q]] over the pixels of
+ * ROI k, for the n frames of a frames-first batch Y (n x D, element type elem, converted to fp32 in the kernel).
+ * pix / w: the C-order pixel ids (< D, ascending within an ROI) and weights of all ROIs, one after the other.
+ * segs: device int64[n_segs][4] = {q0, p (>= 1), out_row, to_ws}: p pixels from pix + q0; to_ws = 0: the segment is a
+ * whole ROI and writes row out_row of out (ld ldo >= n); 1: it is one piece of a split ROI and writes row out_row of
+ * the partial-sum workspace (n_partial_rows x n fp32), which the call then reduces: split: device
+ * int64[n_split][3] = {out_row, ws_row0, parts}, out[out_row][f] = sum_{c < parts} ws[ws_row0 + c][f], c = 0, 1, ...
+ * Sum of a segment: lane l (of 64) runs one fma chain over its pixels l, l + 64, ... from 0, then an xor butterfly
+ * (1, 2, ..., 32) folds the lanes; the order depends on the tables alone, so out[k][f] has the same bits for every n,
+ * every position of the frame in its batch and every element type holding the same values.  The tables are trusted
+ * (the caller validates them: traces.validate_roi_tables); rows of out that no segment / split entry names are not
+ * written.  No atomics, no synchronisation, no allocation.
+ * pmd_roi_combine: d = C[k][f] + offset[k] (C == NULL: d = offset[k]) for k < K, f < n; den[k][f] = d (den may be
+ * NULL); res[k][f] = raw[k][f] - d, from the rounded d (res may be NULL; raw is read only for res). */
+size_t pmd_roi_gather_workspace_bytes(long n_partial_rows, int n);
+int pmd_roi_gather(pmd_ctx* ctx, const void* Y, int elem, int n, long D, long n_segs, const long* segs, const int* pix,
+                   const float* w, long n_partial_rows, int n_split, const long* split, float* out, long ldo, void* ws,
+                   size_t ws_bytes);
+int pmd_roi_combine(pmd_ctx* ctx, long K, int n, const float* C, long ldc, const float* offset, const float* raw, long ldr,
+                    float* den, long ldd, float* res, long lde);
+
 /* A2: background basis = rank-K rSVD of the standardised sample (pmd_loader.py:46-68, :300-314).
  * xs: pixel-major sample with round_up(D,1024) rows allocated (rows >= D zero). basis_out[c][k]. */
 size_t pmd_background_rsvd_workspace_bytes(long D, int n, int K);

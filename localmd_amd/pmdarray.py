@@ -144,6 +144,13 @@ class PMDArray:
 
         return export_movie(self, out, movie, **kw)
 
+    def traces(self, rois, movie=None, **kw):
+        """Denoised / raw / residual time courses of the masks ``rois`` ((K, d1, d2) weights, a label image or a sparse
+        (K, d1 d2) matrix), computed on the GPU (traces.extract_traces; same keywords)."""
+        from .traces import extract_traces
+
+        return extract_traces(self, rois, movie, **kw)
+
     @property
     def _combined_temporal(self):
         """(R * s) V, built on first use and cached: __getitem__ is then one sparse-dense product
