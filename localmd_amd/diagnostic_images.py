@@ -17,6 +17,8 @@ from typing import NamedTuple
 import numpy as np
 
 from ._lib import Context, ptr
+from ._stream import (batch_buffer_bytes, block_plan, check_fit, device_context, mean_std, read_batches, scaled_r,
+                      source_info, upload_f32)
 
 CHUNK_BYTES = 1 << 30
 
@@ -163,10 +165,9 @@ def diag_plan(T, frame_batch_size):
     """[(b0, b1, [(c0, c1), ...])]: the frame batches the movie is read in (those of the streamed decomposition, whole
     1024-frame chunks) and the reconstruction blocks of each, at most DIAG_RECON_FRAMES frames, starting on multiples of
     DIAG_FRAME_BLOCK."""
-    from .decomposition import _stream_batches, _stream_batch_frames
+    from .decomposition import _stream_batch_frames
 
-    rb = min(_stream_batch_frames(frame_batch_size), DIAG_RECON_FRAMES)
-    return [(b0, b1, [(c0, min(b1, c0 + rb)) for c0 in range(b0, b1, rb)]) for b0, b1 in _stream_batches(T, frame_batch_size)]
+    return block_plan(T, frame_batch_size, min(_stream_batch_frames(frame_batch_size), DIAG_RECON_FRAMES))
 
 
 def _fused_workspace_bytes(n, D):
@@ -184,7 +185,7 @@ def _diag_device_bytes(D, nb, esize, n_cols, rank, nnz, lag, n_batches, host_sou
     lag pairs that cross a batch boundary."""
     rb = min(nb, DIAG_RECON_FRAMES)
     ldc = (rb + 3) // 4 * 4
-    need = (2 if host_source and n_batches > 1 else 1) * nb * D * esize
+    need = batch_buffer_bytes(nb, D, esize, host_source, n_batches)
     need += 4 * (n_cols * ldc + D * ldc + rb * D)
     need += _fused_workspace_bytes(rb, D) + DIAG_MOMENTS * D * 8 + 4 * D * 8 + (3 + 2 + 1) * D * 4
     if not factors_on_device:
@@ -201,8 +202,7 @@ def _check_fit(need, ring, free, lag):
         raise ValueError("make_pmd_diagnostic_images: the ring of lag = {} raw frames needs {:.2f} GB of device memory and "
                          "does not fit ({:.2f} GB free besides the batches); use a smaller lag".format(lag, ring / 1e9,
                                                                                                     (free - need + ring) / 1e9))
-    raise ValueError("make_pmd_diagnostic_images needs about {:.2f} GB of device memory, {:.2f} GB are free; lower "
-                     "frame_batch_size".format(need / 1e9, free / 1e9))
+    check_fit("make_pmd_diagnostic_images", need, free)
 
 
 def _check_args(original_movie, pmd, mode, lag):
@@ -210,9 +210,8 @@ def _check_args(original_movie, pmd, mode, lag):
 
     if not isinstance(pmd, PMDArray):
         raise TypeError("pmd must be a localmd_amd.PMDArray, got {}".format(type(pmd).__name__))
-    shape = tuple(int(x) for x in original_movie.shape)
-    if shape != tuple(pmd.shape):
-        raise ValueError("the movie has shape {}, the decomposition {}".format(shape, tuple(pmd.shape)))
+    shape = tuple(int(x) for x in pmd.shape)
+    on_device, esize = source_info(original_movie, shape)
     if mode not in ("max", "mean"):
         raise ValueError(f"mode {mode} not supported")
     if isinstance(lag, bool) or int(lag) != lag:
@@ -220,7 +219,7 @@ def _check_args(original_movie, pmd, mode, lag):
     lag = int(lag)
     if lag < 1 or lag >= shape[0]:
         raise ValueError("lag must be in [1, frames): lag = {}, {} frames".format(lag, shape[0]))
-    return shape, lag
+    return shape, lag, on_device, esize
 
 
 def make_pmd_diagnostic_images(original_movie, pmd, *, mode="max", lag=1, frame_batch_size=10000, num_workers=0,
@@ -236,67 +235,41 @@ def make_pmd_diagnostic_images(original_movie, pmd, *, mode="max", lag=1, frame_
     ((R s) Vt[:, batch] with pmd_gemm, then U and the noise image with the expansion kernels) and one fused kernel forms
     the moments of the movie, the reconstruction and the residual; device memory does not grow with the movie's length
     except for the T doubles of frame_residual_rms."""
-    import torch
-    from ._lib import Context
-    from .decomposition import _device_free_bytes, _stream_dtype
-    from .projection import _device_elem
+    from .decomposition import _device_free_bytes
 
-    (T, d1, d2), lag = _check_args(original_movie, pmd, mode, lag)
+    (T, d1, d2), lag, on_device, esize = _check_args(original_movie, pmd, mode, lag)
     D = d1 * d2
     plan = diag_plan(T, frame_batch_size)
     nb = plan[0][1] - plan[0][0]
     rb = min(nb, DIAG_RECON_FRAMES)
     ldc = (rb + 3) // 4 * 4
     n_cols, rank = (int(x) for x in pmd.r.shape)
-    on_device = isinstance(original_movie, torch.Tensor) and original_movie.device.type != "cpu"
-    if on_device:
-        esize = original_movie.element_size() if _device_elem(original_movie[:0]) is not None else 4
-    else:
-        esize = _stream_dtype(original_movie.detach().numpy() if isinstance(original_movie, torch.Tensor)
-                              else original_movie).itemsize
-    dv = getattr(pmd, "_dev", None)
-    own = False
-    if dv is not None:
-        ctx = dv["ctx"]
-    elif ctx is None:
-        ctx = Context(0 if device is None else int(device))
-        own = True
-    try:
+    with device_context(pmd, device, ctx) as (ctx, dv):
         need, ring_bytes = _diag_device_bytes(D, nb, esize, n_cols, rank, int(pmd.u.nnz), lag, len(plan), not on_device,
                                               dv is not None)
         _check_fit(need + 8 * T, ring_bytes, _device_free_bytes(ctx.device), lag)
         return _diagnostics(ctx, original_movie, pmd, dv, plan, T, d1, d2, mode, lag, rb, ldc, n_cols, rank,
-                            frame_batch_size, num_workers, on_device)
-    finally:
-        if own:
-            ctx.close()
+                            frame_batch_size, num_workers)
 
 
-def _diagnostics(ctx, movie, pmd, dv, plan, T, d1, d2, mode, lag, rb, ldc, n_cols, rank, frame_batch_size, num_workers,
-                 on_device):
+def _diagnostics(ctx, movie, pmd, dv, plan, T, d1, d2, mode, lag, rb, ldc, n_cols, rank, frame_batch_size, num_workers):
     import ctypes as C
 
     import torch
-    from ._lib import ptr
-    from .decomposition import _StreamedMovie
-    from .projection import _device_elem
-
     dev = ctx.device
     D = d1 * d2
-    f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)   # noqa: E731
-    mean = f32(np.asarray(pmd.mean_img).reshape(-1))
-    std = f32(np.asarray(pmd.var_img).reshape(-1))
+    mean, std = mean_std(ctx, pmd)
     # U row of C-order pixel c (the decomposition's pixel order), as PMDArray._getitem_device selects them
     sel = torch.from_numpy(np.ascontiguousarray(pmd.row_indices.reshape(-1), dtype=np.int32)).to(dev)
     if dv is not None:
-        indptr, indices, data, rs, vt_all = dv["indptr"], dv["indices"], dv["data"], dv["rs"], dv["v"]
+        indptr, indices, data, vt_all = dv["indptr"], dv["indices"], dv["data"], dv["v"]
     else:
         u = pmd.u
         indptr = torch.from_numpy(u.indptr.astype(np.int64)).to(dev)
         indices = torch.from_numpy(u.indices.astype(np.int32)).to(dev)
-        data = f32(u.data)
-        rs = f32(pmd.r * pmd.s[None, :])
+        data = upload_f32(ctx, u.data)
         vt_all = None
+    rs = scaled_r(ctx, pmd, dv)
     expand = rank > 0 and n_cols > 0
     ct = torch.zeros((n_cols, ldc), dtype=torch.float32, device=dev) if expand else None
     acc = torch.empty((D, ldc), dtype=torch.float32, device=dev) if expand else None
@@ -357,16 +330,7 @@ def _diagnostics(ctx, movie, pmd, dv, plan, T, d1, d2, mode, lag, rb, ldc, n_col
                 rb8[s:s + k].copy_(bb8[t - b0:t - b0 + k])
                 t += k
 
-    if on_device:
-        for b0, b1, _ in plan:
-            b = movie[b0:b1].to(dev).reshape(b1 - b0, D)
-            elem = _device_elem(b)
-            if elem is None:
-                b, elem = b.to(torch.float32), 0
-            consume(b.contiguous(), elem, b0, b1 - b0)
-    else:
-        src = _StreamedMovie(ctx, movie, frame_batch_size, num_workers=num_workers)
-        src.run_pass(lambda batch, b0, n: consume(batch, src.elem, b0, n))
+    read_batches(ctx, movie, [(b0, b1) for b0, b1, _ in plan], frame_batch_size, num_workers, consume)
 
     img = torch.empty((4, D), dtype=torch.float64, device=dev)
     m_code = 0 if mode == "max" else 1

@@ -13,7 +13,8 @@ block (blocks start on multiples of 1024 whatever the batch size, so every produ
 bit is the same for every batching and source) goes through ``pmd_gemm`` (C = (R s) Vt[:, block]) and one fused kernel,
 ``pmd_group_expand`` (csrc/expand_fused.hip), from C to finished output frames.  The kernel walks, per 64-pixel patch,
 the groups of U's columns that touch it (projection.group_tables, cached on the PMDArray and shared with
-project_frames; the per-patch lists are built here).  Host destinations get each block through a ring of two device
+project_frames; the per-patch lists are built here).  Reading the movie, the block plan and the Vt columns of a block
+are those of _stream, shared with extract_traces.  Host destinations get each block through a ring of two device
 and two page-locked buffers: the copy to the host runs on a side stream and a writer thread puts the frames into the
 file or array while the next block computes.  Device memory and host memory do not grow with the movie's length.
 """
@@ -23,9 +24,11 @@ import threading
 
 import numpy as np
 
-from .projection import MAX_ROWS, P_MAX, ROW_PAD, _device_elem, _pad, tables_for
+from ._stream import BLOCK as EXPORT_BLOCK, block_plan as export_plan
+from ._stream import (VtBlocks, batch_buffer_bytes, check_fit, device_context, mean_std, name_tuple, read_batches, scaled_r,
+                      source_info, upload_f32)
+from .projection import MAX_ROWS, P_MAX, ROW_PAD, _pad, tables_for
 
-EXPORT_BLOCK = 1024     # frames per reconstruction block; blocks start on multiples of it
 EXPORT_PATCH = 64       # pixels per patch of pmd_group_expand
 ENTRY_FIELDS = 4        # {a_off, p64, r, c_row0}
 HOST_SLOTS = 2          # device + page-locked output buffers of a host destination
@@ -47,16 +50,6 @@ def quantize(v, dtype):
     with np.errstate(invalid="ignore"):
         q = np.clip(np.rint(v), info.min, info.max)
     return np.where(np.isnan(q), 0, q).astype(dtype)
-
-
-def export_plan(T, frame_batch_size):
-    """[(b0, b1, [(c0, c1), ...])]: the frame batches the movie is read in (those of the streamed decomposition, whole
-    1024-frame chunks) and the reconstruction blocks of each: EXPORT_BLOCK frames starting on multiples of it, the last
-    one shorter.  The blocks are the same for every frame_batch_size."""
-    from .decomposition import _stream_batches
-
-    return [(b0, b1, [(c0, min(b1, c0 + EXPORT_BLOCK)) for c0 in range(b0, b1, EXPORT_BLOCK)])
-            for b0, b1 in _stream_batches(T, frame_batch_size)]
 
 
 # ---- per-patch tables ----------------------------------------------------------------------------------------------
@@ -122,23 +115,6 @@ def expand_tables_for(pmd):
 
 
 # ---- argument checks (no device work, no file) ---------------------------------------------------------------------
-def _panels(panels):
-    if isinstance(panels, str):
-        panels = (panels,)
-    try:
-        panels = tuple(panels)
-    except TypeError:
-        raise ValueError("panels must be a name or a tuple of names from {}".format(PANELS)) from None
-    if not panels:
-        raise ValueError("panels is empty; choose from {}".format(PANELS))
-    for p in panels:
-        if not isinstance(p, str) or p not in _PANEL_CODE:
-            raise ValueError("unknown panel {!r}; choose from {}".format(p, PANELS))
-    if len(set(panels)) != len(panels):
-        raise ValueError("panels {} name a panel twice".format(panels))
-    return panels
-
-
 def _out_dtype(dtype):
     try:
         key = np.dtype(dtype).name
@@ -275,20 +251,6 @@ def _destination(out, shape, dtype, bigtiff, device_index):
     return _Dest("array", out, shape, dtype)
 
 
-def _movie_info(movie, shape):
-    """(on_device, element size the movie is uploaded / read in)."""
-    import torch
-    from .decomposition import _stream_dtype
-
-    got = tuple(int(x) for x in movie.shape)
-    if got != tuple(shape):
-        raise ValueError("the movie has shape {}, the decomposition {}".format(got, tuple(shape)))
-    if isinstance(movie, torch.Tensor) and movie.device.type != "cpu":
-        return True, movie.element_size() if _device_elem(movie[:0]) is not None else 4
-    src = movie.detach().numpy() if isinstance(movie, torch.Tensor) else movie
-    return False, _stream_dtype(src).itemsize
-
-
 def export_device_bytes(D, nb, esize, n_panels, out_esize, n_cols, rank, n_entries, n_a, n_patches, needs_movie,
                         host_source, n_batches, host_dest, factors_on_device):
     """Device bytes export_movie holds for a movie of D pixels read in batches of nb frames; no term grows with the
@@ -298,7 +260,7 @@ def export_device_bytes(D, nb, esize, n_panels, out_esize, n_cols, rank, n_entri
     B = EXPORT_BLOCK
     need = 0
     if needs_movie:
-        need += (2 if host_source and n_batches > 1 else 1) * nb * D * esize
+        need += batch_buffer_bytes(nb, D, esize, host_source, n_batches)
     if rank > 0 and n_cols > 0:
         need += 4 * (rank * B + n_cols * B)
         if not factors_on_device:
@@ -307,12 +269,6 @@ def export_device_bytes(D, nb, esize, n_panels, out_esize, n_cols, rank, n_entri
         need += HOST_SLOTS * B * D * n_panels * out_esize
     need += 8 * (n_patches + 1) + n_entries * (8 * ENTRY_FIELDS + 4 * EXPORT_PATCH) + 4 * n_a + 2 * 4 * D
     return need + (1 << 20)     # the allocator's rounding of the small arrays
-
-
-def _check_fit(need, free):
-    if need > free:
-        raise ValueError("export_movie needs about {:.2f} GB of device memory, {:.2f} GB are free; lower "
-                         "frame_batch_size".format(need / 1e9, free / 1e9))
 
 
 # ---- public entry point --------------------------------------------------------------------------------------------
@@ -330,14 +286,12 @@ def export_movie(pmd, out, movie=None, *, panels="denoised", dtype="float32", fr
     "uint16" or "int16" (round half to even, saturating, NaN -> 0: quantize).  After ``pmd.to_device()`` its context
     and uploaded factors are reused.  Argument errors are raised before any device work and before a file is created;
     a file this call created is removed when it fails midway."""
-    import torch
-    from ._lib import Context
     from .decomposition import _device_free_bytes
     from .pmdarray import PMDArray
 
     if not isinstance(pmd, PMDArray):
         raise TypeError("pmd must be a localmd_amd.PMDArray, got {}".format(type(pmd).__name__))
-    panels = _panels(panels)
+    panels = name_tuple(panels, PANELS, "panel", "panels")
     out_dtype = _out_dtype(dtype)
     if bigtiff is not None and not isinstance(bigtiff, bool):
         raise ValueError("bigtiff must be None, True or False")
@@ -346,7 +300,7 @@ def export_movie(pmd, out, movie=None, *, panels="denoised", dtype="float32", fr
     needs_movie = any(p != "denoised" for p in panels)
     if needs_movie and movie is None:
         raise ValueError("panels {} need the movie: pass movie=".format(tuple(p for p in panels if p != "denoised")))
-    on_device, esize = _movie_info(movie, pmd.shape) if movie is not None else (False, 4)
+    on_device, esize = source_info(movie, pmd.shape) if movie is not None else (False, 4)
     dv = getattr(pmd, "_dev", None)
     dev_index = dv["ctx"].device_index if dv is not None else (ctx.device_index if ctx is not None else
                                                                (0 if device is None else int(device)))
@@ -356,20 +310,14 @@ def export_movie(pmd, out, movie=None, *, panels="denoised", dtype="float32", fr
     tabs, xt = expand_tables_for(pmd)
     n_cols, rank = (int(x) for x in pmd.r.shape)
 
-    own = False
-    if dv is not None:
-        ctx = dv["ctx"]
-    elif ctx is None:
-        ctx = Context(dev_index)
-        own = True
-    try:
+    with device_context(pmd, dev_index, ctx) as (ctx, dv):
         need = export_device_bytes(D, nb, esize, len(panels), out_dtype.itemsize, n_cols, rank, len(xt["entries"]),
                                    int(tabs["a"].size), int(xt["n_patches"]), needs_movie, not on_device, len(plan),
                                    dest.kind != "device", dv is not None)
-        _check_fit(need, _device_free_bytes(ctx.device))
+        check_fit("export_movie", need, _device_free_bytes(ctx.device))
         dest.open()
         try:
-            _export(ctx, pmd, dv, tabs, xt, movie if needs_movie else None, on_device, plan, panels, out_dtype, dest,
+            _export(ctx, pmd, dv, tabs, xt, movie if needs_movie else None, plan, panels, out_dtype, dest,
                     frame_batch_size, num_workers)
         except BaseException:
             dest.abort()
@@ -377,9 +325,6 @@ def export_movie(pmd, out, movie=None, *, panels="denoised", dtype="float32", fr
         finally:
             dest.shutdown()
         return dest.close()
-    finally:
-        if own:
-            ctx.close()
 
 
 class _HostSink:
@@ -480,12 +425,11 @@ class _DeviceSink:
         pass
 
 
-def _export(ctx, pmd, dv, tabs, xt, movie, on_device, plan, panels, out_dtype, dest, frame_batch_size, num_workers):
+def _export(ctx, pmd, dv, tabs, xt, movie, plan, panels, out_dtype, dest, frame_batch_size, num_workers):
     import ctypes as C
 
     import torch
     from ._lib import ptr
-    from .decomposition import _StreamedMovie
 
     T, d1, d2 = (int(x) for x in pmd.shape)
     D = d1 * d2
@@ -497,51 +441,32 @@ def _export(ctx, pmd, dv, tabs, xt, movie, on_device, plan, panels, out_dtype, d
         code |= _PANEL_CODE[p] << (2 * k)
     out_elem = _ELEM[out_dtype]
     frame_bytes = D * P * out_dtype.itemsize
-    f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)   # noqa: E731
-    # mean / std in C pixel order (the group tables' pixel ids are C-order whatever pmd.order is)
-    mean = f32(np.asarray(pmd.mean_img).reshape(-1))
-    std = f32(np.asarray(pmd.var_img).reshape(-1))
+    mean, std = mean_std(ctx, pmd)
     n_ent = len(xt["entries"])
     patch_ptr = torch.from_numpy(xt["patch_ptr"]).to(dev)
     entries = torch.from_numpy(np.ascontiguousarray(xt["entries"]).reshape(-1)).to(dev) if n_ent else None
     qmap = torch.from_numpy(xt["qmap"]).to(dev) if n_ent else None
-    A = f32(tabs["a"]) if n_ent else None
+    A = upload_f32(ctx, tabs["a"]) if n_ent else None
     expand = n_cols > 0 and n_ent > 0
     B = EXPORT_BLOCK
     ct = torch.zeros((n_cols, B), dtype=torch.float32, device=dev) if expand else None
     if expand and rank > 0:
-        rs = dv["rs"] if dv is not None else f32(pmd.r * pmd.s[None, :])
-        vtb = torch.empty((rank, B), dtype=torch.float32, device=dev)
-    st = {"pin": [None, None], "ev": [None, None], "k": 0}
-
-    def vt_block(c0, m):
-        """Vt[:, c0:c0 + m] into vtb (rank x 1024, the same leading dimension for every block and source)."""
-        if dv is not None:
-            vtb[:, :m].copy_(dv["v"][:, c0:c0 + m])
-            return
-        j = st["k"] % 2
-        st["k"] += 1
-        if st["pin"][j] is None:
-            st["pin"][j] = torch.empty((rank, B), dtype=torch.float32, pin_memory=True)
-        elif st["ev"][j] is not None:
-            st["ev"][j].synchronize()           # the upload that last read this buffer has finished
-        np.copyto(st["pin"][j][:, :m].numpy(), pmd.v[:, c0:c0 + m], casting="unsafe")
-        vtb[:, :m].copy_(st["pin"][j][:, :m], non_blocking=True)
-        st["ev"][j] = torch.cuda.Event()
-        st["ev"][j].record(torch.cuda.current_stream(dev))
+        rs = scaled_r(ctx, pmd, dv)
+        vt = VtBlocks(ctx, pmd, dv)
 
     if dest.kind == "device":
         sink = _DeviceSink(dest.target, frame_bytes)
     else:
         sink = _HostSink(ctx, dest, frame_bytes, (d1, P * d2), out_dtype, max(1, min(T, B)))
     kb = {"k": 0}
+    blocks_of = {b0: blocks for b0, _, blocks in plan}
 
-    def consume(batch, elem, b0, blocks):
-        for c0, c1 in blocks:
+    def consume(batch, elem, b0, n):
+        for c0, c1 in blocks_of[b0]:
             m = c1 - c0
             if expand and rank > 0:
-                vt_block(c0, m)
-                ctx.call("pmd_gemm", 0, 0, n_cols, m, rank, 1.0, ptr(rs), rank, ptr(vtb), B, 0.0, ptr(ct), B)
+                vt.load(c0, m)
+                ctx.call("pmd_gemm", 0, 0, n_cols, m, rank, 1.0, ptr(rs), rank, ptr(vt.buf), B, 0.0, ptr(ct), B)
             k = kb["k"]
             kb["k"] += 1
             yp = C.c_void_p(batch.data_ptr() + (c0 - b0) * D * batch.element_size()) if batch is not None else None
@@ -550,20 +475,7 @@ def _export(ctx, pmd, dv, tabs, xt, movie, on_device, plan, panels, out_dtype, d
             sink.done(k, c0, m)
 
     try:
-        if movie is None:
-            for b0, _, blocks in plan:
-                consume(None, 0, b0, blocks)
-        elif on_device:
-            for b0, b1, blocks in plan:
-                b = movie[b0:b1].to(dev).reshape(b1 - b0, D)
-                elem = _device_elem(b)
-                if elem is None:
-                    b, elem = b.to(torch.float32), 0
-                consume(b.contiguous(), elem, b0, blocks)
-        else:
-            src = _StreamedMovie(ctx, movie, frame_batch_size, num_workers=num_workers)
-            blocks_of = {b0: blocks for b0, _, blocks in plan}
-            src.run_pass(lambda batch, b0, n: consume(batch, src.elem, b0, blocks_of[b0]))
+        read_batches(ctx, movie, [(b0, b1) for b0, b1, _ in plan], frame_batch_size, num_workers, consume)
         sink.finish()
         ctx.sync()
     except BaseException:

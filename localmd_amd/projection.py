@@ -23,7 +23,8 @@ call reduces in chunk order.
 import numpy as np
 import scipy.sparse
 
-from .decomposition import _StreamedMovie, _device_free_bytes, _projected_svd_dev, display
+from ._stream import ToHost, device_context, mean_std, read_batches, upload_f32
+from .decomposition import _device_free_bytes, _projected_svd_dev, display
 from .pmdarray import PMDArray
 
 # Largest group support: the largest tile the decomposition accepts (40 x 40 pixels, pmd_pick_dvariant), so a tile is
@@ -233,47 +234,17 @@ def _as_frames(pmd, frames):
     return frames, shape[0]
 
 
-def _device_elem(t):
-    import torch
-
-    m = {torch.float32: 0, torch.int16: 2}
-    if hasattr(torch, "uint16"):
-        m[torch.uint16] = 1
-    return m.get(t.dtype)
-
-
 class _Run:
-    """One projection: context, uploaded tables, R and the statistics; runs the batches of a source."""
+    """One projection on an open context: uploaded tables, R and the statistics; runs the batches of a source."""
 
-    def __init__(self, pmd, device, ctx):
-        from ._lib import Context
-
-        dv = getattr(pmd, "_dev", None)
-        self.own = False
-        if dv is not None:
-            ctx = dv["ctx"]
-        elif ctx is None:
-            ctx = Context(0 if device is None else int(device))
-            self.own = True
+    def __init__(self, ctx, pmd):
         self.ctx = ctx
-        self.pmd = pmd
         self.rank = int(pmd.r.shape[1])
-
-    def setup(self):
-        import torch
-
-        ctx, pmd = self.ctx, self.pmd
         self.tabs = DeviceTables(ctx, tables_for(pmd))
-        dev = ctx.device
-        self.mean = torch.from_numpy(np.ascontiguousarray(pmd.mean_img, dtype=np.float32).reshape(-1)).to(dev)
-        self.std = torch.from_numpy(np.ascontiguousarray(pmd.var_img, dtype=np.float32).reshape(-1)).to(dev)
-        self.r = torch.from_numpy(np.ascontiguousarray(pmd.r, dtype=np.float32)).to(dev)
+        self.mean, self.std = mean_std(ctx, pmd)
+        self.r = upload_f32(ctx, pmd.r)
         if self.r.shape[0] != self.tabs.n_cols:
             raise ValueError("R has {} rows, U has {} columns".format(self.r.shape[0], self.tabs.n_cols))
-
-    def close(self):
-        if self.own:
-            self.ctx.close()
 
     def run(self, src, n, frame_batch_size, num_workers, sink):
         """Project every frame batch of src: Z = grouped U^T Y_std (pmd_group_project), then C = R^T Z (pmd_gemm) into
@@ -296,69 +267,10 @@ class _Run:
             ctx.call("pmd_gemm", 1, 0, self.rank, nb, tabs.n_cols, 1.0, ptr(self.r), self.rank, ptr(Z), nb, 0.0, ptr(dst), ldc)
             sink.done(t0, nb)
 
-        if isinstance(src, torch.Tensor) and src.device.type != "cpu":
-            step = max(1, int(frame_batch_size))
-            for t0 in range(0, n, step):
-                t1 = min(n, t0 + step)
-                b = src[t0:t1].to(ctx.device).reshape(t1 - t0, tabs.D)
-                elem = _device_elem(b)
-                if elem is None:
-                    b, elem = b.to(torch.float32), 0
-                consume(b.contiguous(), elem, t0, t1 - t0)
-        else:
-            movie = _StreamedMovie(ctx, src, frame_batch_size, num_workers=num_workers)
-            movie.run_pass(lambda batch, t0, nb: consume(batch, movie.elem, t0, nb))
+        # a device tensor is cut by the raw frame_batch_size (a host source by whole 1024-frame chunks of it)
+        step = max(1, int(frame_batch_size))
+        read_batches(ctx, src, [(t0, min(n, t0 + step)) for t0 in range(0, n, step)], frame_batch_size, num_workers, consume)
         sink.finish()
-
-
-class _ToHost:
-    """C batch by batch to host memory: two device buffers and two page-locked buffers, the copy of a batch overlaps the
-    next batch's work; C has no length bound on the device."""
-
-    def __init__(self, ctx, rank, n):
-        import torch
-
-        self.ctx, self.rank = ctx, rank
-        self.out = np.empty((rank, n), dtype=np.float32)
-        self.dev, self.host, self.pending = [None, None], [None, None], []
-        self.k = 0
-        self.torch = torch
-        self.stream = torch.cuda.Stream(device=ctx.device)   # not the upload stream of the staging ring
-
-    def dst(self, t0, nb):
-        torch = self.torch
-        j = self.k % 2
-        if self.dev[j] is None or self.dev[j].numel() < self.rank * nb:
-            self.dev[j] = torch.empty(self.rank * nb, dtype=torch.float32, device=self.ctx.device)
-            self.host[j] = torch.empty(self.rank * nb, dtype=torch.float32, pin_memory=True)
-        return self.dev[j], nb
-
-    def done(self, t0, nb):
-        torch = self.torch
-        j = self.k % 2
-        self.k += 1
-        main = torch.cuda.current_stream(self.ctx.device)
-        side = self.stream
-        ev = torch.cuda.Event()
-        ev.record(main)
-        side.wait_event(ev)
-        with torch.cuda.stream(side):
-            self.host[j][:self.rank * nb].copy_(self.dev[j][:self.rank * nb], non_blocking=True)
-            fin = torch.cuda.Event()
-            fin.record(side)
-        # a buffer pair is written again two batches later: finish the older copy first
-        self.pending.append((fin, j, t0, nb))
-        if len(self.pending) == 2:
-            self._drain(self.pending.pop(0))
-
-    def _drain(self, item):
-        fin, j, t0, nb = item
-        fin.synchronize()
-        self.out[:, t0:t0 + nb] = self.host[j][:self.rank * nb].numpy().reshape(self.rank, nb)
-
-    def finish(self):
-        while self.pending:
-            self._drain(self.pending.pop(0))
 
 
 class _OnDevice:
@@ -388,15 +300,11 @@ def project_frames(pmd, frames, *, frame_batch_size=10000, num_workers=0, device
     rank = int(pmd.r.shape[1])
     if n == 0 or rank == 0:
         return np.zeros((rank, n), dtype=np.float32)
-    run = _Run(pmd, device, ctx)
-    try:
-        run.setup()
-        sink = _ToHost(run.ctx, rank, n)
-        run.run(frames, n, frame_batch_size, num_workers, sink)
-        run.ctx.sync()
+    with device_context(pmd, device, ctx) as (ctx, _):
+        sink = ToHost(ctx, rank, n)
+        _Run(ctx, pmd).run(frames, n, frame_batch_size, num_workers, sink)
+        ctx.sync()
         return sink.out
-    finally:
-        run.close()
 
 
 def _movie_bytes(ctx, n_cols, rank, T):
@@ -417,26 +325,22 @@ def project_movie(pmd, dataset_obj, *, frame_batch_size=10000, num_workers=0, de
     rank = int(pmd.r.shape[1])
     if T == 0 or rank == 0:
         raise ValueError("project_movie needs at least one frame and one component (got {} frames, rank {})".format(T, rank))
-    run = _Run(pmd, device, ctx)
-    try:
-        rctx = run.ctx
+    with device_context(pmd, device, ctx) as (ctx, _):
         n_cols = int(pmd.u.shape[1])
-        need = _movie_bytes(rctx, n_cols, rank, T)
-        free = _device_free_bytes(rctx.device)
+        need = _movie_bytes(ctx, n_cols, rank, T)
+        free = _device_free_bytes(ctx.device)
         if need > free:
             raise ValueError("project_movie: the projection of {} frames on {} components needs about {:.1f} GB of device "
                              "memory, {:.1f} GB are free; use PMDArray.project_frames (C batch by batch on the host) "
                              "instead".format(T, rank, need / 1e9, free / 1e9))
-        run.setup()
-        C = torch.empty((rank, T), dtype=torch.float32, device=rctx.device)
+        run = _Run(ctx, pmd)
+        C = torch.empty((rank, T), dtype=torch.float32, device=ctx.device)
         run.run(frames, T, frame_batch_size, num_workers, _OnDevice(C))
-        R_out, s_out, Vt_out = _projected_svd_dev(rctx, run.r, n_cols, rank, C, rank, T, T)
-        rctx.sync()
+        R_out, s_out, Vt_out = _projected_svd_dev(ctx, run.r, n_cols, rank, C, rank, T, T)
+        ctx.sync()
         r_new, s_new, vt_new = R_out.cpu().numpy(), s_out.cpu().numpy(), Vt_out.cpu().numpy()
         good = s_new != 0
         if not np.all(good):
             r_new, s_new, vt_new = r_new[:, good], s_new[good], vt_new[good, :]
         display("Projected {} frames on {} components".format(T, rank))
         return PMDArray(pmd.u, r_new, s_new, vt_new, (T, d1, d2), pmd.order, pmd.mean_img, pmd.var_img)
-    finally:
-        run.close()

@@ -15,13 +15,13 @@ with weights ``W`` (K x D):
 
 The movie is read once in the frame batches of the streamed decomposition (host sources through its pinned staging ring,
 device tensors sliced in place); the traces leave the device batch by batch through the pinned ring of
-``projection._ToHost``.  Device memory does not grow with the movie's length.
+``_stream.ToHost``.  Device memory does not grow with the movie's length.
 """
 import numpy as np
 import scipy.sparse
 
-from .export import EXPORT_BLOCK, _movie_info, export_plan
-from .projection import _device_elem
+from ._stream import (BLOCK, ToHost, VtBlocks, batch_buffer_bytes, block_plan, check_fit, device_context, name_tuple,
+                      read_batches, scaled_r, source_info, upload_f32)
 
 KINDS = ("denoised", "raw", "residual")
 REDUCE = ("mean", "sum")
@@ -44,23 +44,6 @@ class Traces:
 
 
 # ---- argument checks and tables (no device work) --------------------------------------------------------------------
-def _kinds(kinds):
-    if isinstance(kinds, str):
-        kinds = (kinds,)
-    try:
-        kinds = tuple(kinds)
-    except TypeError:
-        raise ValueError("kinds must be a name or a tuple of names from {}".format(KINDS)) from None
-    if not kinds:
-        raise ValueError("kinds is empty; choose from {}".format(KINDS))
-    for k in kinds:
-        if not isinstance(k, str) or k not in KINDS:
-            raise ValueError("unknown kind {!r}; choose from {}".format(k, KINDS))
-    if len(set(kinds)) != len(kinds):
-        raise ValueError("kinds {} name a kind twice".format(kinds))
-    return kinds
-
-
 def roi_weights(rois, fov, order, reduce="sum"):
     """(W, labels): the K x D float64 CSR weight matrix of ``rois`` with columns numbering pixels in C order
     (c = i d2 + j), indices ascending within a row and explicit zeros dropped, and the (K,) int64 labels of its rows.
@@ -248,21 +231,19 @@ def traces_device_bytes(D, nb, esize, K, n_out, n_scratch, nnz_w, n_segs, n_spli
     the PMDArray already holds it on the device."""
     need = 0
     if needs_movie:
-        need += (2 if host_source and n_batches > 1 else 1) * nb * D * esize
+        need += batch_buffer_bytes(nb, D, esize, host_source, n_batches)
         need += 8 * nnz_w + 8 * (SEG_FIELDS * n_segs + SPLIT_FIELDS * n_split) + 4 * n_partial_rows * nb
     need += 4 * K * nb * (2 * n_out + n_scratch)
-    need += 4 * (K * EXPORT_BLOCK + K * rank + K) + 12 * nnz_b + 8 * (K + 1)
+    need += 4 * (K * BLOCK + K * rank + K) + 12 * nnz_b + 8 * (K + 1)
     if rank > 0 and n_cols > 0:
-        need += 4 * rank * EXPORT_BLOCK
+        need += 4 * rank * BLOCK
         if not factors_on_device:
             need += 4 * n_cols * rank
     return need + (1 << 20)     # the allocator's rounding of the small arrays
 
 
 def _check_fit(need, free):
-    if need > free:
-        raise ValueError("extract_traces needs about {:.2f} GB of device memory, {:.2f} GB are free; lower "
-                         "frame_batch_size".format(need / 1e9, free / 1e9))
+    check_fit("extract_traces", need, free)
 
 
 # ---- public entry point --------------------------------------------------------------------------------------------
@@ -279,13 +260,12 @@ def extract_traces(pmd, rois, movie=None, *, kinds=("denoised",), reduce="mean",
     streamed decomposition, uint16 / int16 in their own dtype) and device tensors (sliced in place).  After
     ``pmd.to_device()`` its context and uploaded factors are reused.  Every trace has the same bits for every
     frame_batch_size and source.  Argument errors are raised before any device work and before the movie is read."""
-    from ._lib import Context
     from .decomposition import _device_free_bytes
     from .pmdarray import PMDArray
 
     if not isinstance(pmd, PMDArray):
         raise TypeError("pmd must be a localmd_amd.PMDArray, got {}".format(type(pmd).__name__))
-    kinds = _kinds(kinds)
+    kinds = name_tuple(kinds, KINDS, "kind", "kinds")
     if reduce not in REDUCE:
         raise ValueError("unknown reduce {!r}; choose from {}".format(reduce, REDUCE))
     T, d1, d2 = (int(x) for x in pmd.shape)
@@ -294,7 +274,7 @@ def extract_traces(pmd, rois, movie=None, *, kinds=("denoised",), reduce="mean",
     needs_den = any(k != "raw" for k in kinds)
     if needs_movie and movie is None:
         raise ValueError("kinds {} need the movie: pass movie=".format(tuple(k for k in kinds if k != "denoised")))
-    on_device, esize = _movie_info(movie, pmd.shape) if movie is not None else (False, 4)
+    on_device, esize = source_info(movie, pmd.shape) if movie is not None else (False, 4)
     tabs = roi_tables(rois, (d1, d2), pmd.order, reduce)
     K = tabs["K"]
     n_cols, rank = (int(x) for x in pmd.r.shape)
@@ -303,29 +283,19 @@ def extract_traces(pmd, rois, movie=None, *, kinds=("denoised",), reduce="mean",
         B, offset = denoised_factors(pmd, tabs["W"])
         if B.shape != (K, n_cols):
             raise ValueError("U has {} columns, R has {} rows".format(B.shape[1], n_cols))
-    plan = export_plan(T, frame_batch_size)
+    plan = block_plan(T, frame_batch_size)
     if not plan:        # a movie without frames
         return Traces(tabs["labels"], **{k: np.zeros((K, 0), dtype=np.float32) for k in kinds})
     nb = plan[0][1] - plan[0][0]
 
-    dv = getattr(pmd, "_dev", None)
-    own = False
-    if dv is not None:
-        ctx = dv["ctx"]
-    elif ctx is None:
-        ctx = Context(0 if device is None else int(device))
-        own = True
-    try:
+    with device_context(pmd, device, ctx) as (ctx, dv):
         n_scratch = 1 if "residual" in kinds and "raw" not in kinds else 0
         need = traces_device_bytes(D, nb, esize, K, len(kinds), n_scratch, tabs["pix"].size, len(tabs["segs"]),
                                    len(tabs["split"]), tabs["n_partial_rows"], B.nnz if B is not None else 0, n_cols, rank,
                                    needs_movie, not on_device, len(plan), dv is not None)
         _check_fit(need, _device_free_bytes(ctx.device))
-        out = _extract(ctx, pmd, dv, tabs, B, offset, movie if needs_movie else None, on_device, plan, kinds,
-                       frame_batch_size, num_workers)
-    finally:
-        if own:
-            ctx.close()
+        out = _extract(ctx, pmd, dv, tabs, B, offset, movie if needs_movie else None, plan, kinds, frame_batch_size,
+                       num_workers)
     return Traces(tabs["labels"], **out)
 
 
@@ -356,18 +326,15 @@ class DeviceRoiTables:
                       0 if ws is None else ws.numel())
 
 
-def _extract(ctx, pmd, dv, tabs, B, offset, movie, on_device, plan, kinds, frame_batch_size, num_workers):
+def _extract(ctx, pmd, dv, tabs, B, offset, movie, plan, kinds, frame_batch_size, num_workers):
     import torch
     from ._lib import ptr
-    from .decomposition import _StreamedMovie
-    from .projection import _ToHost
 
     T = int(pmd.shape[0])
     dev = ctx.device
-    K, D = tabs["K"], tabs["D"]
+    K = tabs["K"]
     n_cols, rank = (int(x) for x in pmd.r.shape)
-    f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)   # noqa: E731
-    BL = EXPORT_BLOCK
+    BL = BLOCK
     nb = plan[0][1] - plan[0][0]
     needs_den = B is not None
     product = needs_den and rank > 0 and n_cols > 0
@@ -375,40 +342,23 @@ def _extract(ctx, pmd, dv, tabs, B, offset, movie, on_device, plan, kinds, frame
     ws_bytes = rt.workspace_bytes(nb) if rt is not None else 0
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
     if needs_den:
-        off_dev = f32(offset)
+        off_dev = upload_f32(ctx, offset)
     if product:
-        rs = dv["rs"] if dv is not None else f32(pmd.r * pmd.s[None, :])
+        rs = scaled_r(ctx, pmd, dv)
         wk = torch.empty((K, rank), dtype=torch.float32, device=dev)
         b_ptr = torch.from_numpy(B.indptr.astype(np.int64)).to(dev)
         b_idx = torch.from_numpy(B.indices.astype(np.int32) if B.nnz else np.zeros(1, np.int32)).to(dev)
-        b_val = f32(B.data if B.nnz else np.zeros(1))
+        b_val = upload_f32(ctx, B.data if B.nnz else np.zeros(1))
         ctx.call("pmd_csr_rows_spmm", ptr(b_ptr), ptr(b_idx), ptr(b_val), None, K, ptr(rs), rank, rank, ptr(wk), rank)
-        vtb = torch.empty((rank, BL), dtype=torch.float32, device=dev)
+        vt = VtBlocks(ctx, pmd, dv)
         ct = torch.empty((K, BL), dtype=torch.float32, device=dev)
-    st = {"pin": [None, None], "ev": [None, None], "k": 0}
-
-    def vt_block(c0, m):
-        """Vt[:, c0:c0 + m] into vtb (rank x 1024, the same leading dimension for every block and source)."""
-        if dv is not None:
-            vtb[:, :m].copy_(dv["v"][:, c0:c0 + m])
-            return
-        j = st["k"] % 2
-        st["k"] += 1
-        if st["pin"][j] is None:
-            st["pin"][j] = torch.empty((rank, BL), dtype=torch.float32, pin_memory=True)
-        elif st["ev"][j] is not None:
-            st["ev"][j].synchronize()           # the upload that last read this buffer has finished
-        np.copyto(st["pin"][j][:, :m].numpy(), pmd.v[:, c0:c0 + m], casting="unsafe")
-        vtb[:, :m].copy_(st["pin"][j][:, :m], non_blocking=True)
-        st["ev"][j] = torch.cuda.Event()
-        st["ev"][j].record(torch.cuda.current_stream(dev))
-
-    sink = _ToHost(ctx, len(kinds) * K, T)
+    sink = ToHost(ctx, len(kinds) * K, T)
     scratch = (torch.empty(K * nb, dtype=torch.float32, device=dev)
                if "residual" in kinds and "raw" not in kinds else None)
     F = 4   # bytes per output value
+    blocks_of = {b0: blocks for b0, _, blocks in plan}
 
-    def consume(batch, elem, b0, n, blocks):
+    def consume(batch, elem, b0, n):
         buf, ld = sink.dst(b0, n)
         row = {k: buf.data_ptr() + F * j * K * ld for j, k in enumerate(kinds)}      # K x n panels, ld n
         raw_p = row.get("raw", scratch.data_ptr() if scratch is not None else None)
@@ -416,29 +366,16 @@ def _extract(ctx, pmd, dv, tabs, B, offset, movie, on_device, plan, kinds, frame
             rt.gather(batch, elem, n, _Ptr(raw_p), ld, ws)
         if needs_den:
             den_p, res_p = row.get("denoised"), row.get("residual")
-            for c0, c1 in blocks:
+            for c0, c1 in blocks_of[b0]:
                 m, o = c1 - c0, F * (c0 - b0)
                 if product:
-                    vt_block(c0, m)
-                    ctx.call("pmd_gemm", 0, 0, K, m, rank, 1.0, ptr(wk), rank, ptr(vtb), BL, 0.0, ptr(ct), BL)
+                    vt.load(c0, m)
+                    ctx.call("pmd_gemm", 0, 0, K, m, rank, 1.0, ptr(wk), rank, ptr(vt.buf), BL, 0.0, ptr(ct), BL)
                 ctx.call("pmd_roi_combine", K, m, ptr(ct) if product else None, BL, ptr(off_dev),
                          _cp(raw_p, o) if res_p is not None else None, ld, _cp(den_p, o), ld, _cp(res_p, o), ld)
         sink.done(b0, n)
 
-    if movie is None:
-        for b0, b1, blocks in plan:
-            consume(None, 0, b0, b1 - b0, blocks)
-    elif on_device:
-        for b0, b1, blocks in plan:
-            b = movie[b0:b1].to(dev).reshape(b1 - b0, D)
-            elem = _device_elem(b)
-            if elem is None:
-                b, elem = b.to(torch.float32), 0
-            consume(b.contiguous(), elem, b0, b1 - b0, blocks)
-    else:
-        src = _StreamedMovie(ctx, movie, frame_batch_size, num_workers=num_workers)
-        blocks_of = {b0: blocks for b0, _, blocks in plan}
-        src.run_pass(lambda batch, b0, n: consume(batch, src.elem, b0, n, blocks_of[b0]))
+    read_batches(ctx, movie, [(b0, b1) for b0, b1, _ in plan], frame_batch_size, num_workers, consume)
     sink.finish()
     ctx.sync()
     return {k: np.ascontiguousarray(sink.out[j * K:(j + 1) * K]) for j, k in enumerate(kinds)}
