@@ -4,6 +4,7 @@ pixel lists, pooling windows, overlap pairs, frame sampling, argument validation
 Mirrors /root/reference/localmd/decomposition.py:528-635 and :695-754.
 """
 import math
+from typing import NamedTuple
 
 import numpy as np
 
@@ -52,6 +53,68 @@ def identify_window_chunks(frame_range: int, total_frames: int, window_chunks: i
     for k in starts:
         frames.extend(range(int(k), int(min(k + window_chunks, total_frames))))
     return frames
+
+
+def select_frames(total_frames: int, frame_range: int, window_chunks, display=None, share=None):
+    """(frames to fit on, frame_range, window_chunks) as decomposition.py:678-693 settles them.  The windows are drawn
+    from the global np.random state (identify_window_chunks); ``share`` (e.g. a broadcast from rank 0) replaces the
+    drawn list by the one every process must use."""
+    say = display if display is not None else (lambda msg: None)
+    if window_chunks is None:
+        window_chunks = frame_range
+    if total_frames < frame_range:
+        say("WARNING: Specified using more frames than there are in the dataset.")
+        frame_range = total_frames
+        frames = list(range(total_frames))
+        if frame_range <= window_chunks:
+            window_chunks = frame_range
+    else:
+        if frame_range <= window_chunks:
+            window_chunks = frame_range
+        frames = identify_window_chunks(frame_range, total_frames, window_chunks, display=display)
+        if share is not None:
+            frames = share(frames)
+    say("We are initializing on a total of {} frames".format(len(frames)))
+    return frames, frame_range, window_chunks
+
+
+class Windows(NamedTuple):
+    """Temporal plan of the tile fits: the first ``crop`` fitted frames, in windows of ``win_len`` frames."""
+    max_components: int
+    crop: int
+    win_len: int
+    win_starts: list
+    a_f: int            # temporal_avg_factor
+
+
+def temporal_windows(n_frames: int, window_chunks: int, temporal_avg_factor: int, max_components: int, display=None) -> Windows:
+    """Rank cap, cropped frame count (decomposition.py:757-774) and the windows of windowed_pmd (:455-463): starts
+    every win_len frames, the last window pulled back so that it ends at ``crop``."""
+    if temporal_avg_factor >= n_frames:
+        raise ValueError("Need at least {} frames".format(temporal_avg_factor))
+    if n_frames // temporal_avg_factor <= max_components:
+        if display is not None:
+            display(
+                f"WARNING: temporal avg factor is too big, max rank per block adjusted to {n_frames // temporal_avg_factor}.\n"
+                "To avoid this, initialize with more frames or reduce temporal avg factor")
+        max_components = int(n_frames // temporal_avg_factor)
+    crop = (n_frames // temporal_avg_factor) * temporal_avg_factor
+    win_len = int(min(window_chunks, crop))
+    win_starts = list(range(0, crop, win_len))
+    if win_starts[-1] + win_len > crop:
+        win_starts[-1] = crop - win_len
+    if len(win_starts) > 1 and win_len % temporal_avg_factor != 0:
+        raise ValueError("window_chunks must be a multiple of temporal_avg_factor")
+    return Windows(int(max_components), crop, win_len, win_starts, int(temporal_avg_factor))
+
+
+def tile_batches(n_tiles: int, n_windows: int, per_tile_bytes: int, tile_batch_bytes: int) -> list:
+    """[(lo, hi)] runs of tiles fitted (and later projected) together: as many as fit in tile_batch_bytes, at least 8;
+    one run when everything fits, and always when there are several temporal windows."""
+    tile_batch = max(8, int(tile_batch_bytes // per_tile_bytes))
+    if n_windows != 1:
+        return [(0, n_tiles)]
+    return [(b0, min(n_tiles, b0 + tile_batch)) for b0 in range(0, max(n_tiles, 1), tile_batch)]
 
 
 def tile_origins(fov, block_sizes):

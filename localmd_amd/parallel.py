@@ -6,7 +6,9 @@ decomposes its run; the only exchange is the gather of the per-tile results befo
 recombination.  The Gaussian test matrix of tile b is keyed by b (counter-based RNG), so the result
 does not depend on the number of ranks.
 """
-from typing import List, Tuple
+from typing import List, NamedTuple, Tuple
+
+from . import grid
 
 
 def tile_partition(n_tiles: int, world: int) -> List[Tuple[int, int]]:
@@ -18,6 +20,46 @@ def tile_partition(n_tiles: int, world: int) -> List[Tuple[int, int]]:
         out.append((lo, hi))
         lo = hi
     return out
+
+
+class Ownership(NamedTuple):
+    """Which part of the field of view one rank works on.  Pixel ranges are C-order pixel ids."""
+    world: int
+    rank: int
+    runs: list      # [lo, hi) tiles of every rank (bands of tile rows)
+    t_lo: int       # this rank's run
+    t_hi: int
+    i_lo: int       # FOV rows its tiles touch: the pixel slab it keeps resident ...
+    i_hi: int
+    P_lo: int       # ... as pixel ids
+    P_hi: int
+    O_lo: int       # pixels it OWNS for sums over pixels: the slab minus the halo shared with the next rank
+    O_hi: int
+    owned: list     # owned range of every rank
+
+    @property
+    def enabled(self):
+        return self.world > 1
+
+
+def ownership_plan(fov, block_sizes, world: int, rank: int) -> Ownership:
+    """Rank r decomposes a band of tile rows (tile_partition of the rows) and keeps only the FOV rows those tiles
+    touch; every pixel is owned by exactly one rank.  One process: slab = owned range = the whole field of view."""
+    d1, d2 = (int(x) for x in fov)
+    blocks = grid.update_block_sizes(list(block_sizes), (d1, d2), display=None)
+    o1, o2 = grid.tile_origins((d1, d2), blocks)
+    n1, n2 = len(o1), len(o2)
+    if world > 1 and world > n1:
+        raise ValueError("distributed=True needs at least one tile row per rank ({} rows, {} ranks)".format(n1, world))
+    row_runs = tile_partition(n1, world)
+    runs = [(a * n2, b * n2) for a, b in row_runs]
+    a_lo, a_hi = row_runs[rank]
+    i_lo, i_hi = (int(o1[a_lo]), int(o1[a_hi - 1]) + int(blocks[0])) if world > 1 else (0, d1)
+    own_starts = [int(o1[a]) for a, _ in row_runs] + [d1]
+    own_starts[0] = 0
+    owned = [(own_starts[k] * d2, own_starts[k + 1] * d2) for k in range(world)]
+    t_lo, t_hi = runs[rank]
+    return Ownership(world, rank, runs, t_lo, t_hi, i_lo, i_hi, i_lo * d2, i_hi * d2, owned[rank][0], owned[rank][1], owned)
 
 
 class Dist:
