@@ -37,7 +37,9 @@ extern "C" {
 typedef struct pmd_ctx pmd_ctx;
 
 int pmd_version(void);
-/* hip_stream: a hipStream_t (0 = the null stream).  The context never owns the stream. */
+/* hip_stream: a hipStream_t (0 = the null stream).  The context never owns the stream.
+ * The PMD_* route switches (A/B comparators) are read from the environment when a context is
+ * created and are fixed for that context; nothing else in the library reads the environment. */
 int pmd_ctx_create(int device, void* hip_stream, pmd_ctx** out);
 int pmd_ctx_destroy(pmd_ctx* ctx);
 int pmd_ctx_set_stream(pmd_ctx* ctx, void* hip_stream);

@@ -5,6 +5,54 @@
 #define CTX_CHECK(ctx) \
   if (!(ctx)) return PMD_ERR_ARG;
 
+// ---------------------------------------------------------------- route switches ----------
+// Every PMD_* variable the library reads, in the order of DESIGN.md section 6a.  A row with accepted values maps each text
+// to the field's value; a row without any takes a number.  Unset, or a text that is not accepted: the default.
+namespace {
+struct route_value { const char* text; int value; };
+struct route_row {
+  const char* name;
+  int pmd_routes::*field;
+  double pmd_routes::*real_field;    // set instead of `field` for the one fractional knob
+  double dflt;
+  route_value accepted[4];           // ends at the first NULL text
+};
+const route_row ROUTE_TABLE[] = {
+    {"PMD_SYEVD", &pmd_routes::syevd, nullptr, PMD_SYEVD_AUTO,
+     {{"f64", PMD_SYEVD_F64}, {"rocsolver", PMD_SYEVD_ROCSOLVER}, {"own", PMD_SYEVD_OWN}, {"twostage", PMD_SYEVD_TWOSTAGE}}},
+    {"PMD_APPLY_Q", &pmd_routes::apply_q_rocsolver, nullptr, 0, {{"rocsolver", 1}}},
+    {"PMD_SYR2K", &pmd_routes::syr2k_rocblas, nullptr, 0, {{"rocblas", 1}}},
+    {"PMD_CHOLESKY", &pmd_routes::cholesky_rocsolver, nullptr, 0, {{"rocsolver", 1}}},
+    {"PMD_CHOL_CHAIN", &pmd_routes::chol_chain_rocblas, nullptr, 0, {{"rocblas", 1}}},
+    {"PMD_SYTRD_ADVANCE", &pmd_routes::sytrd_advance_old, nullptr, 0, {{"old", 1}}},
+    {"PMD_GEMM_SPLIT", &pmd_routes::gemm_split, nullptr, 1, {{"0", 0}}},
+    {"PMD_GEMM_SPLIT_MIN_GFLOP", nullptr, &pmd_routes::gemm_split_min_gflop, 100.0, {}},
+    {"PMD_GEMM_SPLIT_MIN_DIM", &pmd_routes::gemm_split_min_dim, nullptr, 256, {}},
+    {"PMD_GEMM_SPLITK", &pmd_routes::gemm_splitk, nullptr, 1, {{"0", 0}}},
+    {"PMD_GEMM_KCHUNK", &pmd_routes::gemm_kchunk, nullptr, -1, {}},
+    {"PMD_F16X2_MTGM", &pmd_routes::f16x2_mtgm, nullptr, 6, {{"0", 0}}},
+    {"PMD_GRAM_APPLY_MFMA", &pmd_routes::gram_apply_mfma, nullptr, 1, {{"0", 0}}},
+    {"PMD_GRAM_MFMA", &pmd_routes::gram_mfma, nullptr, 1, {{"0", 0}}},
+    {"PMD_ROWMIX_MFMA", &pmd_routes::rowmix_mfma, nullptr, -1, {{"0", 0}, {"16", 16}, {"64", 64}}},
+    {"PMD_ATX_DMA", &pmd_routes::atx_dma, nullptr, 1, {{"0", 0}}},
+    {"PMD_TILE_WHITEN", &pmd_routes::tile_whiten_eig, nullptr, 0, {{"eig", 1}}},
+    {"PMD_WIDE_EIG", &pmd_routes::wide_eig_syevd, nullptr, 0, {{"syevd", 1}}},
+    {"PMD_SMALL_EIG", &pmd_routes::small_eig_rocsolver, nullptr, 0, {{"rocsolver", 1}}},
+};
+
+void pmd_routes_from_env(pmd_routes* r) {
+  for (const route_row& row : ROUTE_TABLE) {
+    const char* text = getenv(row.name);
+    double v = row.dflt;
+    if (text && !row.accepted[0].text) v = atof(text);
+    for (const route_value& a : row.accepted)
+      if (text && a.text && !strcmp(text, a.text)) v = a.value;
+    if (row.real_field) r->*row.real_field = v;
+    else r->*row.field = (int)v;
+  }
+}
+}  // namespace
+
 extern "C" {
 
 int pmd_version(void) { return 1; }
@@ -27,17 +75,8 @@ int pmd_ctx_create(int device, void* hip_stream, pmd_ctx** out) {
   ctx->atx_rows = 0;
   ctx->split_ws = nullptr;
   ctx->split_ws_bytes = 0;
-  {
-    // PMD_GEMM_SPLIT=0: every product through rocBLAS sgemm; default: products of >= PMD_GEMM_SPLIT_MIN_GFLOP (100) GFLOP with no
-    // dimension below PMD_GEMM_SPLIT_MIN_DIM (256) run as three fp16-piece products on the fp16 matrix cores (gemm_f16x2.hip)
-    const char* gs = getenv("PMD_GEMM_SPLIT");
-    ctx->gemm_split = (gs && !strcmp(gs, "0")) ? 0 : 1;
-    const char* gm = getenv("PMD_GEMM_SPLIT_MIN_GFLOP");
-    ctx->gemm_split_min_flop = (gm ? atof(gm) : 100.0) * 1e9;
-    const char* gd = getenv("PMD_GEMM_SPLIT_MIN_DIM");
-    ctx->gemm_split_min_dim = gd ? atoi(gd) : 256;
-    ctx->f16x2 = nullptr;
-  }
+  pmd_routes_from_env(&ctx->routes);
+  ctx->f16x2 = nullptr;
   ctx->blas = nullptr;
   ctx->err[0] = 0;
   ctx->profile = false;

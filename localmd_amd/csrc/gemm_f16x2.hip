@@ -198,9 +198,10 @@ void pmd_f16x2_destroy(pmd_ctx* ctx) {
 
 // which products take this path: PMD_GEMM_SPLIT=0 none; PMD_GEMM_SPLIT_MIN_GFLOP (default 100) sets the size gate
 bool pmd_f16x2_wanted(const pmd_ctx* ctx, int m, int n, int k) {
-  if (!ctx->gemm_split) return false;
-  if (m < ctx->gemm_split_min_dim || n < ctx->gemm_split_min_dim || k < ctx->gemm_split_min_dim) return false;
-  return 2.0 * m * (double)n * k >= ctx->gemm_split_min_flop;
+  const pmd_routes& r = ctx->routes;
+  if (!r.gemm_split) return false;
+  if (m < r.gemm_split_min_dim || n < r.gemm_split_min_dim || k < r.gemm_split_min_dim) return false;
+  return 2.0 * m * (double)n * k >= r.gemm_split_min_gflop * 1e9;
 }
 
 static inline int vec_ok(const void* p, int cols, long ld) { (void)cols; return (ld % 4 == 0) && (((uintptr_t)p & 15) == 0); }

@@ -40,9 +40,8 @@ __global__ void sum_partials_kernel(const float* __restrict__ part, long mn, int
 
 // Length of one fp32 accumulation chain in the library's GEMM-shaped products (PMD_GEMM_KCHUNK overrides; 0 = whole k):
 // 1024 up to k = 16384, 2048 beyond (the output is re-read once per chunk: 12 % / 6 % of the product's time).
-int pmd_gemm_k_chunk(int k) {
-  static int forced = -2;
-  if (forced == -2) { const char* e = getenv("PMD_GEMM_KCHUNK"); forced = e ? atoi(e) : -1; }
+int pmd_gemm_k_chunk(const pmd_ctx* ctx, int k) {
+  const int forced = ctx->routes.gemm_kchunk;
   if (forced == 0) return k;
   if (forced > 0) return forced;
   if (k <= 3072) return k;
@@ -95,16 +94,15 @@ int pmd_gemm_rm(pmd_ctx* ctx, int transA, int transB, int m, int n, int k, float
   }
   {
     // fewer than one 128 x 128 output tile per CU and an inner dimension that leaves >= 4096 per slice
-    static int mode = -1;   // PMD_GEMM_SPLITK=0 switches the path off (A/B runs)
-    if (mode < 0) { const char* e = getenv("PMD_GEMM_SPLITK"); mode = (e && !strcmp(e, "0")) ? 0 : 1; }
+    // (PMD_GEMM_SPLITK=0 switches the path off, A/B runs)
     const long tiles = (long)((m + 127) / 128) * ((n + 127) / 128);
-    if (mode && tiles < 256 && k >= 16384) {
+    if (ctx->routes.gemm_splitk && tiles < 256 && k >= 16384) {
       int S = (int)std::min<long>(std::min<long>(64, k / 4096), (512 + tiles - 1) / tiles);
       if (S >= 2) return gemm_rm_splitk(ctx, transA, transB, m, n, k, S, alpha, A, lda, B, ldb, beta, C, ldc);
     }
   }
   pmd_prof_scope prof__(ctx, "rocblas_sgemm");
-  const int kc = pmd_gemm_k_chunk(k);
+  const int kc = pmd_gemm_k_chunk(ctx, k);
   if (kc < k && !pmd_is_host_pointer(C)) {
     // Long inner dimension: rocBLAS carries ONE fp32 accumulation chain over all of k (measured on MI355X, scripts/
     // gemm_bias_probe.py: entry errors of 4.9e-6 of the diagonal at k = 10^4, against 3.8e-7 when the chain is cut every
@@ -462,7 +460,7 @@ int pmd_projected_svd_impl(pmd_ctx* ctx, const float* P, int rows_p, long ldp, c
     const float one = 1.f, zero = 0.f;
     // (inner dimension in chunks: one fp32 accumulation chain per chunk, see pmd_gemm_rm)
     const int kfull = (n1 <= n2) ? n2 : n1;
-    const int kc = pmd_gemm_k_chunk(kfull);
+    const int kc = pmd_gemm_k_chunk(ctx, kfull);
     for (int k0 = 0; k0 < kfull; k0 += kc) {
       const int kk = std::min(kc, kfull - k0);
       if (n1 <= n2)  // V V^T
@@ -524,7 +522,7 @@ int pmd_projected_svd_impl(pmd_ctx* ctx, const float* P, int rows_p, long ldp, c
 static int psvd_gram_rows(pmd_ctx* ctx, const float* V, int n1, int n2, long ldv, float* C, long ldc) {
   pmd_prof_scope prof__(ctx, "rocblas_ssyrk");
   const float one = 1.f, zero = 0.f;
-  const int kc = pmd_gemm_k_chunk(n2);
+  const int kc = pmd_gemm_k_chunk(ctx, n2);
   if (n2 <= 0) { PMD_HIP(ctx, hipMemsetAsync(C, 0, (size_t)n1 * ldc * sizeof(float), ctx->stream)); return PMD_OK; }
   for (int k0 = 0; k0 < n2; k0 += kc) {
     const int kk = std::min(kc, n2 - k0);
@@ -926,8 +924,7 @@ int pmd_gram_apply_impl(pmd_ctx* ctx, const float* Gblk, const float* Gbg, const
   {
     pmd_prof_scope prof__(ctx, "gram_apply");
     dim3 grid((ncols + 255) / 256, n_tiles);
-    const char* gam = getenv("PMD_GRAM_APPLY_MFMA");
-    const bool mfma_ok = !(gam && atoi(gam) == 0) && ldm % 4 == 0 && ldgm % 4 == 0 && ((uintptr_t)M & 15) == 0 &&
+    const bool mfma_ok = ctx->routes.gram_apply_mfma && ldm % 4 == 0 && ldgm % 4 == 0 && ((uintptr_t)M & 15) == 0 &&
                          ((uintptr_t)GM & 15) == 0 && max_rank <= 64;
     if (mfma_ok) {
       const int ct = (max_rank + 15) / 16;
@@ -1180,14 +1177,9 @@ int pmd_projected_svd_factored_impl(pmd_ctx* ctx, const float* M, int Rc, int m,
 #define CHOL_NB 128
 // n_abs_last > 0: a negative pivot number n_abs_last (1-based, the LAST pivot of the whole matrix) is replaced by its
 // absolute value - the Cholesky-route form of the reference keeping a numerically null direction through |lambda|.
-// linv_out != NULL: the inverse of the factor, row-major lower triangle L^{-1} with leading dimension CHOL_NB (zeros above the
-// diagonal), is formed in the same launch (dynamic LDS: two CHOL_NB x CHOL_LS float arrays): the factor goes to LDS, thread c
-// solves L x = e_c by forward substitution (column c of the inverse, kept in LDS).  This replaces rocBLAS' strtri on the
-// block (five launches, 150 us in its diagonal kernel) in the latency-bound chain of the blocked factorisation.
 #define CHOL_LS (CHOL_NB + 1)
 __global__ __launch_bounds__(256) void potf2_block_kernel(float* __restrict__ A, long ld, int nb, int k0, int* __restrict__ info,
-                                                          int n_abs_last, float* __restrict__ linv_out) {
-  extern __shared__ float chol_dyn[];
+                                                          int n_abs_last) {
   __shared__ float s_col[2][CHOL_NB];
   const int tid = threadIdx.x;
   const int tr = tid >> 4, tc = tid & 15;
@@ -1261,58 +1253,6 @@ __global__ __launch_bounds__(256) void potf2_block_kernel(float* __restrict__ A,
       const int r = tr + 16 * i, c = tc + 16 * j;
       if (r < nb && c <= r) A[(long)r * ld + c] = a[i][j];
     }
-  if (!linv_out) return;
-  float* Ls = chol_dyn;
-  float* Xs = chol_dyn + CHOL_NB * CHOL_LS;
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int r = tr + 16 * i, c = tc + 16 * j;
-      if (r < nb && c <= r) Ls[r * CHOL_LS + c] = a[i][j];
-    }
-  __syncthreads();
-  {
-    // two lanes per column (even / odd k), 32 columns per wave; the inner sums take four (k, k + 2, k + 4, k + 6) terms per
-    // lane and trip with all eight LDS reads issued before the first product (a plain loop waits out one LDS latency per term:
-    // 430 us instead of 40).  A wave only reads inverse entries it wrote itself: wave-level ordering is enough.
-    const int c = tid >> 1, h = tid & 1;
-    const int c0 = __builtin_amdgcn_readfirstlane(c & ~31);
-    if (h == 0 && c < nb) Xs[c * CHOL_LS + c] = 1.f / Ls[c * CHOL_LS + c];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    for (int i = c0 + 1; i < nb; ++i) {
-      const float* lrow = Ls + i * CHOL_LS;
-      float acc0 = 0.f, acc1 = 0.f;
-      for (int k = c0 + h; k < i; k += 8) {
-        float lv[4], xv[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int kk = min(k + 2 * u, CHOL_NB - 1);
-          lv[u] = lrow[kk];
-          xv[u] = Xs[kk * CHOL_LS + min(c, CHOL_NB - 1)];
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int kk = k + 2 * u;
-          const float t = (kk < i && kk >= c) ? lv[u] * xv[u] : 0.f;   // (entries never written are masked, not multiplied)
-          if (u & 1) acc1 += t; else acc0 += t;
-        }
-      }
-      float acc = acc0 + acc1;
-      acc += __shfl_xor(acc, 1);
-      if (h == 0 && i > c && c < nb) Xs[i * CHOL_LS + c] = -acc / lrow[i];
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
-  }
-  __syncthreads();
-  for (int idx = tid; idx < nb * nb; idx += 256) {
-    const int i = idx / nb, c = idx - i * nb;
-    linv_out[(long)i * CHOL_NB + c] = (c <= i) ? Xs[i * CHOL_LS + c] : 0.f;
-  }
 }
 
 // Panel of the blocked factorisation, in place: P (rest x nb, row-major, leading dimension ld) <- P L^{-T}, with
@@ -1381,30 +1321,19 @@ static int chol_lower_rm(pmd_ctx* ctx, int n, float* A, long ld, int* info, floa
   PMD_HIP(ctx, hipMemsetAsync(linv, 0, sizeof(float) * CHOL_NB * CHOL_NB, ctx->stream));
   const float one = 1.f, minus1 = -1.f;
   // PMD_CHOL_CHAIN=rocblas: the earlier chain (strtri on the block, panel by sgemm into a copy) for A/B runs
-  static int own_chain = -1;
-  if (own_chain < 0) { const char* e = getenv("PMD_CHOL_CHAIN"); own_chain = (e && !strcmp(e, "rocblas")) ? 0 : 1; }
-  // PMD_CHOL_FUSED=1: factor and invert the diagonal block in one launch (132 KB of LDS: faster alone, slower next to the
-  // large products of the main stream, see chol_panel_kernel)
-  static int fused_inv = -1;
-  if (fused_inv < 0) { const char* e = getenv("PMD_CHOL_FUSED"); fused_inv = (e && !strcmp(e, "1")) ? 1 : 0; }
-  const size_t lds = 2 * (size_t)CHOL_NB * CHOL_LS * sizeof(float);
-  if (own_chain && fused_inv)
-    PMD_HIP(ctx, hipFuncSetAttribute((const void*)potf2_block_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  const bool own_chain = !ctx->routes.chol_chain_rocblas;
   for (int k0 = 0; k0 < n; k0 += CHOL_NB) {
     const int nb = std::min(CHOL_NB, n - k0);
     float* D = A + (long)k0 * ld + k0;
     const int rest = n - k0 - nb;
-    const bool fused = own_chain && fused_inv && rest > 0;
-    hipLaunchKernelGGL(potf2_block_kernel, dim3(1), dim3(256), fused ? lds : 0, ctx->stream, D, ld, nb, k0, info, abs_last_pivot ? n : -1,
-                       fused ? linv : (float*)nullptr);
+    hipLaunchKernelGGL(potf2_block_kernel, dim3(1), dim3(256), 0, ctx->stream, D, ld, nb, k0, info, abs_last_pivot ? n : -1);
     PMD_LAUNCH_CHECK(ctx, "potf2_block_kernel");
     if (rest <= 0) break;
     float* P = A + (long)(k0 + nb) * ld + k0;        // row-major rest x nb  ==  column-major nb x rest
     float* T22 = A + (long)(k0 + nb) * ld + (k0 + nb);
     if (own_chain) {
       // L21 = A21 L_kk^{-T} in place (+ a compact copy for the trailing update)
-      if (!fused)
-        PMD_BLAS(ctx, rocblas_strtri(ctx->blas, rocblas_fill_upper, rocblas_diagonal_non_unit, nb, D, (rocblas_int)ld, linv, CHOL_NB));
+      PMD_BLAS(ctx, rocblas_strtri(ctx->blas, rocblas_fill_upper, rocblas_diagonal_non_unit, nb, D, (rocblas_int)ld, linv, CHOL_NB));
       hipLaunchKernelGGL(chol_panel_kernel, dim3((rest + CHOL_PR - 1) / CHOL_PR), dim3(256), 0, ctx->stream, P, ld, rest, nb, linv, tmp);
       PMD_LAUNCH_CHECK(ctx, "chol_panel_kernel");
       PMD_BLAS(ctx, rocblas_ssyrk(ctx->blas, rocblas_fill_upper, rocblas_operation_transpose, rest, nb, &minus1, tmp, CHOL_NB, &one,
@@ -1450,12 +1379,8 @@ int pmd_gram_mtgm_impl(pmd_ctx* ctx, const float* M, int rows, int m, long ldm, 
   if (ar.overflow) return pmd_fail(ctx, PMD_ERR_WORKSPACE, "pmd_gram_mtgm", "workspace too small");
   // row blocks C[i0:i0+bs, 0:i0+bs] = Mt[i0:i0+bs, :] GM[:, 0:i0+bs]  (3/5 of the flops at 5 blocks)
   RUN(launch_transpose(ctx, M, ldm, rows, m, Mt, ldt));
-  const char* cbenv = getenv("PMD_C_BLOCKS");
-  const int nblk = cbenv ? std::max(1, atoi(cbenv)) : 5;  // 2/3/4/5/6/8/12/16 blocks at m = 10^4: 70/64/57/52/59/58/60/67 ms
-  const int bs = std::max(256, ((m + nblk - 1) / nblk + 255) / 256 * 256);
-  // fp16-piece products (gemm_f16x2.hip): both operands are split ONCE, the row blocks are views of the pieces
-  bool pieces = false;
-  pmd_f16x2_op ma, gb;
+  constexpr int MTGM_ROW_BLOCKS = 5;  // 2/3/4/5/6/8/12/16 blocks at m = 10^4: 70/64/57/52/59/58/60/67 ms
+  const int bs = std::max(256, ((m + MTGM_ROW_BLOCKS - 1) / MTGM_ROW_BLOCKS + 255) / 256 * 256);
   // C is singular by construction on the R > frames route (its last pivot is the null direction, 3e-12 of the mean diagonal on
   // the headline fixture) and the Cholesky step needs every other pivot positive: this is the one product of the stage whose
   // error structure decides whether the route works at all.  Measured on that fixture (scripts/debug_headline.py): two fp16
@@ -1466,28 +1391,20 @@ int pmd_gram_mtgm_impl(pmd_ctx* ctx, const float* M, int rows, int m, long ldm, 
   // PMD_F16X2_MTGM: 6 (default) = those six products as ONE matrix product per chunk of pmd_gemm_k_chunk(k) inner indices
   // (the "concatenated" form of gemm_f16x2.hip: C is revisited once per chunk, as on the fp32 path: 34 ms against 52 at
   // config 3, s 1.18e-4 / Vt 8.5e-4 / U R 1.05e-1 against the arbiter where sgemm gives 1.11e-4 / 1.2-1.5e-3 / 5.5-6.8e-2);
-  // 3 = six separate products per chunk (42 ms at config 3, but 870 against 690 ms at BASELINE config 4: C is re-read and
-  // re-written six times per chunk); 2 = two pieces (breaks the fixture); 0 = sgemm.
-  static int mtgm_pieces = -1;
-  if (mtgm_pieces < 0) {
-    const char* e = getenv("PMD_F16X2_MTGM");
-    mtgm_pieces = e ? atoi(e) : 6;
-    if (mtgm_pieces != 2 && mtgm_pieces != 3 && mtgm_pieces != 6) mtgm_pieces = 0;
-  }
-  int pm = mtgm_pieces;
+  // 0 = sgemm.  (Six separate products per chunk took 42 ms at config 3, but 870 against 690 ms at BASELINE config 4: C is
+  // re-read and re-written six times per chunk.)
   // (not where the output is small and the inner dimension huge - the many-tile workloads: 10^3 x 10^3 outputs, k = 3 10^5 -
   // there one strided-batched split-K sgemm, pmd_gemm_rm, beats 150 chunks of tiny products)
   const long out_tiles = (long)((std::min(bs, m) + 127) / 128) * ((m + 127) / 128);
-  if (pm == 6 && out_tiles < 256) pm = 0;
-  if (pm == 6 && pmd_f16x2_wanted(ctx, std::min(bs, m), m, rows)) {
-    // PMD_F16X2_MTGM=6: the six piece products of three exact pieces per operand as ONE matrix product per accumulation chunk
+  if (ctx->routes.f16x2_mtgm == 6 && out_tiles >= 256 && pmd_f16x2_wanted(ctx, std::min(bs, m), m, rows)) {
+    // the six piece products of three exact pieces per operand as ONE matrix product per accumulation chunk
     // (gemm_f16x2.hip, "concatenated" form): C is revisited once per chunk, as on the fp32 path, not six times
     const float* X[2] = {Mt, GM};
     const int xr[2] = {m, rows}, xc[2] = {rows, m};
     const long xl[2] = {ldt, ldgm};
     int ex[2] = {0, 0}, usable = 0;
     RUN(pmd_f16x2_exponents(ctx, 2, X, xr, xc, xl, ex, &usable));
-    const int kc = pmd_gemm_k_chunk(rows);
+    const int kc = pmd_gemm_k_chunk(ctx, rows);
     const long lda6 = 6L * pmd_round_up(kc, 8), ldb6 = pmd_round_up(m, 8);
     void* w = nullptr;
     if (usable) RUN(pmd_split_scratch(ctx, ((size_t)bs * lda6 + 6 * (size_t)kc * ldb6) * sizeof(_Float16) + 512, &w));
@@ -1511,59 +1428,17 @@ int pmd_gram_mtgm_impl(pmd_ctx* ctx, const float* M, int rows, int m, long ldm, 
       if (ok6) return PMD_OK;
     }
   }
-  if (pm == 6) pm = 0;
-  if (pm && pmd_f16x2_wanted(ctx, std::min(bs, m), m, rows)) {
-    const size_t na = pmd_f16x2_bytes(m, rows, pm), nb = pmd_f16x2_bytes(rows, m, pm);
-    void* w = nullptr;
-    RUN(pmd_split_scratch(ctx, na + nb, &w));
-    const float* X[2] = {Mt, GM};
-    if (w) {
-    const int xr[2] = {m, rows}, xc[2] = {rows, m};
-    const long xl[2] = {ldt, ldgm};
-    void* buf[2] = {w, (char*)w + na};
-    pmd_f16x2_op ops[2];
-    int usable = 0;
-    RUN(pmd_f16x2_split(ctx, 2, X, xr, xc, xl, buf, ops, &usable, pm));
-    if (usable) { pieces = true; ma = ops[0]; gb = ops[1]; }
-    }
-  }
   for (int i0 = 0; i0 < m; i0 += bs) {
     const int nr = std::min(bs, m - i0);
-    if (pieces) {
-      pmd_f16x2_op a = ma;
-      a.h1 += (long)i0 * ma.ld;
-      a.h2 += (long)i0 * ma.ld;
-      if (a.h3) a.h3 += (long)i0 * ma.ld;
-      // inner dimension in chunks: one fp32 accumulation chain per chunk, of the length the fp32 path uses (the matrix-core
-      // kernel otherwise carries one chain over all of k); PMD_F16X2_MTGM_KCHUNK overrides
-      static int kch_env = -2;
-      if (kch_env == -2) { const char* e = getenv("PMD_F16X2_MTGM_KCHUNK"); kch_env = e ? atoi(e) : -1; }
-      const int kch = kch_env > 0 ? kch_env : (kch_env == 0 ? rows : pmd_gemm_k_chunk(rows));
-      int done = 1;
-      for (int k0 = 0; k0 < rows && done; k0 += kch) {
-        const int kk = std::min(kch, rows - k0);
-        pmd_f16x2_op ak = a, bk = gb;
-        ak.h1 += k0; ak.h2 += k0;
-        if (ak.h3) ak.h3 += k0;
-        bk.h1 += (long)k0 * gb.ld; bk.h2 += (long)k0 * gb.ld;
-        if (bk.h3) bk.h3 += (long)k0 * gb.ld;
-        RUN(pmd_f16x2_matmul(ctx, 0, 0, nr, i0 + nr, kk, 1.f, ak, bk, k0 ? 1.f : 0.f, C + (long)i0 * ldc, ldc, &done));
-      }
-      if (done) continue;
-      pieces = false;   // (the product below may reuse the scratch that held the pieces)
-    }
     // the fp32 product: no piece route above produced this block, and pmd_gemm_rm's own fp16-piece product (two pieces in ONE
     // chain over all of `rows`, gemm_f16x2.hip) is the arithmetic that breaks this product (the many-tile workloads, where
     // the concatenated route is gated off, have row blocks above its size gate: 4x the fp32 error at 1000 x 309 827)
-    const int keep = ctx->gemm_split;
-    ctx->gemm_split = 0;
+    const int keep = ctx->routes.gemm_split;
+    ctx->routes.gemm_split = 0;
     const int rc = pmd_gemm_rm(ctx, 0, 0, nr, i0 + nr, rows, 1.f, Mt + (long)i0 * ldt, ldt, GM, ldgm, 0.f, C + (long)i0 * ldc, ldc);
-    ctx->gemm_split = keep;
+    ctx->routes.gemm_split = keep;
     RUN(rc);
   }
-  // the pieces of both operands are three quarters of M and GM together (27 GB at BASELINE config 4): a scratch of that
-  // size goes back to the device before the eigensolver asks for its workspace
-  if (pieces) RUN(pmd_split_scratch_trim(ctx, (size_t)8 << 30));
   return PMD_OK;
 }
 
@@ -1572,13 +1447,8 @@ int pmd_gram_mtgm_impl(pmd_ctx* ctx, const float* M, int rows, int m, long ldm, 
 // reference's rank_prune and R > frames routes drive to 1e5 ... 1e7: in fp32 the signal singular values of such draws came
 // out 27 % off where NumPy's (double-precision LAPACK on fp32 data) are 2 % off (seeded fuzz, options 104 / 42).
 // Orders up to which the Cholesky step runs in double precision (rocSOLVER dpotrf + dtrtri on a widened copy, results
-// rounded).  PMD_CHOL_F64_MAX overrides.
-static int chol_f64_max() {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("PMD_CHOL_F64_MAX"); v = e ? atoi(e) : 512; }
-  return v;
-}
-#define CHOL_F64_MAX chol_f64_max()
+// rounded).  A constant: pmd_chol_inverse_workspace_bytes sizes the caller's buffer from it without a context.
+constexpr int CHOL_F64_MAX = 512;
 
 namespace {
 __global__ void chol_widen_kernel(const float* __restrict__ src, long lds_, double* __restrict__ dst, long ldd, int n) {
@@ -1625,7 +1495,7 @@ int pmd_chol_inverse_impl(pmd_ctx* ctx, float* C, int m, long ldc, int abs_last_
   if (ar.overflow) return pmd_fail(ctx, PMD_ERR_WORKSPACE, "pmd_chol_inverse", "workspace too small");
   *ok_host = 0;
   int hinfo = 0;
-  if (m <= CHOL_F64_MAX && m >= 1 && !getenv("PMD_CHOLESKY")) {
+  if (m <= CHOL_F64_MAX && m >= 1 && !ctx->routes.cholesky_rocsolver) {
     pmd_prof_scope prof__(ctx, "cholesky_f64");
     double* Cd = ar.take_n<double>((size_t)m * m);
     if (ar.overflow) return pmd_fail(ctx, PMD_ERR_WORKSPACE, "pmd_chol_inverse", "workspace too small");
@@ -1655,14 +1525,11 @@ int pmd_chol_inverse_impl(pmd_ctx* ctx, float* C, int m, long ldc, int abs_last_
     *ok_host = 1;
     return PMD_OK;
   }
-  {
-    const char* cmode = getenv("PMD_CHOLESKY");
-    if (cmode && !strcmp(cmode, "rocsolver") && !abs_last_pivot) {
-      pmd_prof_scope prof__(ctx, "rocsolver_spotrf");
-      PMD_BLAS(ctx, rocsolver_spotrf(ctx->blas, rocblas_fill_upper, m, C, (rocblas_int)ldc, info));
-    } else {
-      RUN(chol_lower_rm(ctx, m, C, ldc, info, chol_tmp, chol_linv, abs_last_pivot));
-    }
+  if (ctx->routes.cholesky_rocsolver && !abs_last_pivot) {
+    pmd_prof_scope prof__(ctx, "rocsolver_spotrf");
+    PMD_BLAS(ctx, rocsolver_spotrf(ctx->blas, rocblas_fill_upper, m, C, (rocblas_int)ldc, info));
+  } else {
+    RUN(chol_lower_rm(ctx, m, C, ldc, info, chol_tmp, chol_linv, abs_last_pivot));
   }
   PMD_HIP(ctx, hipMemcpyAsync(&hinfo, info, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   PMD_HIP(ctx, hipStreamSynchronize(ctx->stream));

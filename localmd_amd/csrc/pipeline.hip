@@ -202,10 +202,8 @@ int pmd_tiles_decompose_impl(pmd_ctx* ctx, const float* Xf, long ldx, long n_row
                                 ranks_out, sing_out, ws, stages);
   const long s64d = 64L * p.dpad, s64P = 64L * p.Ppad, s64b = 64L * p.ld_b, s64v = 64L * ldv;
   // PMD_TILE_WHITEN=eig restores the eigenvector form of the two pure orthonormalisation steps (A/B runs)
-  static int whiten_mode = -1;
-  if (whiten_mode < 0) { const char* e = getenv("PMD_TILE_WHITEN"); whiten_mode = (e && !strcmp(e, "eig")) ? 0 : 1; }
-  const bool whiten_chol = whiten_mode && stages == 7;   // the spatial_denoiser hook sees S = X V_b^T column by column
-  const bool whiten_chol_u0 = whiten_mode != 0;
+  const bool whiten_chol_u0 = !ctx->routes.tile_whiten_eig;
+  const bool whiten_chol = whiten_chol_u0 && stages == 7;   // the spatial_denoiser hook sees S = X V_b^T column by column
   // Time slices of the two contractions over all frames: four per tile give a few thousand tiles enough workgroups to fill
   // the chip; with many tiles (the 16 x 16-pixel regime: 16 129 / 65 025 tiles) one slice does, and the partial results
   // and their reduction pass (10 of 300 ms at 1024 x 1024 x 1000, b = 16) disappear.

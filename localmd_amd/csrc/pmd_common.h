@@ -29,6 +29,32 @@ struct pmd_prof_rec {
   hipEvent_t start, stop;
 };
 
+// Route switches: A/B comparators and library-routine fallbacks selected by PMD_* environment variables.  The table in
+// capi.hip is the list of them (one row per variable: field, default, accepted values).  They are read ONCE, when a
+// context is created, and are fixed for that context; a value outside a row's accepted set means the default.
+enum { PMD_SYEVD_AUTO = 0, PMD_SYEVD_F64, PMD_SYEVD_ROCSOLVER, PMD_SYEVD_OWN, PMD_SYEVD_TWOSTAGE };
+struct pmd_routes {
+  int syevd;                         // PMD_SYEVD: one of PMD_SYEVD_* (sytrd.hip)
+  int apply_q_rocsolver;             // PMD_APPLY_Q=rocsolver: sormtr in place of the blocked back-transformation
+  int syr2k_rocblas;                 // PMD_SYR2K=rocblas: ssyr2k in place of the rank-2k kernel of the tridiagonalisation
+  int cholesky_rocsolver;            // PMD_CHOLESKY=rocsolver: spotrf in place of the blocked factorisation (and no fp64 form of small orders)
+  int chol_chain_rocblas;            // PMD_CHOL_CHAIN=rocblas: strtri + sgemm per panel in place of chol_panel_kernel
+  int sytrd_advance_old;             // PMD_SYTRD_ADVANCE=old: 64 positions x 4 parts per workgroup
+  int gemm_split;                    // PMD_GEMM_SPLIT: 1 (default) = large fp32 products as fp16-piece products (gemm_f16x2.hip); 0: rocBLAS sgemm only
+  double gemm_split_min_gflop;       // PMD_GEMM_SPLIT_MIN_GFLOP: ... for products of at least this many GFLOP
+  int gemm_split_min_dim;            // PMD_GEMM_SPLIT_MIN_DIM: ... and no dimension below this
+  int gemm_splitk;                   // PMD_GEMM_SPLITK: 1 (default) = strided-batched split-K sgemm for few output tiles and a long k
+  int gemm_kchunk;                   // PMD_GEMM_KCHUNK: length of one fp32 accumulation chain; -1 (default) = by k, 0 = whole k
+  int f16x2_mtgm;                    // PMD_F16X2_MTGM: 6 (default) = M^T G M as concatenated fp16-piece products; 0: sgemm
+  int gram_apply_mfma;               // PMD_GRAM_APPLY_MFMA: 1 (default); 0: the scalar gram_apply_kernel
+  int gram_mfma;                     // PMD_GRAM_MFMA: 1 (default); 0: the scalar tile_gram_kernel
+  int rowmix_mfma;                   // PMD_ROWMIX_MFMA: -1 (default) = by shape; 0: scalar kernels; 16 / 64: that many positions per wave
+  int atx_dma;                       // PMD_ATX_DMA: 1 (default) = LDS-DMA staged tile_atx for d in (256, 400]; 0: the plain variant
+  int tile_whiten_eig;               // PMD_TILE_WHITEN=eig: eigenvector form of the two pure orthonormalisation steps
+  int wide_eig_syevd;                // PMD_WIDE_EIG=syevd: rocSOLVER's batched divide-and-conquer solver in place of dsyevj
+  int small_eig_rocsolver;           // PMD_SMALL_EIG=rocsolver: the tile eigenproblems through the wide (rocSOLVER) path
+};
+
 struct pmd_ctx {
   int device;
   hipStream_t stream;
@@ -42,9 +68,7 @@ struct pmd_ctx {
   size_t scratch_bytes;
   void* scratch2;                    // library-owned device scratch of the fp64 eigenvector refinement (sytrd.hip)
   size_t scratch2_bytes;
-  int gemm_split;                    // 1 (default): large fp32 products as three fp16-piece products (gemm_f16x2.hip); 0: rocBLAS sgemm only
-  double gemm_split_min_flop;        // ... for products with at least this many flops
-  int gemm_split_min_dim;            // ... and no dimension below this
+  pmd_routes routes;                 // the PMD_* route switches, as the environment had them when the context was created
   void* f16x2;                       // state of gemm_f16x2.hip (hipBLASLt handle, plans), created on first use
   void* split_ws;                    // library-owned device scratch of the split products (fp16 pieces, split-K partial sums)
   size_t split_ws_bytes;

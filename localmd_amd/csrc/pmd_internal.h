@@ -122,7 +122,7 @@ int pmd_background_rsvd_impl(pmd_ctx* ctx, const float* xs, long D, int n, long 
 // global.hip
 int pmd_gemm_rm(pmd_ctx* ctx, int transA, int transB, int m, int n, int k, float alpha, const float* A, long lda,
                 const float* B, long ldb, float beta, float* C, long ldc);
-int pmd_gemm_k_chunk(int k);
+int pmd_gemm_k_chunk(const pmd_ctx* ctx, int k);
 // gemm_f16x2.hip: fp32 products from two fp16 pieces per operand (X 2^-e = h1 + 2^-11 h2)
 struct pmd_f16x2_op {
   const _Float16* h1;
@@ -151,6 +151,7 @@ int pmd_split_scratch_trim(pmd_ctx* ctx, size_t keep_bytes);
 void pmd_f16x2_destroy(pmd_ctx* ctx);
 bool pmd_is_host_pointer(const void* p);
 int pmd_syevd(pmd_ctx* ctx, int n, float* A, long lda, float* w, float* work, int* info);
+int pmd_ctx_scratch2(pmd_ctx* ctx, size_t bytes, void** out);   // sytrd.hip: grows ctx->scratch2 to at least `bytes`
 size_t pmd_sy2sb_workspace_bytes_impl(int n);
 int pmd_sy2sb_impl(pmd_ctx* ctx, int n, float* A, long lda, float* tau1, int* flag_host, void* ws, size_t ws_bytes);
 int pmd_apply_q_off_impl(pmd_ctx* ctx, int n, const float* A, long lda, const float* tau, float* Z, long ldz, void* ws,

@@ -1,7 +1,7 @@
 // Batched small dense factorizations, one workgroup per tile, fp64 in LDS.
 //   small_qr   : reduced Householder QR (LAPACK dgeqr2 + dorg2r conventions), replaces
 //                jnp.linalg.qr at decomposition.py:64 / pmd_loader.py:58
-//   small_eig  : cyclic parallel Jacobi eigensolver of a symmetric n x n Gram matrix (n <= 64);
+//   small_eig  : tridiagonal QL eigensolver of a symmetric n x n Gram matrix (n <= 64), one wave per problem;
 //                with the streaming Gram/rowmix kernels it replaces the jnp.linalg.svd calls at
 //                decomposition.py:66, :301, :315-317, :319 (SVD of M as eigh(M M^T))
 //   roughness statistics and the keep/discard scan (evaluation.py:84-126, :133-222)
@@ -133,151 +133,17 @@ int pmd_launch_small_qr(pmd_ctx* ctx, const float* Yt, long y_tile_stride, int y
   return PMD_OK;
 }
 
-// ---------------------------------------------------------------- Jacobi eigensolver ------
-// G: [tile][slices][64][64] doubles (summed on load; only the leading n x n block is used).
+// ---------------------------------------------------------------- tridiagonal QL eigensolver, one wave per problem ----
+// G: [tile][slices][64][64] doubles (summed over the slices and symmetrised on load; only the leading n x n block is used).
 // Nout[tile][c'][c] = eigenvector c (descending eigenvalue), component c'.
 //   mode 0: plain eigenvectors
 //   mode 1: column c scaled by 1/sqrt(lambda_c); columns with lambda_c <= tol*lambda_max zeroed
 // lam_out[tile][c] = eigenvalue c (descending); entries >= n are zero.
-#define EIG_LD 65
-// Threads per problem (PMD_EIG_THREADS=256|512|1024, default 1024).  A problem holds 66.5 KB of LDS (A and V in fp64), so
-// two share a CU whatever the workgroup size; one rotation step is ~18 000 fp64 FMAs (A <- J^T A J and V <- V J at
-// n = 60) between two barriers.  Measured (round 2, 16 129 tiles x 4 launches): 83 / 96 / 130 ms per step with 1024 /
-// 512 / 256 threads - the step is bound by its chain of dependent LDS round trips, which more threads shorten, not by
-// the fp64 rate.
-template <int EIG_THREADS>
-__global__ __launch_bounds__(EIG_THREADS) void small_eig_kernel(const double* __restrict__ G, long g_tile_stride, int slices,
-                                                        int n, int mode, double tol, double* __restrict__ Nout,
-                                                        double* __restrict__ lam_out) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  double* A = reinterpret_cast<double*>(smem);  // [64][EIG_LD]
-  double* V = A + 64 * EIG_LD;                  // [64][EIG_LD]
-  double* cs = V + 64 * EIG_LD;                 // [32][2]
-  int* pq = reinterpret_cast<int*>(cs + 64);    // [32][2]
-  int* flag = pq + 64;                          // [2]
-  int* order = flag + 2;                        // [64]
-  const int tid = threadIdx.x;
-  const double* g = G + (long)blockIdx.x * g_tile_stride;
-  for (int i = tid; i < 64 * 64; i += EIG_THREADS) {
-    const int r = i >> 6, c = i & 63;
-    double s = 0.0;
-    if (r < n && c < n)
-      for (int k = 0; k < slices; ++k) s += g[(long)k * 4096 + r * 64 + c] + g[(long)k * 4096 + c * 64 + r];
-    A[r * EIG_LD + c] = 0.5 * s;
-    V[r * EIG_LD + c] = (r == c) ? 1.0 : 0.0;
-  }
-  __syncthreads();
-  const int npad = (n + 1) & ~1;
-  const int half = npad / 2;
-  for (int sweep = 0; sweep < 40; ++sweep) {
-    if (tid == 0) flag[0] = 0;
-    __syncthreads();
-    for (int m = 0; m < npad - 1; ++m) {
-      if (tid < half) {
-        // round-robin pairing: fix player npad-1, rotate the rest
-        int p, q;
-        if (tid == 0) { p = npad - 1; q = m; }
-        else { p = (m + tid) % (npad - 1); q = (m - tid + (npad - 1)) % (npad - 1); }
-        if (p > q) { const int t = p; p = q; q = t; }
-        double c = 1.0, s = 0.0;
-        if (q < n) {
-          const double app = A[p * EIG_LD + p], aqq = A[q * EIG_LD + q], apq = A[p * EIG_LD + q];
-          const double prod = fabs(app * aqq), apq2 = apq * apq;
-          if (apq2 > 1e-34 * prod && fabs(apq) > 1e-300) {
-            // This chain sits between two barriers of every step, so it is kept short: t = tan(theta) from fp32
-            // arithmetic on exponent-normalised operands (an error of 1e-7 in t leaves 1e-7 apq behind instead of
-            // zero - the next sweep takes it; convergence stays quadratic), then c = 1/sqrt(1 + t^2), s = t c in
-            // fp64, which is what keeps the accumulated rotations orthogonal to fp64 accuracy.
-            const double num = aqq - app, den = 2.0 * apq;
-            const int ex = max(__builtin_amdgcn_frexp_exp(num), __builtin_amdgcn_frexp_exp(den));
-            const float th = (float)ldexp(num, -ex) / (float)ldexp(den, -ex);
-            const float ath = fabsf(th);
-            const float t32 = (ath > 1e9f) ? 0.5f / th : copysignf(1.0f, th) / (ath + sqrtf(1.0f + th * th));
-            const double t = (double)t32;
-            c = rsqrt(1.0 + t * t);
-            s = t * c;
-            // another sweep is needed only if this one still met an off-diagonal above 1e-6 sqrt(app aqq): the rotations of
-            // this sweep take such entries to ~1e-12 (quadratic convergence), fp64 grade for vectors that leave as fp32.
-            // (1e-24 here ran one more full sweep of 59 two-barrier steps to verify what the bound already says: 12 % of the
-            // kernel on the many-tile workloads.)
-            if (apq2 > 1e-12 * prod) flag[0] = 1;
-          }
-        }
-        cs[2 * tid] = c; cs[2 * tid + 1] = s;
-        pq[2 * tid] = p; pq[2 * tid + 1] = q;
-      }
-      __syncthreads();
-      // A <- J^T A J in one pass: the 2x2 block (pair k rows) x (pair k' columns) gets both rotations;
-      // blocks are disjoint, so one barrier per step suffices.  V <- V J rides in the same phase.
-      for (int i = tid; i < half * half; i += EIG_THREADS) {
-        const int k = i / half, kp = i - k * half;
-        const double c = cs[2 * k], s = cs[2 * k + 1], c2 = cs[2 * kp], s2 = cs[2 * kp + 1];
-        if (s != 0.0 || s2 != 0.0) {
-          const int p = pq[2 * k], q = pq[2 * k + 1], p2 = pq[2 * kp], q2 = pq[2 * kp + 1];
-          const double a11 = A[p * EIG_LD + p2], a12 = A[p * EIG_LD + q2];
-          const double a21 = A[q * EIG_LD + p2], a22 = A[q * EIG_LD + q2];
-          const double r11 = c * a11 - s * a21, r12 = c * a12 - s * a22;   // rows rotated
-          const double r21 = s * a11 + c * a21, r22 = s * a12 + c * a22;
-          A[p * EIG_LD + p2] = c2 * r11 - s2 * r12;
-          A[p * EIG_LD + q2] = s2 * r11 + c2 * r12;
-          A[q * EIG_LD + p2] = c2 * r21 - s2 * r22;
-          A[q * EIG_LD + q2] = s2 * r21 + c2 * r22;
-        }
-      }
-      for (int i = tid; i < half * n; i += EIG_THREADS) {
-        const int k = i / n, j = i - k * n;
-        const double c = cs[2 * k], s = cs[2 * k + 1];
-        if (s != 0.0) {
-          const int p = pq[2 * k], q = pq[2 * k + 1];
-          const double vp = V[j * EIG_LD + p], vq = V[j * EIG_LD + q];
-          V[j * EIG_LD + p] = c * vp - s * vq;
-          V[j * EIG_LD + q] = s * vp + c * vq;
-        }
-      }
-      __syncthreads();
-    }
-    if (flag[0] == 0) break;
-    __syncthreads();
-  }
-  // rank eigenvalues (descending, ties by index)
-  if (tid < 64) {
-    int rank = 0;
-    if (tid < n) {
-      const double li = A[tid * EIG_LD + tid];
-      for (int j = 0; j < n; ++j) {
-        const double lj = A[j * EIG_LD + j];
-        rank += (lj > li) || (lj == li && j < tid);
-      }
-      order[rank] = tid;
-    }
-  }
-  __syncthreads();
-  double lmax = (n > 0) ? A[order[0] * EIG_LD + order[0]] : 0.0;
-  double* no = Nout + (long)blockIdx.x * 4096;
-  for (int i = tid; i < 4096; i += EIG_THREADS) {
-    const int r = i >> 6, c = i & 63;
-    double v = 0.0;
-    if (r < n && c < n) {
-      const int src = order[c];
-      v = V[r * EIG_LD + src];
-      if (mode == 1) {
-        const double lam = A[src * EIG_LD + src];
-        v = (lam > tol * lmax && lam > 0.0) ? v / sqrt(lam) : 0.0;
-      }
-    }
-    no[i] = v;
-  }
-  if (tid < 64) lam_out[(long)blockIdx.x * 64 + tid] = (tid < n) ? A[order[tid] * EIG_LD + order[tid]] : 0.0;
-}
-
-// ---------------------------------------------------------------- tridiagonal QL eigensolver, one wave per problem ----
-// The same contract as small_eig_kernel (G summed over its slices and symmetrised on load; Nout / lam_out in descending
-// order; mode 1 scaling and null rule), by Householder tridiagonalisation (LAPACK dsytd2 'L' conventions), in-place
-// formation of Q (dorg2r on the shifted array, as dorgtr does) and the implicit QL iteration with the rotations
-// accumulated into Q (EISPACK tql2) - all in ONE wave on one n x (n + 1) fp64 array in LDS (29 KB at n = 60: five problems
-// share a CU; the Jacobi kernel above holds A and V, 66 KB, two per CU, and spends two 1024-thread barriers on every one
-// of its ~470 rotation steps).  The tridiagonal matrix lives in REGISTERS: lane i holds d[i], e[i], tau[i]; a scalar is
-// fetched with v_readlane and stored by a predicated move, so the dependent chain of a rotation is ~250 cycles of fp64
+// By Householder tridiagonalisation (LAPACK dsytd2 'L' conventions), in-place formation of Q (dorg2r on the shifted array,
+// as dorgtr does) and the implicit QL iteration with the rotations accumulated into Q (EISPACK tql2) - all in ONE wave on
+// one n x (n + 1) fp64 array in LDS (29 KB at n = 60: five problems share a CU; the parallel cyclic Jacobi kernel this one
+// replaced held A and V, 66 KB, two per CU, and spent two 1024-thread barriers on every one of its ~470 rotation steps:
+// 49 against 25 ms).  The tridiagonal matrix lives in REGISTERS: lane i holds d[i], e[i], tau[i]; a scalar is fetched with v_readlane and stored by a predicated move, so the dependent chain of a rotation is ~250 cycles of fp64
 // arithmetic with no memory access in it.  The accumulated rotations touch a lane's own row of Q only (no cross-lane
 // hazard in the whole QL phase), and the column two rotations share stays in a register.  Cross-lane traffic through LDS
 // exists only in the two Householder phases (reflector broadcast), fenced by single-wave barriers.
@@ -479,54 +345,19 @@ int pmd_launch_small_eig(pmd_ctx* ctx, const double* G, int slices, int n, int m
   pmd_prof_scope prof__(ctx, "small_eig");
   if (n_tiles <= 0) return PMD_OK;
   if (n > 64 || n < 1) return pmd_fail(ctx, PMD_ERR_UNSUPPORTED, "small_eig", "n must be in [1, 64]");
-  {
-    // A/B: PMD_SMALL_EIG=rocsolver routes the batch through rocSOLVER's strided-batched dsyevd (wide.hip, rp = 64)
-    static int lib_mode = -1;
-    if (lib_mode < 0) { const char* e = getenv("PMD_SMALL_EIG"); lib_mode = (e && !strcmp(e, "rocsolver")) ? 1 : 0; }
-    if (lib_mode) {
-      const size_t need = pmd_wide_eig_workspace_bytes(64, n_tiles);
-      if (ctx->scratch2_bytes < need) {
-        PMD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->scratch2) (void)hipFree(ctx->scratch2);
-        ctx->scratch2 = nullptr;
-        ctx->scratch2_bytes = 0;
-        PMD_HIP(ctx, hipMalloc(&ctx->scratch2, need));
-        ctx->scratch2_bytes = need;
-      }
-      return pmd_launch_wide_eig(ctx, G, slices, 64, n, mode, tol, Nout, lam_out, n_tiles, ctx->scratch2, ctx->scratch2_bytes);
-    }
+  if (ctx->routes.small_eig_rocsolver) {
+    // A/B: the batch through rocSOLVER's strided-batched solver (wide.hip, rp = 64)
+    const size_t need = pmd_wide_eig_workspace_bytes(64, n_tiles);
+    void* ws = nullptr;
+    int rc = pmd_ctx_scratch2(ctx, need, &ws);
+    if (rc != PMD_OK) return rc;
+    return pmd_launch_wide_eig(ctx, G, slices, 64, n, mode, tol, Nout, lam_out, n_tiles, ws, ctx->scratch2_bytes);
   }
-  {
-    // default: the one-wave QL kernel; PMD_SMALL_EIG=jacobi restores the parallel Jacobi kernel (A/B runs)
-    static int ql_mode = -1;
-    if (ql_mode < 0) { const char* e = getenv("PMD_SMALL_EIG"); ql_mode = (e && !strcmp(e, "jacobi")) ? 0 : 1; }
-    if (ql_mode) {
-      const size_t lds = ((size_t)n * (n + 1) + 2 * 64) * sizeof(double) + 64 * sizeof(int) + 64;
-      PMD_HIP(ctx, hipFuncSetAttribute((const void*)small_eig_ql_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL(small_eig_ql_kernel, dim3(n_tiles), dim3(64), lds, ctx->stream, G, (long)slices * 4096, slices, n, mode, tol,
-                         Nout, lam_out);
-      PMD_LAUNCH_CHECK(ctx, "small_eig_ql_kernel");
-      return PMD_OK;
-    }
-  }
-  const size_t bytes = (size_t)2 * 64 * EIG_LD * sizeof(double) + 64 * sizeof(double) + (64 + 2 + 64) * sizeof(int) + 64;
-  static int threads = 0;
-  if (!threads) {
-    const char* e = getenv("PMD_EIG_THREADS");
-    threads = e ? atoi(e) : 1024;
-    if (threads != 256 && threads != 512 && threads != 1024) threads = 1024;
-  }
-#define PMD_EIG_LAUNCH(TH)                                                                                                      \
-  do {                                                                                                                          \
-    PMD_HIP(ctx, hipFuncSetAttribute((const void*)small_eig_kernel<TH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes)); \
-    hipLaunchKernelGGL(small_eig_kernel<TH>, dim3(n_tiles), dim3(TH), bytes, ctx->stream, G, (long)slices * 4096, slices, n,    \
-                       mode, tol, Nout, lam_out);                                                                               \
-  } while (0)
-  if (threads == 1024) PMD_EIG_LAUNCH(1024);
-  else if (threads == 512) PMD_EIG_LAUNCH(512);
-  else PMD_EIG_LAUNCH(256);  // 83 / 96 / 130 ms per step with 1024 / 512 / 256 threads on the 16 129-tile workload: latency, not fp64 rate, bounds a step
-#undef PMD_EIG_LAUNCH
-  PMD_LAUNCH_CHECK(ctx, "small_eig_kernel");
+  const size_t lds = ((size_t)n * (n + 1) + 2 * 64) * sizeof(double) + 64 * sizeof(int) + 64;
+  PMD_HIP(ctx, hipFuncSetAttribute((const void*)small_eig_ql_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(small_eig_ql_kernel, dim3(n_tiles), dim3(64), lds, ctx->stream, G, (long)slices * 4096, slices, n, mode, tol,
+                     Nout, lam_out);
+  PMD_LAUNCH_CHECK(ctx, "small_eig_ql_kernel");
   return PMD_OK;
 }
 
@@ -535,7 +366,7 @@ int pmd_launch_small_eig(pmd_ctx* ctx, const double* G, int slices, int n, int m
 // (upper R), Nout[tile][c'][c] = (R^{-1})[c'][c], so that tile_rowmix turns rows with Gram matrix G into orthonormal
 // rows (new row c = sum_c' N[c'][c] old row c').  A pivot <= tol * max diagonal marks a direction that depends on the
 // earlier ones: its column is zero (the counterpart of small_eig's lambda <= tol * lambda_max).  One wave per problem,
-// ~50 us against ~0.7 ms for the Jacobi solver: two of the four factorisations of single_block_md
+// ~50 us against ~0.7 ms for the Jacobi eigensolver of that time: two of the four factorisations of single_block_md
 // (decomposition.py:301, :315-317) only feed spans - span(S) does not depend on the basis of the row space of V_ds, and
 // U = U0 Wl does not depend on the basis U0 of span(S) - and take this path when no denoiser hook reads the vectors.
 __global__ __launch_bounds__(64) void small_chol_kernel(const double* __restrict__ G, long g_tile_stride, int slices, int n,

@@ -35,9 +35,8 @@ namespace {
 
 constexpr int NB = 64;      // panel width
 constexpr int BR = 64;      // rows of one symv tile
-constexpr int CW = 1024;    // positions of one symv tile: 4 x 256 (2 row halves of 32 rows) or, for the
-                            // smaller trailing blocks, 512 = 2 x 256 (4 row quarters of 16 rows: half the registers,
-                            // two workgroups per CU, twice the workgroups)
+constexpr int CW = 512;     // positions of one symv tile: 2 x 256 (4 row quarters of 16 rows, two workgroups per CU);
+                            // measured at n = 10^4: 334 ms (1024 = 4 x 256, 2 row halves of 32 rows), 303 ms (512), 320 ms (256)
 constexpr int DCH = 256;    // positions per dot-product workgroup
 
 struct sytrd_bufs {
@@ -50,7 +49,7 @@ struct sytrd_bufs {
   float* DP;    // [dot chunk][2][NB]: partial W_k^T v, V_k^T v
   double* NP;   // per advance workgroup: partial sum of squares
   float* scal;  // beta, tau, scale of the current reflector
-  int cw;       // tile width (positions) of the symv launch whose partials RP / CP / SP currently hold
+  int cw;       // tile width (positions) of the symv launches: CW
 };
 
 __device__ __forceinline__ int tile_r0(int cs, int b) { return (cs + b * BR) & ~3; }
@@ -699,15 +698,12 @@ __global__ __launch_bounds__(512, CWT == 1024 ? 2 : 4) void sytrd_symv_kernel(co
 // Panel update of the trailing block (slatrd's A22 -= V W^T + W V^T) on the triangle that is read:
 //   T[c][r] -= sum_k V_k[c] W_k[r] + W_k[c] V_k[r],   ts <= c <= r < n,  k < nbc <= 64.
 // One workgroup = one 64 x 64 tile (I <= J); wave w owns rows 16 w .. 16 w + 15 of it in four 16 x 16 fp32 MFMA
-// accumulators.  The operands are MFMA-fragment-shaped dword loads straight from the two 64-row panels (L2
-// resident, 16 consecutive floats per lane group); rocBLAS' ssyr2k spends several launches per call on this.
+// accumulators; rocBLAS' ssyr2k spends several launches per call on this.  The panel operands are staged through LDS:
+// the workgroup copies the 64 x 64 blocks of V and W it needs (row side and column side, two halves of 32 panel rows,
+// coalesced 256-byte rows) into LDS once and every wave reads its MFMA fragments from there (fragments loaded straight
+// from the panels cost ten 4-byte loads per eight MFMAs, the column side fetched by all four waves: 2.5 x the L2 traffic).
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// The same update with the panel operands staged through LDS (round 3).  In the form below every lane fetches its MFMA
-// operands one float at a time (ten 4-byte loads per eight MFMAs) and the four waves of a workgroup fetch the same column-side
-// fragments four times.  Here the workgroup copies the 64 x 64 blocks of V and W it needs (row side and column side, two
-// halves of 32 panel rows, coalesced 256-byte rows) into LDS once and every wave reads its fragments from there: 2.5 x less
-// traffic through L2, a third of the load instructions.  Same MFMAs in the same order: bit-identical results.
 __global__ __launch_bounds__(256) void sytrd_rank2k_lds_kernel(float* __restrict__ A, long lda, int n, int ts, int j0, int nbc,
                                                                const float* __restrict__ W, long ldw) {
   constexpr int LS = 68;
@@ -753,48 +749,6 @@ __global__ __launch_bounds__(256) void sytrd_rank2k_lds_kernel(float* __restrict
     }
   }
   if (c0 >= n) return;
-#pragma unroll
-  for (int jn = 0; jn < 4; ++jn) {
-    const int col = r0 + 16 * jn + n16;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int row = c0 + 4 * kk + i;
-      if (row < n && col < n && col >= row) A[(long)row * lda + col] -= acc[jn][i];
-    }
-  }
-}
-
-__global__ __launch_bounds__(256) void sytrd_rank2k_kernel(float* __restrict__ A, long lda, int n, int ts, int j0, int nbc,
-                                                           const float* __restrict__ W, long ldw) {
-  const int I = blockIdx.y, J = blockIdx.x;
-  if (J < I) return;
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // (uniform, and known to be)
-  const int n16 = lane & 15, kk = lane >> 4;
-  const int c0 = ts + 64 * I + 16 * wave, r0 = ts + 64 * J;
-  if (c0 >= n) return;
-  const float* V = A + (long)j0 * lda;
-  const int c = min(c0 + n16, n - 1);
-  int r[4];
-#pragma unroll
-  for (int jn = 0; jn < 4; ++jn) r[jn] = min(r0 + 16 * jn + n16, n - 1);
-  f32x4 acc[4];
-#pragma unroll
-  for (int jn = 0; jn < 4; ++jn) acc[jn] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int k0 = 0; k0 < 64; k0 += 4) {
-    const int k = k0 + kk;
-    const bool in = k < nbc;
-    const long kc = in ? k : 0;   // unconditional loads on a valid row, masked below
-    float a1 = V[kc * lda + c], a2 = W[kc * ldw + c];
-    a1 = in ? a1 : 0.f;
-    a2 = in ? a2 : 0.f;
-#pragma unroll
-    for (int jn = 0; jn < 4; ++jn) {
-      const float b1 = W[kc * ldw + r[jn]], b2 = V[kc * lda + r[jn]];
-      acc[jn] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, acc[jn], 0, 0, 0);
-      acc[jn] = __builtin_amdgcn_mfma_f32_16x16x4f32(a2, b2, acc[jn], 0, 0, 0);
-    }
-  }
 #pragma unroll
   for (int jn = 0; jn < 4; ++jn) {
     const int col = r0 + 16 * jn + n16;
@@ -927,15 +881,9 @@ int pmd_sytrd_impl(pmd_ctx* ctx, int n, float* A, long lda, float* d, float* e, 
   if (ar.overflow) return pmd_fail(ctx, PMD_ERR_WORKSPACE, "pmd_sytrd", "workspace too small");
   hipStream_t st = ctx->stream;
 
-  const char* s2k = getenv("PMD_SYR2K");
-  const bool use_rocblas_syr2k = s2k && !strcmp(s2k, "rocblas");
-  const char* cwf = getenv("PMD_SYMV_CW");
-  // symv tile width: 512 (two workgroups per CU); measured at n = 10^4: 334 ms (1024), 303 ms (512), 320 ms (256)
-  int cw_fixed = cwf ? atoi(cwf) : 512;
-  if (cw_fixed != 256 && cw_fixed != 512 && cw_fixed != 1024) cw_fixed = 512;
   B.cw = CW;
-  const char* advf = getenv("PMD_SYTRD_ADVANCE");  // "old": 64 positions x 4 parts per workgroup
-  const bool adv_old = advf && !strcmp(advf, "old");
+  const bool use_rocblas_syr2k = ctx->routes.syr2k_rocblas;
+  const bool adv_old = ctx->routes.sytrd_advance_old;   // 64 positions x 4 parts per workgroup
   const float one = 1.f, minus1 = -1.f;
   int nsp = 0;
   for (int j0 = 0; j0 < n - 1; j0 += NB) {
@@ -955,8 +903,7 @@ int pmd_sytrd_impl(pmd_ctx* ctx, int n, float* A, long lda, float* d, float* e, 
       const int nbk = (n - cs + BR - 1) / BR;
       const int npairs = (nbk + 1) / 2;
       auto r0 = [&](int b) { return (cs + b * BR) & ~3; };
-      const int cw = cw_fixed;
-      auto nq = [&](int b) { return (n - r0(b) + cw - 1) / cw; };
+      auto nq = [&](int b) { return (n - r0(b) + CW - 1) / CW; };
       int nqx = 1;
       for (int p = 0; p < npairs; ++p) nqx = std::max(nqx, nq(p) + ((nbk - 1 - p != p) ? nq(nbk - 1 - p) : 0));
       const int ndch = (i > 0) ? (n - cs + DCH - 1) / DCH : 0;
@@ -964,13 +911,7 @@ int pmd_sytrd_impl(pmd_ctx* ctx, int n, float* A, long lda, float* d, float* e, 
       {
         // with profiling on, every 64th column's product is timed on its own (bench.py: roofline of this kernel)
         pmd_prof_scope sample__((ctx->profile && (j & 63) == 32) ? ctx : nullptr, "sytrd_symv_sample");
-        if (cw == 256)
-          hipLaunchKernelGGL(sytrd_symv_kernel<256>, dim3(nqx, npairs + drows), dim3(512), 0, st, A, lda, n, j, j0, B, ga, npairs, nbk, e, tau);
-        else if (cw == 512)
-          hipLaunchKernelGGL(sytrd_symv_kernel<512>, dim3(nqx, npairs + drows), dim3(512), 0, st, A, lda, n, j, j0, B, ga, npairs, nbk, e, tau);
-        else
-          hipLaunchKernelGGL(sytrd_symv_kernel<1024>, dim3(nqx, npairs + drows), dim3(512), 0, st, A, lda, n, j, j0, B, ga, npairs, nbk, e, tau);
-        B.cw = cw;  // the advance launches that follow read these partials
+        hipLaunchKernelGGL(sytrd_symv_kernel<CW>, dim3(nqx, npairs + drows), dim3(512), 0, st, A, lda, n, j, j0, B, ga, npairs, nbk, e, tau);
       }
       nsp = nqx * npairs;
     }
@@ -987,11 +928,8 @@ int pmd_sytrd_impl(pmd_ctx* ctx, int n, float* A, long lda, float* d, float* e, 
                                    A + (long)ts * lda + ts, (rocblas_int)lda));
     } else {
       const int nt = (n - ts + 63) / 64;
-      static int r2k_lds = -1;   // PMD_RANK2K=direct: operands straight from the panels (the form of rounds 1-2)
-      if (r2k_lds < 0) { const char* e = getenv("PMD_RANK2K"); r2k_lds = (e && !strcmp(e, "direct")) ? 0 : 1; }
-      if (r2k_lds) hipLaunchKernelGGL(sytrd_rank2k_lds_kernel, dim3(nt, nt), dim3(256), 0, st, A, lda, n, ts, j0, nbc, B.W, B.ldw);
-      else hipLaunchKernelGGL(sytrd_rank2k_kernel, dim3(nt, nt), dim3(256), 0, st, A, lda, n, ts, j0, nbc, B.W, B.ldw);
-      PMD_LAUNCH_CHECK(ctx, "sytrd_rank2k_kernel");
+      hipLaunchKernelGGL(sytrd_rank2k_lds_kernel, dim3(nt, nt), dim3(256), 0, st, A, lda, n, ts, j0, nbc, B.W, B.ldw);
+      PMD_LAUNCH_CHECK(ctx, "sytrd_rank2k_lds_kernel");
     }
   }
   hipLaunchKernelGGL((sytrd_advance_kernel<false, false>), dim3(1), dim3(320), 0, st, A, lda, n, n - 1, n - 1, B, 0, d);
@@ -1129,9 +1067,12 @@ static int syevd_f64(pmd_ctx* ctx, int n, float* A, long lda, float* w, int* inf
 //     X <- X + X E
 // converges quadratically for the pairs outside clusters (delta = 1e-5 max |lambda|: what fp32 cannot separate stays the
 // fp32 solver's choice, orthonormalised).  7 n^3 fp64 flops per step on the fp64 matrix cores: 1.5 ms per step at
-// n = 2000, 12 ms at 4096; applied between PMD_SYEVD_F64_MAX (512; below it the whole problem runs in double) and
-// PMD_SYEVD_REFINE_MAX (4096; beyond it the cost reaches the solver's own).  PMD_SYEVD_REFINE_STEPS (2; 0 = off).
+// n = 2000, 12 ms at 4096; applied between SYEVD_F64_MAX (up to it the whole problem runs in double) and
+// SYEVD_REFINE_MAX (beyond it the cost reaches the solver's own).
 // ---------------------------------------------------------------------------------------------------------------
+constexpr int SYEVD_F64_MAX = 512;
+constexpr int SYEVD_REFINE_MAX = 4096;
+constexpr int SYEVD_REFINE_STEPS = 2;
 namespace {
 __global__ void refine_lambda_kernel(const double* __restrict__ S, const double* __restrict__ G, int n, double* __restrict__ lam) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1156,7 +1097,7 @@ __global__ void narrow_vec_kernel(const double* __restrict__ src, float* __restr
 }
 }  // namespace
 
-static int ctx_scratch2(pmd_ctx* ctx, size_t bytes, void** out) {
+int pmd_ctx_scratch2(pmd_ctx* ctx, size_t bytes, void** out) {
   if (ctx->scratch2_bytes < bytes) {
     PMD_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (ctx->scratch2) (void)hipFree(ctx->scratch2);
@@ -1169,18 +1110,7 @@ static int ctx_scratch2(pmd_ctx* ctx, size_t bytes, void** out) {
   return PMD_OK;
 }
 
-static int refine_steps_for(int n) {
-  static int f64_max = -1, ref_max = -1, steps = -1;
-  if (f64_max < 0) {
-    const char* e0 = getenv("PMD_SYEVD_F64_MAX");
-    const char* e1 = getenv("PMD_SYEVD_REFINE_MAX");
-    const char* e2 = getenv("PMD_SYEVD_REFINE_STEPS");
-    f64_max = e0 ? atoi(e0) : 512;
-    ref_max = e1 ? atoi(e1) : 4096;
-    steps = e2 ? atoi(e2) : 2;
-  }
-  return (n > f64_max && n <= ref_max && steps > 0) ? steps : 0;
-}
+static int refine_steps_for(int n) { return (n > SYEVD_F64_MAX && n <= SYEVD_REFINE_MAX) ? SYEVD_REFINE_STEPS : 0; }
 
 // Ad: widened copy of the input matrix (column-major lower triangle valid), taken BEFORE the fp32 solver overwrote A;
 // A (memory row j = eigenvector j) and w are refined in place.  ws: 5 n^2 + n doubles behind Ad.
@@ -1218,11 +1148,10 @@ static int pmd_syevd_f32(pmd_ctx* ctx, int n, float* A, long lda, float* w, floa
 // Symmetric eigendecomposition, ascending eigenvalues; on exit memory row j of A is eigenvector j.
 // Only the row-major upper triangle of A (= column-major lower) is read.  work: n floats, info: device int.
 int pmd_syevd(pmd_ctx* ctx, int n, float* A, long lda, float* w, float* work, int* info) {
-  const char* mode0 = getenv("PMD_SYEVD");
-  const int steps = (!mode0 || strcmp(mode0, "f64")) ? refine_steps_for(n) : 0;
+  const int steps = ctx->routes.syevd != PMD_SYEVD_F64 ? refine_steps_for(n) : 0;
   if (steps == 0) return pmd_syevd_f32(ctx, n, A, lda, w, work, info);
   void* s2 = nullptr;
-  int rc0 = ctx_scratch2(ctx, (6 * (size_t)n * n + (size_t)n) * sizeof(double) + 4096, &s2);
+  int rc0 = pmd_ctx_scratch2(ctx, (6 * (size_t)n * n + (size_t)n) * sizeof(double) + 4096, &s2);
   if (rc0 != PMD_OK) return rc0;
   double* Ad = static_cast<double*>(s2);
   hipLaunchKernelGGL(widen_kernel, dim3((n + 255) / 256, n), dim3(256), 0, ctx->stream, A, lda, Ad, (long)n, n);
@@ -1233,21 +1162,17 @@ int pmd_syevd(pmd_ctx* ctx, int n, float* A, long lda, float* w, float* work, in
 }
 
 static int pmd_syevd_f32(pmd_ctx* ctx, int n, float* A, long lda, float* w, float* work, int* info) {
-  const char* mode = getenv("PMD_SYEVD");
-  const bool force_lib = mode && !strcmp(mode, "rocsolver");
-  const bool force_own = mode && !strcmp(mode, "own");
-  if (!mode || !strcmp(mode, "f64")) {
-    static int f64_max = -1;
-    if (f64_max < 0) { const char* e_ = getenv("PMD_SYEVD_F64_MAX"); f64_max = e_ ? atoi(e_) : 512; }
-    if (n >= 1 && (n <= f64_max || mode)) return syevd_f64(ctx, n, A, lda, w, info);
-  }
+  const int mode = ctx->routes.syevd;
+  const bool force_lib = mode == PMD_SYEVD_ROCSOLVER;
+  const bool force_own = mode == PMD_SYEVD_OWN;
+  if (n >= 1 && (mode == PMD_SYEVD_F64 || (mode == PMD_SYEVD_AUTO && n <= SYEVD_F64_MAX))) return syevd_f64(ctx, n, A, lda, w, info);
   const bool own = !force_lib && (force_own || n >= 192) && n >= 3 && lda % 4 == 0 && lda >= pmd_round_up(n, 4) && !((uintptr_t)A & 15);
   if (!own) {
     pmd_prof_scope prof__(ctx, "rocsolver_ssyevd");
     PMD_BLAS(ctx, rocsolver_ssyevd(ctx->blas, rocblas_evect_original, rocblas_fill_lower, n, A, (rocblas_int)lda, w, work, info));
     return PMD_OK;
   }
-  const bool two_stage = mode && !strcmp(mode, "twostage") && n >= 256;
+  const bool two_stage = mode == PMD_SYEVD_TWOSTAGE && n >= 256;
   if (two_stage) {
     int done = 0;
     const int rc2 = pmd_syevd_two_stage(ctx, n, A, lda, w, info, &done);
@@ -1270,8 +1195,7 @@ static int pmd_syevd_f32(pmd_ctx* ctx, int n, float* A, long lda, float* w, floa
     pmd_prof_scope prof__(ctx, "rocsolver_sstedc");
     PMD_BLAS(ctx, rocsolver_sstedc(ctx->blas, rocblas_evect_tridiagonal, n, w, e, Z, n, info));
   }
-  const char* qmode = getenv("PMD_APPLY_Q");
-  if (qmode && !strcmp(qmode, "rocsolver")) {
+  if (ctx->routes.apply_q_rocsolver) {
     pmd_prof_scope prof__(ctx, "rocsolver_sormtr");
     PMD_BLAS(ctx, rocsolver_sormtr(ctx->blas, rocblas_side_left, rocblas_fill_lower, rocblas_operation_none, n, n, A,
                                    (rocblas_int)lda, tau, Z, n));

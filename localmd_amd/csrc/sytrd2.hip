@@ -10,7 +10,7 @@
 //                            A22 -= V W^T + W V^T,  W = Y - V (T^T V^T Y) / 2,  Y = A22 V T.
 //   stage 2  B = Q2 T Q2^T   band -> tridiagonal by bulge chasing (sweep s eliminates column s below the first subdiagonal,
 //                            task k of the sweep acts on rows s + 1 + k SB .. + SB); task (s, k) needs (s, k - 1) and
-//                            (s - 1, k + 1).  A workgroup runs SW consecutive sweeps in lockstep (one step per barrier, sweep
+//                            (s - 1, k + 1).  A workgroup runs WSW consecutive sweeps in lockstep (one step per barrier, sweep
 //                            i two tasks behind sweep i - 1); consecutive workgroups are kept apart by launches.
 //   T = Z L Z^T              rocSOLVER sstedc
 //   E = Q1 (Q2 Z)            Q2: the length-64 reflectors of stage 2 applied to 32-vector slabs (one workgroup per slab, no
@@ -342,12 +342,11 @@ int pmd_sy2sb_impl(pmd_ctx* ctx, int n, float* A, long lda, float* tau1, int* fl
 //   in both cases the diagonal block D = B(r_k, r_k) is updated from both sides.  The reflector (length SB, zero padded) goes
 //   to V2[k][s][.] / tau2[k][s] for the back-transformation.
 // Scheduling: task (s, k) runs at step t = 2 s + k (needs (s, k - 1) and (s - 1, k + 1), both at t - 1).  A workgroup owns
-// SW consecutive sweeps (one 256-thread team each) and walks the steps of its window with one barrier per phase; workgroup g
+// WSW consecutive sweeps (one wave each) and walks the steps of its window with one barrier per step; workgroup g
 // runs window q = L - g in launch L, so whatever its first sweep needs from workgroup g - 1 was finished by an earlier launch.
 // =============================================================================================
 namespace {
 
-constexpr int SW = 4;          // sweeps per workgroup
 constexpr int LDB = 2 * SB;    // band storage row length
 
 __global__ void band_extract_kernel(const float* __restrict__ A, long lda, int n, float* __restrict__ AB) {
@@ -362,175 +361,14 @@ __global__ void band_diag_kernel(const float* __restrict__ AB, int n, float* __r
   if (j < n - 1) e[j] = AB[(long)j * LDB + 1];
 }
 
-// team-wide sum of one value per thread of the 256-thread team (4 waves): returns the total to every thread of the team.
-// red: SW x 4 floats of shared memory; two barriers (the whole workgroup executes it in lockstep)
-__device__ __forceinline__ float team_sum(float v, float* red, int team, int tt) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  __syncthreads();
-  if ((tt & 63) == 0) red[team * 4 + (tt >> 6)] = v;
-  __syncthreads();
-  return red[team * 4] + red[team * 4 + 1] + red[team * 4 + 2] + red[team * 4 + 3];
-}
-
-__global__ __launch_bounds__(SW * 256) void sb2st_kernel(float* __restrict__ AB, int n, int launch, int h, int g_lo,
-                                                         float* __restrict__ V2, float* __restrict__ tau2) {
-  __shared__ float Bs[SW][SB][SB + 1];
-  __shared__ float Ds[SW][SB][SB + 1];
-  __shared__ float vcur[SW][SB], vprev[SW][SB], wv[SW][SB], zv[SW][SB];
-  __shared__ float sc[SW][4];      // tau_prev, tau, beta, alpha
-  __shared__ float red[SW * 4];
-  const int g = g_lo + blockIdx.x;
-  const int q = launch - g;
-  const int team = threadIdx.x >> 8, tt = threadIdx.x & 255;
-  const int i = tt >> 2, qd = tt & 3;          // row i, column quarter qd (columns qd * 16 .. + 15)
-  const int s = g * SW + team;
-  if (q < 0) return;
-  // the previous reflector of the sweep (task k - 1 ran in the previous step, possibly in the previous launch)
-  {
-    const int k_first = q * h - 2 * s;
-    float tp = 0.f;
-    if (s < n - 2 && k_first >= 1 && s + 1 + (long)(k_first - 1) * SB < n) {   // (a window may start behind the sweep's last task)
-      const long idx = (long)(k_first - 1) * n + s;
-      if (tt < SB) vprev[team][tt] = V2[idx * SB + tt];
-      tp = tau2[idx];
-    } else if (tt < SB) vprev[team][tt] = 0.f;
-    if (tt == 0) sc[team][0] = tp;
-  }
-  __syncthreads();
-  for (int t = q * h; t < (q + 1) * h; ++t) {
-    const int k = t - 2 * s;
-    const int r0 = s + 1 + k * SB;
-    const bool exists = s < n - 2 && k >= 0 && r0 < n && !(k == 0 && n - r0 < 2);
-    const int L = exists ? min(SB, n - r0) : 0;
-    const int c0 = r0 - SB;
-    // ---- load Bm (k >= 1) and D
-    if (exists) {
-#pragma unroll
-      for (int u = 0; u < 16; ++u) {
-        const int j = qd * 16 + u;
-        float bv = 0.f, dv = 0.f;
-        if (i < L) {
-          if (k >= 1) bv = AB[(long)(c0 + j) * LDB + SB + i - j];
-          if (j < L) dv = (i >= j) ? AB[(long)(r0 + j) * LDB + i - j] : AB[(long)(r0 + i) * LDB + j - i];
-        }
-        Bs[team][i][j] = bv;
-        Ds[team][i][j] = dv;
-      }
-      if (k == 0 && tt < SB) Bs[team][tt][0] = (tt < L) ? AB[(long)s * LDB + 1 + tt] : 0.f;   // x = B(r_0, s) as column 0
-    }
-    __syncthreads();
-    // ---- (a) Bm <- Bm (I - tau_prev v_prev v_prev^T)
-    float part = 0.f;
-    if (exists && k >= 1) {
-#pragma unroll
-      for (int u = 0; u < 16; ++u) part = fmaf(Bs[team][i][qd * 16 + u], vprev[team][qd * 16 + u], part);
-    }
-    part += __shfl_xor(part, 1);
-    part += __shfl_xor(part, 2);
-    if (exists && k >= 1) {
-      const float f = sc[team][0] * part;
-#pragma unroll
-      for (int u = 0; u < 16; ++u) Bs[team][i][qd * 16 + u] -= f * vprev[team][qd * 16 + u];
-    }
-    __syncthreads();
-    // ---- (b) reflector from column 0 (rows 0 .. L - 1)
-    const float x = (exists && tt < L && tt >= 1) ? Bs[team][tt][0] : 0.f;
-    const float xn2 = team_sum(x * x, red, team, tt);
-    if (tt == 0) {
-      float tau = 0.f, beta = 0.f, scale = 0.f;
-      if (exists && L >= 2) {
-        const float alpha = Bs[team][0][0];
-        beta = alpha;
-        if (xn2 > 0.f) {
-          beta = -copysignf(sqrtf(alpha * alpha + xn2), alpha);
-          tau = (beta - alpha) / beta;
-          scale = 1.f / (alpha - beta);
-        }
-      } else if (exists) {
-        beta = Bs[team][0][0];
-      }
-      sc[team][1] = tau; sc[team][2] = beta; sc[team][3] = scale;
-    }
-    __syncthreads();
-    const float tau = sc[team][1];
-    if (tt < SB) vcur[team][tt] = (exists && tt < L) ? ((tt == 0) ? 1.f : Bs[team][tt][0] * sc[team][3]) : 0.f;
-    __syncthreads();
-    // ---- (c) rest of Bm from the left: z[j] = sum_i v[i] Bm[i][j]; thread (j = i, quarter of the rows = qd)
-    if (exists && k >= 1 && tau != 0.f) {
-      float zp = 0.f;
-#pragma unroll
-      for (int u = 0; u < 16; ++u) zp = fmaf(vcur[team][qd * 16 + u], Bs[team][qd * 16 + u][i], zp);
-      zp += __shfl_xor(zp, 1);
-      zp += __shfl_xor(zp, 2);
-      if (qd == 0) zv[team][i] = zp;
-    }
-    __syncthreads();
-    if (exists && k >= 1 && tau != 0.f) {
-      const float f = tau * vcur[team][i];
-#pragma unroll
-      for (int u = 0; u < 16; ++u) {
-        const int j = qd * 16 + u;
-        if (j >= 1) Bs[team][i][j] -= f * zv[team][j];
-      }
-    }
-    // ---- (d) D <- H D H:  p = tau D v, alpha = -tau p^T v / 2, qv = p + alpha v, D -= v qv^T + qv v^T
-    float pp = 0.f;
-    if (exists && tau != 0.f) {
-#pragma unroll
-      for (int u = 0; u < 16; ++u) pp = fmaf(Ds[team][i][qd * 16 + u], vcur[team][qd * 16 + u], pp);
-    }
-    pp += __shfl_xor(pp, 1);
-    pp += __shfl_xor(pp, 2);
-    pp *= tau;
-    if (qd == 0) wv[team][i] = pp;
-    const float pv = team_sum((qd == 0) ? pp * vcur[team][i] : 0.f, red, team, tt);
-    const float alpha = -0.5f * tau * pv;
-    if (exists && tau != 0.f) {
-      if (qd == 0) wv[team][i] = pp + alpha * vcur[team][i];
-    }
-    __syncthreads();
-    // ---- store
-    if (exists) {
-      if (tau != 0.f) {
-        const float vi = vcur[team][i], qi = wv[team][i];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) {
-          const int j = qd * 16 + u;
-          if (i < L && j <= i) AB[(long)(r0 + j) * LDB + i - j] = Ds[team][i][j] - vi * wv[team][j] - qi * vcur[team][j];
-        }
-      }
-      if (k >= 1) {
-#pragma unroll
-        for (int u = 0; u < 16; ++u) {
-          const int j = qd * 16 + u;
-          if (i < L) {
-            float bv = Bs[team][i][j];
-            if (j == 0 && L >= 2) bv = (i == 0) ? sc[team][2] : 0.f;
-            AB[(long)(c0 + j) * LDB + SB + i - j] = bv;
-          }
-        }
-      } else if (tt < L) {
-        AB[(long)s * LDB + 1 + tt] = (tt == 0) ? sc[team][2] : 0.f;
-      }
-      const long idx = (long)k * n + s;
-      if (tt < SB) V2[idx * SB + tt] = vcur[team][tt];
-      if (tt == 0) tau2[idx] = tau;
-    }
-    __syncthreads();
-    if (tt < SB) vprev[team][tt] = exists ? vcur[team][tt] : vprev[team][tt];
-    if (tt == 0 && exists) sc[team][0] = tau;
-    __syncthreads();
-  }
-}
-
-
-// ---- second form: one WAVE per task (lane i = row i of the 64 x 64 blocks).  The off-diagonal block lives in the lane's
-// registers (row access) and in LDS (column access for z = v^T B), the diagonal block in registers only; vectors are
-// broadcast with readlane, reductions run on DPP, nothing inside a step needs a workgroup barrier: one barrier per step keeps
-// the WSW sweeps of a workgroup in lockstep.  Same scheduling as above (task (s, k) at step 2 s + k, workgroup g runs window
-// L - g in launch L).
+// One WAVE per task (lane i = row i of the 64 x 64 blocks).  The off-diagonal block lives in the lane's registers (row
+// access) and in LDS (column access for z = v^T B), the diagonal block in registers only; vectors are broadcast with
+// readlane, reductions run on DPP, nothing inside a step needs a workgroup barrier: one barrier per step keeps the WSW
+// sweeps of a workgroup in lockstep (a 256-thread team per task with workgroup barriers inside a step: 667 against 298 ms
+// at n = 10^4).
 constexpr int WSW = 8;         // sweeps (= waves) per workgroup
+// steps per launch: measured at n = 10^4 - 373 / 393 / 450 ms for 2 / 4 / 8
+constexpr int SB2ST_H = 2;
 
 __device__ __forceinline__ float wave_sum64(float v) {
   v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
@@ -726,14 +564,8 @@ int pmd_sb2st_impl(pmd_ctx* ctx, int n, const float* A, long lda, float* d, floa
   PMD_HIP(ctx, hipMemsetAsync(V2, 0, K * n * SB * sizeof(float), st));
   if (n > 2) {
     const int n_sweeps = n - 2;
-    static int team_form = -1;   // PMD_SB2ST=team: the first form (256-thread teams, four sweeps per workgroup)
-    if (team_form < 0) { const char* e_ = getenv("PMD_SB2ST"); team_form = (e_ && !strcmp(e_, "team")) ? 1 : 0; }
-    // steps per launch: measured at n = 10^4 - wave form 373 / 393 / 450 ms for h = 2 / 4 / 8, team form 667 ms at h = 8
-    static int h_env = 0;
-    if (!h_env) { const char* e_ = getenv("PMD_SB2ST_H"); h_env = e_ ? std::max(1, atoi(e_)) : (team_form ? 8 : 2); }
-    const int h = h_env;
-    const int SWX = team_form ? SW : WSW;
-    const int n_wg = (n_sweeps + SWX - 1) / SWX;
+    const int h = SB2ST_H;
+    const int n_wg = (n_sweeps + WSW - 1) / WSW;
     auto tasks_of = [&](int s) { return (n - s - 1 + SB - 1) / SB; };   // K_s
     // last step of the whole reduction, windows per workgroup
     long t_max = 0;
@@ -742,23 +574,20 @@ int pmd_sb2st_impl(pmd_ctx* ctx, int n, const float* A, long lda, float* d, floa
     const long Q = t_max / h + 1;
     for (long L = 0; L < Q + n_wg - 1; ++L) {
       // workgroups with work in launch L: window q = L - g, steps [q h, q h + h) against the workgroup's steps
-      // [2 g SW, 2 (g SW + SW - 1) + K_{g SW} - 1]
+      // [2 g WSW, 2 (g WSW + WSW - 1) + K_{g WSW} - 1]
       long g_lo = std::max<long>(0, L - Q + 1), g_hi = std::min<long>(n_wg - 1, L);
       while (g_lo <= g_hi) {   // drop workgroups whose window lies before / behind their steps
-        const long q = L - g_lo, t_first = 2L * g_lo * SWX, t_last = 2L * (g_lo * SWX + SWX - 1) + tasks_of((int)(g_lo * SWX)) - 1;
+        const long q = L - g_lo, t_first = 2L * g_lo * WSW, t_last = 2L * (g_lo * WSW + WSW - 1) + tasks_of((int)(g_lo * WSW)) - 1;
         if ((q + 1) * h - 1 < t_first || q * h > t_last) ++g_lo; else break;
       }
       while (g_hi >= g_lo) {
-        const long q = L - g_hi, t_first = 2L * g_hi * SWX, t_last = 2L * (g_hi * SWX + SWX - 1) + tasks_of((int)(g_hi * SWX)) - 1;
+        const long q = L - g_hi, t_first = 2L * g_hi * WSW, t_last = 2L * (g_hi * WSW + WSW - 1) + tasks_of((int)(g_hi * WSW)) - 1;
         if ((q + 1) * h - 1 < t_first || q * h > t_last) --g_hi; else break;
       }
       if (g_lo > g_hi) continue;
-      if (team_form)
-        hipLaunchKernelGGL(sb2st_kernel, dim3((unsigned)(g_hi - g_lo + 1)), dim3(SW * 256), 0, st, AB, n, (int)L, h, (int)g_lo, V2, tau2);
-      else
-        hipLaunchKernelGGL(sb2st_wave_kernel, dim3((unsigned)(g_hi - g_lo + 1)), dim3(WSW * 64), 0, st, AB, n, (int)L, h, (int)g_lo, V2, tau2);
+      hipLaunchKernelGGL(sb2st_wave_kernel, dim3((unsigned)(g_hi - g_lo + 1)), dim3(WSW * 64), 0, st, AB, n, (int)L, h, (int)g_lo, V2, tau2);
     }
-    PMD_LAUNCH_CHECK(ctx, "sb2st_kernel");
+    PMD_LAUNCH_CHECK(ctx, "sb2st_wave_kernel");
   }
   hipLaunchKernelGGL(band_diag_kernel, dim3((n + 255) / 256), dim3(256), 0, st, AB, n, d, e);
   PMD_LAUNCH_CHECK(ctx, "band_diag_kernel");

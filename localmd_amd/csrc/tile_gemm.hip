@@ -436,8 +436,7 @@ int pmd_launch_tile_atx(pmd_ctx* ctx, const float* X, long ldx, const int* pix, 
                                               out_tile_stride, ldo, n_tiles, T, slices, kz);
   // d in (256, 400]: LDS-DMA staged variant (needs the two spare chunks behind every row: ldx >= 32 (chunks + 2))
   {
-    const char* dm = getenv("PMD_ATX_DMA");
-    const bool dma_ok = !(dm && !strcmp(dm, "0")) && ldx >= 32L * ((T + 31) / 32 + 2) && (ldx % 4) == 0;
+    const bool dma_ok = ctx->routes.atx_dma && ldx >= 32L * ((T + 31) / 32 + 2) && (ldx % 4) == 0;
     if (v.kjw == 25 && v.ks == 1 && dma_ok)
       return launch_atx_dma<25>(ctx, X, ldx, pix, pix_stride, row0_stride, d, A, a_tile_stride, a_ld, Out, out_tile_stride,
                                 ldo, n_tiles, T, slices, ctx->atx_ranks);
@@ -456,94 +455,14 @@ int pmd_launch_tile_atx(pmd_ctx* ctx, const float* X, long ldx, const int* pix, 
 }
 
 // ------------------------------------------------------------------------------------------
-// tile_xbt.  No LDS: wave w of workgroup (tile, slice, mblock) owns MPW 16-pixel M tiles and all
-// four 16-component N tiles; per 16-frame group every lane loads one float4 of X per M tile
-// (16 rows x 64 B per wave instruction) and one float4 of B per N tile, then issues 4*MPW*4
-// MFMAs.  K order inside a group is permuted like tile_atx (slot kk <-> frame 4*kk + s).
-// Loads run one group ahead of the MFMAs (two register sets).
+// tile_xbt.  Wave w of workgroup (tile, slice, mblock) owns MPW 16-pixel M tiles and all four
+// 16-component N tiles; per 16-frame group every lane loads one float4 of X per M tile (16 rows
+// x 64 B per wave instruction), then issues 4*MPW*4 MFMAs.  K order inside a group is permuted
+// like tile_atx (slot kk <-> frame 4*kk + s).  Loads run one group ahead of the MFMAs.
+// B is staged through LDS: wave w fetches component tile w only and publishes it (two 4 KB buffers, one barrier per
+// group: 112 MFMAs = 3 600 cycles apart); every wave reads its four operand fragments from there (four waves each
+// loading all of B fetch the same 4 KB four times: 27 of 68 GB through L2 per launch at config 3, 20.5 against 15.3 ms).
 // ------------------------------------------------------------------------------------------
-template <int MPW>
-__global__ __launch_bounds__(256) void tile_xbt_kernel(const float* __restrict__ X, long ldx,
-                                                       const int* __restrict__ pix, int pix_stride, long row0_stride,
-                                                       int d, const float* __restrict__ B, long b_tile_stride, long ldb,
-                                                       float* __restrict__ S, long s_tile_stride, long s_slice_stride,
-                                                       int s_ld, int n_groups_total, int groups_per_slice) {
-  const int tile = pmd_xcd_tile();
-  const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // (uniform, and known to be)
-  const int n16 = lane & 15, kk = lane >> 4;
-  const int m0 = (blockIdx.z * 4 + wid) * MPW;  // first M tile of this wave
-  const int g_begin = blockIdx.y * groups_per_slice;
-  const int g_end = min(n_groups_total, g_begin + groups_per_slice);
-
-  const float* xrow[MPW];
-  bool mvalid[MPW];
-  float rmask[MPW];
-#pragma unroll
-  for (int i = 0; i < MPW; ++i) {
-    const int q = 16 * (m0 + i) + n16;
-    mvalid[i] = 16 * (m0 + i) < d;  // wave-uniform
-    const int qc = min(q, d - 1);
-    const long row = pix ? (long)pix[(long)tile * pix_stride + qc] : (long)tile * row0_stride + qc;
-    xrow[i] = X + row * ldx + 4 * kk;
-    rmask[i] = (q < d) ? 1.f : 0.f;
-  }
-  const float* brow = B + (long)tile * b_tile_stride + (long)n16 * ldb + 4 * kk;
-
-  f32x4 acc[MPW][4];
-#pragma unroll
-  for (int i = 0; i < MPW; ++i)
-#pragma unroll
-    for (int n = 0; n < 4; ++n) acc[i][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-  if (g_begin < g_end && mvalid[0]) {
-    f32x4 a0[MPW], b0[4], a1[MPW], b1[4];
-    auto load = [&](f32x4* a, f32x4* b, int g) {
-      const long t = (long)g * 16;
-#pragma unroll
-      for (int i = 0; i < MPW; ++i)
-        if (mvalid[i]) a[i] = *reinterpret_cast<const f32x4*>(xrow[i] + t);
-#pragma unroll
-      for (int n = 0; n < 4; ++n) b[n] = *reinterpret_cast<const f32x4*>(brow + (long)(16 * n) * ldb + t);
-    };
-    auto compute = [&](const f32x4* a, const f32x4* b) {
-#pragma unroll
-      for (int s = 0; s < 4; ++s)
-#pragma unroll
-        for (int i = 0; i < MPW; ++i)
-          if (mvalid[i]) {
-            const float av = a[i][s] * rmask[i];
-#pragma unroll
-            for (int n = 0; n < 4; ++n) acc[i][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b[n][s], acc[i][n], 0, 0, 0);
-          }
-    };
-    load(a0, b0, g_begin);
-    int g = g_begin;
-    for (; g + 1 < g_end; g += 2) {
-      load(a1, b1, g + 1);
-      compute(a0, b0);
-      if (g + 2 < g_end) load(a0, b0, g + 2);
-      compute(a1, b1);
-    }
-    if (g < g_end) compute(a0, b0);
-  }
-
-  float* sp = S + (long)tile * s_tile_stride + (long)blockIdx.y * s_slice_stride;
-#pragma unroll
-  for (int i = 0; i < MPW; ++i) {
-    if (!mvalid[i]) continue;
-#pragma unroll
-    for (int n = 0; n < 4; ++n) {
-      // C layout: col = lane&15 -> component, row = 4*(lane>>4) + reg -> pixel
-      float* o = sp + (long)(16 * n + n16) * s_ld + 16 * (m0 + i) + 4 * kk;
-      *reinterpret_cast<f32x4*>(o) = acc[i][n];
-    }
-  }
-}
-
-// The same with B staged through LDS (round 3).  In the form above every wave loads all four 16-component tiles of B for
-// every 16-frame group - the four waves of a workgroup fetch the same 4 KB four times, 27 GB of the 68 GB the kernel pulls
-// through L2 per launch at config 3.  Here wave w fetches component tile w only and publishes it in LDS (two 4 KB buffers,
-// one barrier per group: 112 MFMAs = 3 600 cycles apart); every wave reads its four operand fragments from there.
 template <int MPW>
 __global__ __launch_bounds__(256) void tile_xbt_lds_kernel(const float* __restrict__ X, long ldx,
                                                            const int* __restrict__ pix, int pix_stride, long row0_stride,
@@ -659,20 +578,12 @@ int pmd_launch_tile_xbt(pmd_ctx* ctx, const float* X, long ldx, const int* pix, 
                                   (size_t)(slices_asked - slices) * s_slice_stride * sizeof(float), (size_t)n_tiles, ctx->stream));
   }
   // M tiles per wave: spread small tiles over the four waves, 7 per wave (112 accumulator VGPRs) at most
-  // PMD_XBT_LDS=0: every wave loads all of B itself (the form of rounds 1-2, A/B runs)
-  static int blds = -1;
-  if (blds < 0) { const char* e = getenv("PMD_XBT_LDS"); blds = (e && !strcmp(e, "0")) ? 0 : 1; }
 #define XBT_LAUNCH(MPW_)                                                                                              \
   {                                                                                                                   \
     const int mblocks = (mtiles + 4 * MPW_ - 1) / (4 * MPW_);                                                         \
-    if (blds)                                                                                                         \
-      hipLaunchKernelGGL(tile_xbt_lds_kernel<MPW_>, dim3(n_tiles, slices, mblocks), dim3(256), 0, ctx->stream, X, ldx, pix, \
-                         pix_stride, row0_stride, d, B, b_tile_stride, ldb, S, s_tile_stride, s_slice_stride, s_ld,   \
-                         n_groups, gps);                                                                              \
-    else                                                                                                              \
-      hipLaunchKernelGGL(tile_xbt_kernel<MPW_>, dim3(n_tiles, slices, mblocks), dim3(256), 0, ctx->stream, X, ldx, pix, \
-                         pix_stride, row0_stride, d, B, b_tile_stride, ldb, S, s_tile_stride, s_slice_stride, s_ld,   \
-                         n_groups, gps);                                                                              \
+    hipLaunchKernelGGL(tile_xbt_lds_kernel<MPW_>, dim3(n_tiles, slices, mblocks), dim3(256), 0, ctx->stream, X, ldx, pix, \
+                       pix_stride, row0_stride, d, B, b_tile_stride, ldb, S, s_tile_stride, s_slice_stride, s_ld,     \
+                       n_groups, gps);                                                                                \
   }
   if (mtiles <= 4) XBT_LAUNCH(1)
   else if (mtiles <= 8) XBT_LAUNCH(2)
@@ -796,8 +707,7 @@ int pmd_launch_tile_gram(pmd_ctx* ctx, const float* In, long tile_stride, long l
   if (slices < 1) slices = 1;
   int cps = (len + slices - 1) / slices;
   cps = (int)pmd_round_up(cps, 32);
-  const char* gm = getenv("PMD_GRAM_MFMA");
-  if (!(gm && !strcmp(gm, "0")) && ld % 4 == 0 && ld >= 16 && tile_stride % 4 == 0 && !((uintptr_t)In & 15))
+  if (ctx->routes.gram_mfma && ld % 4 == 0 && ld >= 16 && tile_stride % 4 == 0 && !((uintptr_t)In & 15))
     hipLaunchKernelGGL(tile_gram_mfma_kernel, dim3(n_tiles, slices), dim3(256), 0, ctx->stream, In, tile_stride, ld, len,
                        cps, G, (long)slices * 4096);
   else
@@ -1067,12 +977,12 @@ int pmd_launch_tile_rowmix(pmd_ctx* ctx, const float* In, long in_tile_stride, l
     const float* in = In + (long)t0 * in_tile_stride;
     const double* nn = N + (long)t0 * n_tile_stride;
     float* out = Out + (long)t0 * out_tile_stride;
-    const char* rm = getenv("PMD_ROWMIX_MFMA");
+    const int rm = ctx->routes.rowmix_mfma;   // PMD_ROWMIX_MFMA: -1 = by shape, 0 = scalar kernels, 16 / 64 = that MFMA form
     const bool quads = ld_in % 4 == 0 && ld_out % 4 == 0 && in_tile_stride % 4 == 0 && out_tile_stride % 4 == 0 && !((uintptr_t)in & 15) &&
-                       !((uintptr_t)out & 15) && ld_in >= ((len + 3) & ~3) && len >= 4 && !(rm && !strcmp(rm, "16"));
+                       !((uintptr_t)out & 15) && ld_in >= ((len + 3) & ~3) && len >= 4 && rm != 16;
     // (the 64-position form pays with 200 VGPRs - two workgroups per CU: it wins where tiles are plentiful and each one is
     // small - 13.3 against 18.0 ms at 16 129 tiles x 1000 frames - and loses at 2601 tiles x 10^4 frames, 11.6 against 7.7)
-    if (n_out > 4 && !(rm && !strcmp(rm, "0")) && quads && (n_tiles >= 8192 || (rm && !strcmp(rm, "64")))) {
+    if (n_out > 4 && rm != 0 && quads && (n_tiles >= 8192 || rm == 64)) {
       // workgroups per tile: each one first loads its slice of the 64 x 64 mixing matrix (32 KB per tile and workgroup),
       // so no more of them than it takes to fill the chip (~8192 workgroups in all)
       int bxm = (len + 63) / 64;
@@ -1081,7 +991,7 @@ int pmd_launch_tile_rowmix(pmd_ctx* ctx, const float* In, long in_tile_stride, l
       if (bxm > 16) bxm = 16;
       hipLaunchKernelGGL(tile_rowmix_mfma4_kernel, dim3(bxm, tn), dim3(256), 0, ctx->stream, in, in_tile_stride, ld_in, nn,
                          n_tile_stride, n_in, n_out, out, out_tile_stride, ld_out, len);
-    } else if (n_out > 4 && !(rm && !strcmp(rm, "0"))) {
+    } else if (n_out > 4 && rm != 0) {
       int bxm = (len + 15) / 16;
       if (bxm > 16) bxm = 16;
       hipLaunchKernelGGL(tile_rowmix_mfma_kernel, dim3(bxm, tn), dim3(256), 0, ctx->stream, in, in_tile_stride, ld_in, nn,

@@ -161,9 +161,7 @@ int pmd_launch_wide_eig(pmd_ctx* ctx, const double* G, int slices, int rp, int n
   }
   // rocSOLVER's batched Jacobi solver (dsyevj; PMD_WIDE_EIG=syevd selects the divide-and-conquer one, which runs the
   // problems of a batch one after the other: 640 us per 60 x 60 problem measured, 10 s for a 65 000-problem batch)
-  static int use_syevd = -1;
-  if (use_syevd < 0) { const char* m = getenv("PMD_WIDE_EIG"); use_syevd = (m && !strcmp(m, "syevd")) ? 1 : 0; }
-  if (use_syevd) {
+  if (ctx->routes.wide_eig_syevd) {
     WIDE_BLAS(ctx, rocsolver_dsyevd_strided_batched(ctx->blas, rocblas_evect_original, rocblas_fill_lower, n, A, n, (rocblas_stride)n * n, w,
                                                     (rocblas_stride)n, e, (rocblas_stride)n, info, n_tiles));
   } else {

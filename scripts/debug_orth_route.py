@@ -6,7 +6,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tests.test_gpu_fuzz import draw_wide_cases
 import tests.test_gpu_parity as tp
-from tests.util import DeviceSource
+from tests.util import DeviceSource, context_under
 from oracle import pmd_oracle as O
 import torch
 from localmd_amd._lib import Context, ptr
@@ -51,8 +51,11 @@ for drv in ("evd", "ev", "evr"):
     lam, E = scipy.linalg.eigh(C32, driver=drv, check_finite=False)
     figure(f"same C32, LAPACK ssy{drv}", lam, E)
 # own eigensolver on the same C32
+mode_ctx = {}   # one context per mode: the route switches are read when a context is created
 def own_eig(Cm, mode):
-    os.environ["PMD_SYEVD"] = mode
+    if mode not in mode_ctx:
+        mode_ctx[mode] = context_under({"PMD_SYEVD": mode})
+    ctx = mode_ctx[mode]
     m = Cm.shape[0]
     ld = (m + 3) // 4 * 4
     A = torch.zeros((m, ld), dtype=torch.float32, device=ctx.device)
@@ -60,7 +63,6 @@ def own_eig(Cm, mode):
     w = torch.zeros(m, dtype=torch.float32, device=ctx.device); work = torch.zeros(m, dtype=torch.float32, device=ctx.device)
     info = torch.zeros(4, dtype=torch.int32, device=ctx.device)
     ctx.call("pmdk_syevd", m, ptr(A), ld, ptr(w), ptr(work), ptr(info)); ctx.sync()
-    os.environ.pop("PMD_SYEVD")
     return w.cpu().numpy(), A[:, :m].cpu().numpy().T
 for mode in ("own", "rocsolver", "twostage"):
     lam, E = own_eig(C32, mode)

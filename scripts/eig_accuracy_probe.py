@@ -5,6 +5,7 @@ import numpy as np
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from localmd_amd import _lib
+from tests.util import context_under
 
 def report(name, G64, V, w, E):
     # E columns = eigenvectors, w eigenvalues (any order)
@@ -32,9 +33,9 @@ for n, T, ratio in ((89, 314, 66.0), (300, 1000, 100.0), (1200, 3000, 100.0)):
     import scipy.linalg
     w, E = scipy.linalg.eigh(G32, driver="evd", check_finite=False)
     report("scipy float32 ssyevd", G64, V, w, E)
-    ctx = _lib.Context(0); P = _lib.ptr
+    P = _lib.ptr
     for mode in ("rocsolver", "own"):
-        os.environ["PMD_SYEVD"] = mode
+        ctx = context_under({"PMD_SYEVD": mode})   # the route switches are read when a context is created
         ld = (n + 3) // 4 * 4
         buf = np.zeros((n, ld), np.float32); buf[:, :n] = G32
         A = torch.from_numpy(buf).cuda()
@@ -42,4 +43,4 @@ for n, T, ratio in ((89, 314, 66.0), (300, 1000, 100.0), (1200, 3000, 100.0)):
         ctx.call("pmdk_syevd", n, P(A), ld, P(wd), P(work), P(info)); ctx.sync()
         Eg = A.cpu().numpy()[:, :n].T   # memory row j = eigenvector j
         report("GPU " + mode, G64, V, wd.cpu().numpy(), Eg)
-    ctx.close()
+        ctx.close()

@@ -8,6 +8,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from localmd_amd import _lib  # noqa: E402
+from tests.util import context_under  # noqa: E402
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 10000
 ctx = _lib.Context(0)
@@ -26,8 +27,10 @@ for impl in (1, 0, 1):
     print("sytrd impl", impl, "%.1f ms" % ((time.perf_counter() - t0) * 1e3), "d[:3]", d[:3].tolist(), "e[:3]", e[:3].tolist(), flush=True)
 w = torch.zeros(n, device="cuda"); work = torch.zeros(n, device="cuda"); info = torch.zeros(4, dtype=torch.int32, device="cuda")
 res = {}
+# one context per mode: the route switches are read when a context is created
+mode_ctx = {mode: context_under({"PMD_SYEVD": mode}) for mode in ("own", "rocsolver")}
 for mode in ("own", "rocsolver", "own"):
-    os.environ["PMD_SYEVD"] = mode
+    ctx = mode_ctx[mode]
     A = S.clone()
     ctx.profile_enable(True)
     torch.cuda.synchronize()

@@ -4,8 +4,10 @@ import os, sys, time, ctypes as C
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from localmd_amd._lib import Context, ptr
-ctx = Context(0)
+from localmd_amd._lib import ptr
+from tests.util import context_under
+# one context per mode: the route switches are read when a context is created
+mode_ctx = {mode: context_under({"PMD_SYEVD": mode}) for mode in ("own", "twostage")}
 sizes = [int(a) for a in sys.argv[1:]] or [300, 1030, 4000]
 for n in sizes:
     rng = np.random.default_rng(n)
@@ -14,7 +16,7 @@ for n in sizes:
     lda = (n + 3) // 4 * 4
     res = {}
     for mode in ("own", "twostage"):
-        os.environ["PMD_SYEVD"] = mode
+        ctx = mode_ctx[mode]
         for rep in range(2):
             A = torch.zeros((n, lda), dtype=torch.float32, device=ctx.device)
             A[:, :n] = torch.from_numpy(A0).to(ctx.device)

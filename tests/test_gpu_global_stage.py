@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 from localmd_amd import grid
+from tests.util import context_under
 
 pytestmark = pytest.mark.gpu
 
@@ -39,18 +40,9 @@ def _i32(ctx, a):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(ctx.device)
 
 
-def _fresh_ctx(monkeypatch, split):
-    """A Context of its own: PMD_GEMM_SPLIT is read when a context is created."""
-    from localmd_amd._lib import Context
-
-    if split:
-        monkeypatch.delenv("PMD_GEMM_SPLIT", raising=False)
-    else:
-        monkeypatch.setenv("PMD_GEMM_SPLIT", "0")
-    try:
-        return Context(0)
-    finally:
-        monkeypatch.delenv("PMD_GEMM_SPLIT", raising=False)
+def _fresh_ctx(split):
+    """A Context of its own: PMD_GEMM_SPLIT, like every route switch, is read when a context is created."""
+    return context_under({"PMD_GEMM_SPLIT": None if split else "0"})
 
 
 def _profiled(ctx, fn):
@@ -238,31 +230,37 @@ def _apply_setup(name, cap):
     return L
 
 
+@pytest.fixture(scope="module")
+def plain_apply_ctx():
+    """One context for all "plain" cases below, created under PMD_GRAM_APPLY_MFMA=0."""
+    ctx = context_under({"PMD_GRAM_APPLY_MFMA": "0"})
+    yield ctx
+    ctx.close()
+
+
 @pytest.mark.parametrize("ncols", [1, 3, 4, 255, 257, 1000])
 @pytest.mark.parametrize("kernel", ["mfma", "plain"])
 @pytest.mark.parametrize("layout", [("grid70x80", 16), ("grid70x80", 32), ("snapped73x82", 48), ("grid70x80", 64),
                                     ("virtual", 64)])
-def test_gram_apply_matches_float64(gpu_ctx, monkeypatch, layout, kernel, ncols):
+def test_gram_apply_matches_float64(gpu_ctx, plain_apply_ctx, layout, kernel, ncols):
     """pmd_gram_apply (GM = G M on the block-sparse G) against float64 G M with the same fp32 G: element-wise within
     n 2^-24 (|G| |M|), n the terms of the row (any summation order); both kernels, every max_rank bucket (tile ranks capped
     at 16 / 32 / 48 / 64: MFMA CT 1-4, plain 16 / 32 / 64); columns >= ncols of GM untouched; a call on a tile sub-range
     (the sharded driver's call) gives those tiles' rows bit for bit."""
     torch = _t()
-    ctx = gpu_ctx
+    ctx = gpu_ctx if kernel == "mfma" else plain_apply_ctx
     name, cap = layout
     L = _apply_setup(name, cap)
     K, Rt = L["K"], L["Rt"]
     Rc = Rt + K
     gb = _gram_blocks(ctx, L)
     if kernel == "mfma":
-        monkeypatch.delenv("PMD_GRAM_APPLY_MFMA", raising=False)
         ldm = (ncols + 1 + 3) // 4 * 4           # ncols = ldm - 1 where ncols % 4 == 3 (the driver's "drop" shape)
         ldgm = ldm
         Mbuf = torch.empty((Rc * ldm,), device=ctx.device)
         GMbuf = torch.full((Rc * ldgm,), float("nan"), device=ctx.device)
         M, GM = Mbuf.view(Rc, ldm), GMbuf.view(Rc, ldgm)
     else:
-        monkeypatch.setenv("PMD_GRAM_APPLY_MFMA", "0")
         ldm = ncols + (1 if ncols % 2 == 0 else 2)    # odd
         ldgm = ldm + 2
         Mbuf = torch.empty((Rc * ldm + 1,), device=ctx.device)
@@ -356,7 +354,7 @@ def _mtgm_operands(torch, device, rows, m, seed):
     return M, GM
 
 
-def test_gram_mtgm_concatenated_route(gpu_ctx, monkeypatch):
+def test_gram_mtgm_concatenated_route(gpu_ctx):
     """The concatenated fp16-piece route of pmd_gram_mtgm at its default gates: m = 4096 (row blocks of 1024: 256 output
     macro tiles), rows = 12 500 (above 100 GFLOP per row block; 13 accumulation chunks of 1024, the last one ragged).  The
     profile shows gemm_f16x2; every row block's error against float64 stays at the level of the fp32 route of a
@@ -370,7 +368,7 @@ def test_gram_mtgm_concatenated_route(gpu_ctx, monkeypatch):
     bs = _mtgm_block_size(m)
     errs, prof = _mtgm_errors(ctx, M, GM, rows, m, C64, bs)
     assert "gemm_f16x2" in prof, prof
-    ref_ctx = _fresh_ctx(monkeypatch, split=False)
+    ref_ctx = _fresh_ctx(split=False)
     try:
         errs32, prof32 = _mtgm_errors(ref_ctx, M, GM, rows, m, C64, bs)
     finally:
@@ -381,7 +379,7 @@ def test_gram_mtgm_concatenated_route(gpu_ctx, monkeypatch):
 
 
 @pytest.mark.parametrize("m,rows", [(1000, 309827), (2000, 110576)])
-def test_gram_mtgm_fallback_keeps_the_fp32_product(gpu_ctx, monkeypatch, m, rows):
+def test_gram_mtgm_fallback_keeps_the_fp32_product(gpu_ctx, m, rows):
     """Where the concatenated route is gated off (fewer than 256 output macro tiles: the many-tile workloads of bench.py,
     1024x1024x1000_b16 and 1024x1024x2000_b32), every row block of pmd_gram_mtgm is the fp32 product: no fp16-piece product
     in the profile of the call (a two-piece product over the whole inner dimension is the arithmetic that breaks this
@@ -394,7 +392,7 @@ def test_gram_mtgm_fallback_keeps_the_fp32_product(gpu_ctx, monkeypatch, m, rows
     C64 = _mtgm64(torch, M, GM, rows, m)
     bs = _mtgm_block_size(m)
     errs, prof = _mtgm_errors(ctx, M, GM, rows, m, C64, bs)
-    ref_ctx = _fresh_ctx(monkeypatch, split=False)
+    ref_ctx = _fresh_ctx(split=False)
     try:
         errs32, _ = _mtgm_errors(ref_ctx, M, GM, rows, m, C64, bs)
     finally:
@@ -404,7 +402,7 @@ def test_gram_mtgm_fallback_keeps_the_fp32_product(gpu_ctx, monkeypatch, m, rows
     assert "gemm_f16x2" not in prof and "f16x2_split" not in prof, sorted(prof)
 
 
-def test_gemm_mtz_many_tile_shape(gpu_ctx, monkeypatch):
+def test_gemm_mtz_many_tile_shape(gpu_ctx):
     """pmd_gemm as the driver calls it for M^T Z at the many-tile shape (1000 x 1000 x 309 827, M^T at leading dimension
     pmd_gram_mtgm_ld): error against float64 at most 1.5 x that of the split-K sgemm route (PMD_GEMM_SPLIT=0 context).
     Measured on MI355X: 1.56e-6 from the two-piece product over the whole inner dimension, 3.5e-6 from split-K sgemm."""
@@ -421,7 +419,7 @@ def test_gemm_mtz_many_tile_shape(gpu_ctx, monkeypatch):
         ref += Mt[:, r0:r1].double() @ Z[r0:r1].double()
     errs = []
     for split in (True, False):
-        cx = ctx if split else _fresh_ctx(monkeypatch, split=False)
+        cx = ctx if split else _fresh_ctx(split=False)
         try:
             W1 = torch.empty((m, T), device=ctx.device)
             cx.call("pmd_gemm", 0, 0, m, T, rows, 1.0, P(Mt), ld, P(Z), T, 0.0, P(W1), T)

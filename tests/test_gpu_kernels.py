@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from oracle import pmd_oracle as O, philox
-from tests.util import rel_err
+from tests.util import context_under, rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -280,7 +280,8 @@ def test_small_eig(gpu_ctx):
     Nn = V1[b, :n, :n]
     W = Nn.T @ mats[b] @ Nn
     # (the QL kernel resolves eigenvalues to eps64 lambda_max absolutely, the Jacobi kernel relatively: the smallest kept one is
-    # 1e-8 lambda_max here, so N^T M N is the identity to ~1e-8 / 1e-16 = a few 1e-9 with QL, 1e-12 with PMD_SMALL_EIG=jacobi)
+    # 1e-8 lambda_max here, so N^T M N is the identity to ~1e-8 / 1e-16 = a few 1e-9 with QL, where the Jacobi kernel it
+    # replaced gave 1e-12)
     assert np.abs(W[np.ix_(kept, kept)] - np.eye(kept.sum())).max() < 1e-7
     assert np.all(Nn[:, ~kept] == 0)
 
@@ -445,7 +446,7 @@ def test_sytrd_eigenvalues_2500(gpu_ctx):
 
 @pytest.mark.parametrize("n", [3, 40, 72, 191, 512])
 def test_syevd_small_orders_in_double(gpu_ctx, n):
-    """Orders <= 512 (PMD_SYEVD_F64_MAX) are diagonalised in double precision and rounded: the result is the correctly
+    """Orders <= 512 (SYEVD_F64_MAX of sytrd.hip) are diagonalised in double precision and rounded: the result is the correctly
     rounded eigendecomposition of the fp32 matrix - graded spectrum, small eigenvalues to high RELATIVE accuracy."""
     torch = _t()
     ctx = gpu_ctx
@@ -479,11 +480,19 @@ def test_syevd_small_orders_in_double(gpu_ctx, n):
 
 
 @pytest.mark.parametrize("n,force", [(150, True), (301, True), (1200, False)])
-def test_syevd_own_path(gpu_ctx, n, force, monkeypatch):
+def test_syevd_own_path(gpu_ctx, n, force):
+    if force:   # the route switches are read when a context is created
+        ctx = context_under({"PMD_SYEVD": "own"})
+        try:
+            _check_syevd_own_path(ctx, n)
+        finally:
+            ctx.close()
+    else:
+        _check_syevd_own_path(gpu_ctx, n)
+
+
+def _check_syevd_own_path(ctx, n):
     torch = _t()
-    ctx = gpu_ctx
-    if force:
-        monkeypatch.setenv("PMD_SYEVD", "own")
     rng = np.random.default_rng(n)
     S = _sym_matrix(rng, n)
     ld = (n + 3) // 4 * 4
@@ -509,14 +518,21 @@ def test_syevd_own_path(gpu_ctx, n, force, monkeypatch):
     assert np.abs(E @ S64 - wv[:, None] * E).max() < 1e-5 * np.abs(S64).max() * np.sqrt(n)
 
 
+@pytest.fixture(scope="module")
+def twostage_ctx():
+    """A context created under PMD_SYEVD=twostage (the route switches are read when a context is created)."""
+    ctx = context_under({"PMD_SYEVD": "twostage"})
+    yield ctx
+    ctx.close()
+
+
 @pytest.mark.parametrize("n,rank", [(300, None), (1030, None), (2117, None), (600, 100)])
-def test_syevd_two_stage_route(gpu_ctx, n, rank, monkeypatch):
+def test_syevd_two_stage_route(twostage_ctx, n, rank):
     """PMD_SYEVD=twostage: dense -> band -> tridiagonal (sytrd2.hip), sstedc, both back-transformations.  An exactly zero
     trailing block (rank given: only the leading rank x rank block is set) makes a panel of stage 1 singular: the call has to
     fall back to the one-stage route, same contract."""
     torch = _t()
-    ctx = gpu_ctx
-    monkeypatch.setenv("PMD_SYEVD", "twostage")
+    ctx = twostage_ctx
     rng = np.random.default_rng(n)
     if rank is None:
         S = _sym_matrix(rng, n)
@@ -548,6 +564,43 @@ def test_syevd_two_stage_route(gpu_ctx, n, rank, monkeypatch):
     np.testing.assert_allclose(wv, np.linalg.eigvalsh(S64), atol=3e-6 * np.abs(S64).max() * np.sqrt(n))
     assert np.abs(E @ E.T - np.eye(n)).max() < 5e-5 * np.sqrt(n)
     assert np.abs(E @ S64 - wv[:, None] * E).max() < 1e-5 * np.abs(S64).max() * np.sqrt(n)
+
+
+def test_route_switches_are_fixed_when_a_context_is_created(monkeypatch):
+    """The library reads its PMD_* route switches when a context is created and keeps them for that context: a variable
+    set afterwards does not reach an existing context, and does reach one created from then on."""
+    torch = _t()
+    n = 300
+    S = _sym_matrix(np.random.default_rng(n), n)
+
+    def groups(ctx):
+        Sd = dev(ctx, S)
+        w = torch.empty(n, dtype=torch.float32, device=ctx.device)
+        work = torch.empty(n, dtype=torch.float32, device=ctx.device)
+        info = torch.zeros(4, dtype=torch.int32, device=ctx.device)
+        ctx.profile_enable(True)
+        ctx.call("pmdk_syevd", n, P(Sd), n, P(w), P(work), P(info))
+        ctx.sync()
+        prof = ctx.profile_summary()
+        ctx.profile_enable(False)
+        assert int(info[0]) == 0
+        return prof
+
+    old_ctx = context_under({"PMD_SYEVD": None})
+    try:
+        monkeypatch.setenv("PMD_SYEVD", "twostage")
+        prof = groups(old_ctx)
+        assert "sy2sb" not in prof, prof
+        from localmd_amd._lib import Context
+
+        new_ctx = Context(0)
+        try:
+            prof = groups(new_ctx)
+            assert "sy2sb" in prof, prof
+        finally:
+            new_ctx.close()
+    finally:
+        old_ctx.close()
 
 
 @pytest.mark.parametrize("m", [90, 300, 515])
@@ -613,7 +666,7 @@ def test_sytrd_beyond_one_batch_of_partials(gpu_ctx, n):
     np.testing.assert_allclose(d1[:50], d0[:50], rtol=1e-4)   # the first columns have not drifted yet
 
 
-def test_sytrd_advance_forms_agree(gpu_ctx, monkeypatch):
+def test_sytrd_advance_forms_agree(gpu_ctx):
     """The advance step with 32 positions x 8 parts per workgroup (default) and the 64 x 4 form (PMD_SYTRD_ADVANCE=old)
     sum the same partials in different orders: same tridiagonal matrix up to fp32 rounding (compared through its
     eigenvalues, which are well conditioned; the entries of T are not), each form reproducible bit for bit."""
@@ -629,11 +682,7 @@ def test_sytrd_advance_forms_agree(gpu_ctx, monkeypatch):
     Sp[:, :n] = (X @ X.T) / n
     del X
 
-    def run(form):
-        if form is None:
-            monkeypatch.delenv("PMD_SYTRD_ADVANCE", raising=False)
-        else:
-            monkeypatch.setenv("PMD_SYTRD_ADVANCE", form)
+    def run(ctx):
         A = Sp.clone()
         d = torch.zeros(n, device=ctx.device)
         e = torch.zeros(n, device=ctx.device)
@@ -642,9 +691,13 @@ def test_sytrd_advance_forms_agree(gpu_ctx, monkeypatch):
         ctx.sync()
         return d.cpu().numpy(), e.cpu().numpy()[:n - 1]
 
-    d1, e1 = run(None)
-    d1b, e1b = run(None)
-    d0, e0 = run("old")
+    d1, e1 = run(gpu_ctx)
+    d1b, e1b = run(gpu_ctx)
+    old_ctx = context_under({"PMD_SYTRD_ADVANCE": "old"})   # the route switches are read when a context is created
+    try:
+        d0, e0 = run(old_ctx)
+    finally:
+        old_ctx.close()
     np.testing.assert_array_equal(d1, d1b)
     np.testing.assert_array_equal(e1, e1b)
     ev1 = eigvalsh_tridiagonal(d1.astype(np.float64), e1.astype(np.float64))
@@ -730,9 +783,6 @@ def test_gemm_large_product_takes_the_fp16_piece_path(gpu_ctx):
     """A product above the library's own size gate (>= 100 GFLOP, no dimension below 256) runs from fp16 pieces without any
     option set; sampled entries against fp64, next to the sgemm path of a second context (PMD_GEMM_SPLIT=0)."""
     torch = _t()
-    from localmd_amd._lib import Context
-    import os
-
     ctx = gpu_ctx
     m, n, k = 1024, 1536, 40000
     assert ctx.lib.pmd_gemm_split_active(ctx.handle, m, n, k) == 1
@@ -745,15 +795,7 @@ def test_gemm_large_product_takes_the_fp16_piece_path(gpu_ctx):
     rows = torch.arange(0, m, 37, device=ctx.device)
     ref = (a[rows].double() @ b.double()).cpu().numpy()
     err = np.linalg.norm(c[rows].cpu().numpy() - ref) / np.linalg.norm(ref)
-    old = os.environ.get("PMD_GEMM_SPLIT")
-    os.environ["PMD_GEMM_SPLIT"] = "0"
-    try:
-        ref_ctx = Context(0)
-    finally:
-        if old is None:
-            del os.environ["PMD_GEMM_SPLIT"]
-        else:
-            os.environ["PMD_GEMM_SPLIT"] = old
+    ref_ctx = context_under({"PMD_GEMM_SPLIT": "0"})
     try:
         c2 = torch.empty((m, n), device=ctx.device)
         ref_ctx.call("pmd_gemm", 0, 0, m, n, k, 1.0, P(a), k, P(b), n, 0.0, P(c2), n)

@@ -1,5 +1,29 @@
 """Shared helpers for the parity tests (test infrastructure only)."""
+import os
+
 import numpy as np
+
+
+def context_under(env, device_index=0):
+    """A Context of its own, created with the variables of ``env`` set (a value of None: unset).  The library reads its
+    PMD_* route switches when a context is created and keeps them for that context, so a test that wants a route gets it
+    from a context made for it; the environment is put back before this returns.  The caller closes the context."""
+    from localmd_amd._lib import Context
+
+    saved = {name: os.environ.get(name) for name in env}
+    try:
+        for name, value in env.items():
+            if value is None:
+                os.environ.pop(name, None)
+            else:
+                os.environ[name] = value
+        return Context(device_index)
+    finally:
+        for name, value in saved.items():
+            if value is None:
+                os.environ.pop(name, None)
+            else:
+                os.environ[name] = value
 
 
 class DeviceSource:
