@@ -58,7 +58,7 @@ int rccl_fail(pmd_ctx* ctx, rccl_api* api, const char* what, int rc) {
 
 }  // namespace
 
-int pmd_comm_unique_id_impl(void* out128) {
+extern "C" int pmd_comm_unique_id(void* out128) {
   rccl_api* api = load_rccl();
   if (!api || !out128) return PMD_ERR_UNSUPPORTED;
   pmd_nccl_id id;
@@ -67,7 +67,8 @@ int pmd_comm_unique_id_impl(void* out128) {
   return PMD_OK;
 }
 
-int pmd_comm_init_impl(pmd_ctx* ctx, const void* unique_id128, int rank, int world) {
+extern "C" int pmd_comm_init(pmd_ctx* ctx, const void* unique_id128, int rank, int world) {
+  CTX_CHECK(ctx);
   rccl_api* api = load_rccl();
   if (!api) return pmd_fail(ctx, PMD_ERR_UNSUPPORTED, "pmd_comm_init", "librccl could not be loaded");
   if (!unique_id128 || world < 1 || rank < 0 || rank >= world) return pmd_fail(ctx, PMD_ERR_ARG, "pmd_comm_init", "bad argument");
@@ -84,7 +85,8 @@ int pmd_comm_init_impl(pmd_ctx* ctx, const void* unique_id128, int rank, int wor
   return PMD_OK;
 }
 
-int pmd_comm_destroy_impl(pmd_ctx* ctx) {
+extern "C" int pmd_comm_destroy(pmd_ctx* ctx) {
+  CTX_CHECK(ctx);
   rccl_api* api = load_rccl();
   if (ctx->comm && api) {
     PMD_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -96,7 +98,9 @@ int pmd_comm_destroy_impl(pmd_ctx* ctx) {
 }
 
 // in-place sum over the ranks, enqueued on the context's stream
-int pmd_comm_all_reduce_f32_impl(pmd_ctx* ctx, float* buf, size_t count) {
+extern "C" int pmd_comm_all_reduce_f32(pmd_ctx* ctx, float* buf, size_t count) {
+  CTX_CHECK(ctx);
+  if (!buf && count) return pmd_fail(ctx, PMD_ERR_ARG, "pmd_comm_all_reduce_f32", "null pointer");
   rccl_api* api = load_rccl();
   if (!api || !ctx->comm) return pmd_fail(ctx, PMD_ERR_ARG, "pmd_comm_all_reduce_f32", "no communicator (pmd_comm_init)");
   if (count == 0) return PMD_OK;
@@ -105,7 +109,9 @@ int pmd_comm_all_reduce_f32_impl(pmd_ctx* ctx, float* buf, size_t count) {
 }
 
 // recv[r * bytes_per_rank ...] = rank r's send block, on every rank
-int pmd_comm_all_gather_impl(pmd_ctx* ctx, const void* send, void* recv, size_t bytes_per_rank) {
+extern "C" int pmd_comm_all_gather(pmd_ctx* ctx, const void* send, void* recv, size_t bytes_per_rank) {
+  CTX_CHECK(ctx);
+  if ((!send || !recv) && bytes_per_rank) return pmd_fail(ctx, PMD_ERR_ARG, "pmd_comm_all_gather", "null pointer");
   rccl_api* api = load_rccl();
   if (!api || !ctx->comm) return pmd_fail(ctx, PMD_ERR_ARG, "pmd_comm_all_gather", "no communicator (pmd_comm_init)");
   if (bytes_per_rank == 0) return PMD_OK;

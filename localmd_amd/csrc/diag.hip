@@ -158,15 +158,17 @@ __global__ void lag_image_kernel(const double* __restrict__ mom, long D, double 
 
 }  // namespace
 
-size_t pmd_diag_workspace_bytes_impl(long T, long D) {
+extern "C" size_t pmd_diag_workspace_bytes(long T, long D) {
   const int fpb = 1024;
   const long slices = (T + fpb - 1) / fpb;
   return (size_t)slices * 10 * (size_t)D * sizeof(double) + 4096;
 }
 
 // moments[10][D] (+)= neighbour moments of the frames given (A - B, B may be NULL); ref[D] = reference frame
-int pmd_neighbour_moments_impl(pmd_ctx* ctx, const float* A, const float* B, const float* ref, long T, int d1, int d2,
-                               int accumulate, double* moments, void* ws, size_t ws_bytes) {
+extern "C" int pmd_neighbour_moments(pmd_ctx* ctx, const float* A, const float* B, const float* ref, long T, int d1,
+                                     int d2, int accumulate, double* moments, void* ws, size_t ws_bytes) {
+  CTX_CHECK(ctx);
+  if (!A || !ref || !moments || !ws || d1 < 1 || d2 < 1) return pmd_fail(ctx, PMD_ERR_ARG, "pmd_neighbour_moments", "bad argument");
   pmd_prof_scope prof__(ctx, "diag_moments");
   if (T <= 0) return PMD_OK;
   const long D = (long)d1 * d2;
@@ -184,8 +186,10 @@ int pmd_neighbour_moments_impl(pmd_ctx* ctx, const float* A, const float* B, con
 }
 
 // moments[5][D] (+)= lag moments of the T resident frames: pairs (t, t - lag) for t in [lag, T), see lag_moments_kernel
-int pmd_lag_moments_impl(pmd_ctx* ctx, const float* A, const float* ref, long T, long D, int lag, int accumulate, double* moments,
-                         void* ws, size_t ws_bytes) {
+extern "C" int pmd_lag_moments(pmd_ctx* ctx, const float* A, const float* ref, long T, long D, int lag, int accumulate,
+                               double* moments, void* ws, size_t ws_bytes) {
+  CTX_CHECK(ctx);
+  if (!A || !ref || !moments || !ws || D < 1) return pmd_fail(ctx, PMD_ERR_ARG, "pmd_lag_moments", "bad argument");
   pmd_prof_scope prof__(ctx, "diag_moments");
   if (lag < 1 || lag >= T) return pmd_fail(ctx, PMD_ERR_ARG, "pmd_lag_moments", "need 1 <= lag < frames");
   const int fpb = 1024;
@@ -202,8 +206,11 @@ int pmd_lag_moments_impl(pmd_ctx* ctx, const float* A, const float* ref, long T,
   return PMD_OK;
 }
 
-int pmd_neighbour_image_impl(pmd_ctx* ctx, const double* num, const double* den, long T, int d1, int d2, int kind, int mode,
-                             double* out) {
+extern "C" int pmd_neighbour_image(pmd_ctx* ctx, const double* num, const double* den, long T, int d1, int d2, int kind,
+                                   int mode, double* out) {
+  CTX_CHECK(ctx);
+  if (!num || !out || T < 2 || (kind != 0 && kind != 1) || (mode != 0 && mode != 1))
+    return pmd_fail(ctx, PMD_ERR_ARG, "pmd_neighbour_image", "bad argument");
   pmd_prof_scope prof__(ctx, "diag_image");
   if (kind != 0 && !den) return pmd_fail(ctx, PMD_ERR_ARG, "pmd_neighbour_image", "kind 1 needs the moments of the normalising movie");
   const long D = (long)d1 * d2;
@@ -213,7 +220,9 @@ int pmd_neighbour_image_impl(pmd_ctx* ctx, const double* num, const double* den,
   return PMD_OK;
 }
 
-int pmd_lag_image_impl(pmd_ctx* ctx, const double* moments, long D, long n, double* out) {
+extern "C" int pmd_lag_image(pmd_ctx* ctx, const double* moments, long D, long n, double* out) {
+  CTX_CHECK(ctx);
+  if (!moments || !out || n < 1) return pmd_fail(ctx, PMD_ERR_ARG, "pmd_lag_image", "bad argument");
   pmd_prof_scope prof__(ctx, "diag_image");
   hipLaunchKernelGGL(lag_image_kernel, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, ctx->stream, moments, D, (double)n, out);
   PMD_LAUNCH_CHECK(ctx, "lag_image_kernel");

@@ -183,7 +183,7 @@ size_t pmd_diag_fused_workspace_bytes(int n, long D) {
 int pmd_diag_fused_accumulate(pmd_ctx* ctx, const void* Y, int elem, long ybase, const float* W, const void* ring, int lag,
                               long c0, int n, long T, int d1, int d2, const float* mean, float* ref, double* moments,
                               double* frame_ss, void* ws, size_t ws_bytes) {
-  if (!ctx) return PMD_ERR_ARG;
+  CTX_CHECK(ctx);
   const char* what = "pmd_diag_fused_accumulate";
   if (elem != PMD_ELEM_F32 && elem != PMD_ELEM_U16 && elem != PMD_ELEM_I16)
     return pmd_fail(ctx, PMD_ERR_ARG, what, "unknown element type");

@@ -81,8 +81,11 @@ __global__ __launch_bounds__(256) void transpose_affine_kernel(const float* __re
 
 }  // namespace
 
-int pmd_csr_rows_spmm_impl(pmd_ctx* ctx, const long* indptr, const int* indices, const float* data, const int* rows,
-                           long n_sel, const float* B, long ldb, int ncols, float* out, long ldo) {
+extern "C" int pmd_csr_rows_spmm(pmd_ctx* ctx, const int64_t* indptr, const int* indices, const float* data,
+                                 const int* rows, long n_sel, const float* B, long ldb, int ncols, float* out,
+                                 long ldo) {
+  CTX_CHECK(ctx);
+  if (!indptr || !indices || !data || !B || !out) return pmd_fail(ctx, PMD_ERR_ARG, "pmd_csr_rows_spmm", "null pointer");
   if (n_sel <= 0 || ncols <= 0) return PMD_OK;
   if (n_sel > 2147483647L) return pmd_fail(ctx, PMD_ERR_ARG, "pmd_csr_rows_spmm", "too many rows in one call");
   const bool vec = ncols >= 256 && ldb % 4 == 0 && ldo % 4 == 0 && ncols % 4 == 0 && ((uintptr_t)B & 15) == 0 && ((uintptr_t)out & 15) == 0;
@@ -101,8 +104,10 @@ int pmd_csr_rows_spmm_impl(pmd_ctx* ctx, const long* indptr, const int* indices,
   return PMD_OK;
 }
 
-int pmd_transpose_affine_impl(pmd_ctx* ctx, const float* src, long lds_, long rows, int cols, const float* scale,
-                              const float* shift, float* dst, long ldd) {
+extern "C" int pmd_transpose_affine(pmd_ctx* ctx, const float* src, long lds_, long rows, int cols, const float* scale,
+                                    const float* shift, float* dst, long ldd) {
+  CTX_CHECK(ctx);
+  if (!src || !dst) return pmd_fail(ctx, PMD_ERR_ARG, "pmd_transpose_affine", "null pointer");
   if (rows <= 0 || cols <= 0) return PMD_OK;
   const long gx = (rows + 31) / 32;
   const unsigned gy = (unsigned)((cols + 31) / 32);

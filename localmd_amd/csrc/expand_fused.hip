@@ -163,7 +163,7 @@ int pmd_group_expand(pmd_ctx* ctx, const float* C, long ldc, int n, int d1, int 
                      long n_patches, const long* patch_ptr, long n_entries, const long* entries, const int* qmap,
                      const float* A, const void* Y, int y_elem, long ldy, int n_panels, int panels, void* out,
                      int out_elem) {
-  if (!ctx) return PMD_ERR_ARG;
+  CTX_CHECK(ctx);
   const char* what = "pmd_group_expand";
   const long D = (long)d1 * d2;
   if (n < 0 || d1 < 1 || d2 < 1 || n_panels < 1 || n_panels > 3 || ldc < n || n_patches != (D + EX_PX - 1) / EX_PX)

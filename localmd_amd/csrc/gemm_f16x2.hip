@@ -24,6 +24,14 @@
 #include <map>
 #include <tuple>
 
+struct pmd_f16x2_op {
+  const _Float16* h1;
+  const _Float16* h2;
+  const _Float16* h3;   // third piece (2^-22), or NULL
+  long ld;
+  int e;
+};
+
 #define PMD_LT(ctx, call)                                                                               \
   do {                                                                                                  \
     hipblasStatus_t s__ = (call);                                                                       \
@@ -32,12 +40,6 @@
       snprintf(buf__, sizeof(buf__), "hipBLASLt status %d", (int)s__);                                  \
       return pmd_fail(ctx, PMD_ERR_BLAS, #call, buf__);                                                 \
     }                                                                                                   \
-  } while (0)
-
-#define RUN_OK(call)                 \
-  do {                               \
-    int rc__ = (call);               \
-    if (rc__ != PMD_OK) return rc__; \
   } while (0)
 
 namespace {
@@ -204,11 +206,16 @@ bool pmd_f16x2_wanted(const pmd_ctx* ctx, int m, int n, int k) {
   return 2.0 * m * (double)n * k >= r.gemm_split_min_gflop * 1e9;
 }
 
+extern "C" int pmd_gemm_split_active(pmd_ctx* ctx, int m, int n, int k) {
+  if (!ctx) return 0;
+  return pmd_f16x2_wanted(ctx, m, n, k) ? 1 : 0;
+}
+
 static inline int vec_ok(const void* p, int cols, long ld) { (void)cols; return (ld % 4 == 0) && (((uintptr_t)p & 15) == 0); }
 
-long pmd_f16x2_ld(int cols) { return pmd_round_up(cols, 8); }
+static long pmd_f16x2_ld(int cols) { return pmd_round_up(cols, 8); }
 
-size_t pmd_f16x2_bytes(int rows, int cols, int pieces) { return pieces * sizeof(_Float16) * (size_t)rows * pmd_f16x2_ld(cols) + 256; }
+static size_t pmd_f16x2_bytes(int rows, int cols, int pieces) { return pieces * sizeof(_Float16) * (size_t)rows * pmd_f16x2_ld(cols) + 256; }
 
 // Splits up to two operands with ONE read-back of their maxima.  h1 of operand i = (char*)buf_i, h2 follows it.
 // *usable = 0 when an operand cannot take the path (Inf / NaN, all zero, subnormal maximum): nothing was written then.
@@ -216,7 +223,7 @@ size_t pmd_f16x2_bytes(int rows, int cols, int pieces) { return pieces * sizeof(
 // cannot take the path (Inf / NaN, all zero, subnormal maximum).
 int pmd_f16x2_exponents(pmd_ctx* ctx, int count, const float* const* X, const int* rows, const int* cols, const long* ld, int* e_out,
                         int* usable) {
-  RUN_OK(ensure_state(ctx));
+  RUN(ensure_state(ctx));
   f16x2_state* st = state_of(ctx);
   *usable = 0;
   if (count < 1 || count > 2) return pmd_fail(ctx, PMD_ERR_ARG, "pmd_f16x2_exponents", "one or two operands");
@@ -296,9 +303,9 @@ int pmd_f16cat_b(pmd_ctx* ctx, const float* X, int kk, int cols, long ld, int e,
   return PMD_OK;
 }
 
-int pmd_f16x2_split(pmd_ctx* ctx, int count, const float* const* X, const int* rows, const int* cols, const long* ld, void* const* buf,
+static int pmd_f16x2_split(pmd_ctx* ctx, int count, const float* const* X, const int* rows, const int* cols, const long* ld, void* const* buf,
                     pmd_f16x2_op* ops, int* usable, int pieces) {
-  RUN_OK(ensure_state(ctx));
+  RUN(ensure_state(ctx));
   f16x2_state* st = state_of(ctx);
   *usable = 0;
   if (count < 1 || count > 2) return pmd_fail(ctx, PMD_ERR_ARG, "pmd_f16x2_split", "one or two operands");
@@ -374,13 +381,13 @@ static int plan_for(pmd_ctx* ctx, f16x2_state* st, int tA, int tB, int m, int n,
 // row-major C (m x n) = alpha op(A) op(B) + beta C from split operands (A: m x k or k x m, B: k x n or n x k; the pieces may
 // be sub-blocks of a split array: same leading dimension, pointers advanced).  *done = 0: no hipBLASLt kernel for the
 // shape, nothing was written.
-int pmd_f16x2_matmul(pmd_ctx* ctx, int tA, int tB, int m, int n, int k, float alpha, const pmd_f16x2_op& a, const pmd_f16x2_op& b, float beta,
+static int pmd_f16x2_matmul(pmd_ctx* ctx, int tA, int tB, int m, int n, int k, float alpha, const pmd_f16x2_op& a, const pmd_f16x2_op& b, float beta,
                      float* C, long ldc, int* done) {
-  RUN_OK(ensure_state(ctx));
+  RUN(ensure_state(ctx));
   f16x2_state* st = state_of(ctx);
   *done = 0;
   lt_plan* p = nullptr;
-  RUN_OK(plan_for(ctx, st, tA, tB, m, n, k, a.ld, b.ld, ldc, &p));
+  RUN(plan_for(ctx, st, tA, tB, m, n, k, a.ld, b.ld, ldc, &p));
   if (!p->ok) return PMD_OK;
   pmd_prof_scope prof__(ctx, "gemm_f16x2");
   const float a_main = alpha * ldexpf(1.f, a.e + b.e), a_small = alpha * ldexpf(1.f, a.e + b.e - 11), one = 1.f;
@@ -411,11 +418,11 @@ int pmd_f16x2_matmul(pmd_ctx* ctx, int tA, int tB, int m, int n, int k, float al
 // row-major C (m x n) = alpha A B + beta C with fp16 operands as they are (A: m x k, B: k x n)
 int pmd_f16_plain_matmul(pmd_ctx* ctx, int m, int n, int k, float alpha, const _Float16* A, long lda, const _Float16* B, long ldb, float beta,
                          float* C, long ldc, int* done) {
-  RUN_OK(ensure_state(ctx));
+  RUN(ensure_state(ctx));
   f16x2_state* st = state_of(ctx);
   *done = 0;
   lt_plan* p = nullptr;
-  RUN_OK(plan_for(ctx, st, 0, 0, m, n, k, lda, ldb, ldc, &p));
+  RUN(plan_for(ctx, st, 0, 0, m, n, k, lda, ldb, ldc, &p));
   if (!p->ok) return PMD_OK;
   pmd_prof_scope prof__(ctx, "gemm_f16x2");
   PMD_LT(ctx, hipblasLtMatmul(st->lt, p->desc, &alpha, B, p->la, A, p->lb, &beta, C, p->lc, C, p->lc, &p->algo, st->ws, st->ws_bytes, ctx->stream));
@@ -444,7 +451,8 @@ int pmd_split_scratch(pmd_ctx* ctx, size_t need, void** out) {
 }
 
 // frees the scratch when it is larger than `keep_bytes` (end of a decomposition: the next one may need the room for its movie)
-int pmd_split_scratch_trim(pmd_ctx* ctx, size_t keep_bytes) {
+extern "C" int pmd_scratch_trim(pmd_ctx* ctx, size_t keep_bytes) {
+  CTX_CHECK(ctx);
   if (ctx->split_ws && ctx->split_ws_bytes > keep_bytes) {
     PMD_HIP(ctx, hipStreamSynchronize(ctx->stream));
     (void)hipFree(ctx->split_ws);
@@ -461,7 +469,7 @@ int pmd_gemm_f16x2(pmd_ctx* ctx, int transA, int transB, int m, int n, int k, fl
   const int a_rows = transA ? k : m, a_cols = transA ? m : k, b_rows = transB ? n : k, b_cols = transB ? k : n;
   const size_t na = pmd_f16x2_bytes(a_rows, a_cols, 2), nb = pmd_f16x2_bytes(b_rows, b_cols, 2);
   void* w = nullptr;
-  RUN_OK(pmd_split_scratch(ctx, na + nb, &w));
+  RUN(pmd_split_scratch(ctx, na + nb, &w));
   if (!w) return PMD_OK;
   const float* X[2] = {A, B};
   const int rows[2] = {a_rows, b_rows}, cols[2] = {a_cols, b_cols};
@@ -469,7 +477,7 @@ int pmd_gemm_f16x2(pmd_ctx* ctx, int transA, int transB, int m, int n, int k, fl
   void* buf[2] = {w, (char*)w + na};
   pmd_f16x2_op ops[2];
   int usable = 0;
-  RUN_OK(pmd_f16x2_split(ctx, 2, X, rows, cols, ld, buf, ops, &usable, 2));
+  RUN(pmd_f16x2_split(ctx, 2, X, rows, cols, ld, buf, ops, &usable, 2));
   if (!usable) return PMD_OK;
   return pmd_f16x2_matmul(ctx, transA, transB, m, n, k, alpha, ops[0], ops[1], beta, C, ldc, done);
 }

@@ -9,12 +9,6 @@
 #include <cmath>
 #include <vector>
 
-#define RUN(call)                 \
-  do {                            \
-    int rc__ = (call);            \
-    if (rc__ != PMD_OK) return rc__; \
-  } while (0)
-
 #define PMD_BLAS(ctx, call)                                                     \
   do {                                                                          \
     rocblas_status s__ = (call);                                                \
@@ -40,7 +34,7 @@ __global__ void sum_partials_kernel(const float* __restrict__ part, long mn, int
 
 // Length of one fp32 accumulation chain in the library's GEMM-shaped products (PMD_GEMM_KCHUNK overrides; 0 = whole k):
 // 1024 up to k = 16384, 2048 beyond (the output is re-read once per chunk: 12 % / 6 % of the product's time).
-int pmd_gemm_k_chunk(const pmd_ctx* ctx, int k) {
+static int pmd_gemm_k_chunk(const pmd_ctx* ctx, int k) {
   const int forced = ctx->routes.gemm_kchunk;
   if (forced == 0) return k;
   if (forced > 0) return forced;
@@ -48,7 +42,7 @@ int pmd_gemm_k_chunk(const pmd_ctx* ctx, int k) {
   return k <= 16384 ? 1024 : 2048;
 }
 
-bool pmd_is_host_pointer(const void* p) {
+static bool pmd_is_host_pointer(const void* p) {
   hipPointerAttribute_t attr;
   if (hipPointerGetAttributes(&attr, p) != hipSuccess) { (void)hipGetLastError(); return false; }
   return attr.type == hipMemoryTypeHost;
@@ -127,6 +121,12 @@ int pmd_gemm_rm(pmd_ctx* ctx, int transA, int transB, int m, int n, int k, float
   return PMD_OK;
 }
 
+extern "C" int pmd_gemm(pmd_ctx* ctx, int transA, int transB, int m, int n, int k, float alpha, const float* A, long lda, const float* B,
+                        long ldb, float beta, float* C, long ldc) {
+  CTX_CHECK(ctx);
+  return pmd_gemm_rm(ctx, transA, transB, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc);
+}
+
 // ---------------------------------------------------------------- weighted tile bases ------
 // Uw[tile][c][q] = Ut[tile][c][q] * w[q] / cumw[pix[tile][q]] for c < ranks[tile], else 0
 // (decomposition.py:812-816, :847-853).
@@ -144,8 +144,9 @@ __global__ void weight_tiles_kernel(const float* __restrict__ Ut, long tile_stri
   }
 }
 
-int pmd_launch_weight_tiles(pmd_ctx* ctx, const float* Ut, int dpad, const int* pix, int d, const float* w,
-                            const float* cumw, const int* ranks, float* Uw, int n_tiles) {
+extern "C" int pmd_weight_tiles(pmd_ctx* ctx, const float* Ut, int dpad, const int* pix, int d, const float* w,
+                                const float* cumw, const int* ranks, float* Uw, int n_tiles) {
+  CTX_CHECK(ctx);
   pmd_prof_scope prof__(ctx, "weight_tiles");
   for (int t0 = 0; t0 < n_tiles; t0 += 32768) {
     const int tn = (n_tiles - t0 < 32768) ? n_tiles - t0 : 32768;
@@ -168,8 +169,10 @@ __global__ void compact_rows_kernel(const float* __restrict__ Out, long tile_str
       Z[(off + c) * ldz + t] = Out[(long)tile * tile_stride + (long)c * ldo + t];
 }
 
-int pmd_launch_compact_rows(pmd_ctx* ctx, const float* Out, long tile_stride, long ldo, const int* col_off,
-                            const int* ranks, int T, float* Z, long ldz, int n_tiles) {
+extern "C" int pmd_compact_rows(pmd_ctx* ctx, const float* Out, long ldo, const int* col_off, const int* ranks, int T,
+                                float* Z, long ldz, int n_tiles) {
+  CTX_CHECK(ctx);
+  const long tile_stride = 64L * ldo;
   pmd_prof_scope prof__(ctx, "compact_rows");
   for (int t0 = 0; t0 < n_tiles; t0 += 32768) {
     const int tn = (n_tiles - t0 < 32768) ? n_tiles - t0 : 32768;
@@ -283,9 +286,10 @@ __global__ __launch_bounds__(256) void gram_bgbg_kernel(const float* __restrict_
   }
 }
 
-int pmd_gram_u_impl(pmd_ctx* ctx, const float* Uw, int dpad, int b1, int b2, const int* pix, const int* pairs,
-                    int n_pairs, const int* origins, const int* col_off, const int* ranks, int n_tiles, int Rt,
-                    const float* basis, long D, int K, float* G, long ldg) {
+extern "C" int pmd_gram_u(pmd_ctx* ctx, const float* Uw, int dpad, int b1, int b2, const int* pix, const int* pairs,
+                          int n_pairs, const int* origins, const int* col_off, const int* ranks, int n_tiles, int Rt,
+                          const float* basis, long D, int K, float* G, long ldg) {
+  CTX_CHECK(ctx);
   pmd_prof_scope prof__(ctx, "gram_u");
   const long R = Rt + K;
   PMD_HIP(ctx, hipMemsetAsync(G, 0, (size_t)R * ldg * sizeof(float), ctx->stream));
@@ -359,7 +363,7 @@ static int launch_transpose(pmd_ctx* ctx, const float* src, long lds_, int rows,
 // G: R x R (overwritten).  M: R x m right matrix (row-major, ldm) or NULL for the identity
 // (reference: right_mat = v if R > v.shape[1] else eye(R)).  P_out: R x R' (ldp >= m).
 // Host sync: the eigenvalues come back to count R' (reference: good_components = eig_vals > 0).
-size_t pmd_orthogonalize_workspace_bytes_impl(int R, int m, int has_m) {
+extern "C" size_t pmd_orthogonalize_workspace_bytes(int R, int m, int has_m) {
   size_t b = 0;
   b += (size_t)m * sizeof(float) * 4 + (size_t)m * sizeof(int) + 4096;  // w, work, scale, perm, info
   if (has_m) b += (size_t)R * m * sizeof(float) + (size_t)m * m * sizeof(float);  // GM, C
@@ -367,8 +371,9 @@ size_t pmd_orthogonalize_workspace_bytes_impl(int R, int m, int has_m) {
   return b + 8192;
 }
 
-int pmd_orthogonalize_impl(pmd_ctx* ctx, float* G, int R, const float* M, int m, long ldm, float* P_out, long ldp,
-                           int* rprime_out, void* ws, size_t ws_bytes) {
+extern "C" int pmd_orthogonalize(pmd_ctx* ctx, float* G, int R, const float* M, int m, long ldm, float* P_out, long ldp,
+                                 int* rprime_out, void* ws, size_t ws_bytes) {
+  CTX_CHECK(ctx);
   pmd_arena ar(ws, ws_bytes);
   float* w = ar.take_n<float>(m);
   float* work = ar.take_n<float>(m);
@@ -432,15 +437,17 @@ int pmd_orthogonalize_impl(pmd_ctx* ctx, float* G, int R, const float* M, int m,
 // projected_svd (decomposition.py:1042-1060) with fewer_rows (:1089-1099) / fewer_columns
 // (:1128-1137).  V: n1 x n2 (row-major, overwritten when n1 <= n2 is false? no: preserved).
 // Outputs: R_out (rows_p x nk), s_out (nk), Vt_out (nk x n2), nk = min(n1, n2).
-size_t pmd_projected_svd_workspace_bytes_impl(int rows_p, int n1, int n2) {
+extern "C" size_t pmd_projected_svd_workspace_bytes(int rows_p, int n1, int n2) {
   const size_t nk = (size_t)std::min(n1, n2);
   size_t b = (nk + 4) * nk * sizeof(float) * 2 + nk * (sizeof(float) * 5 + sizeof(int)) + 8192;
   if (n1 > n2) b += (size_t)n1 * n2 * sizeof(float);
   return b + 8192;
 }
 
-int pmd_projected_svd_impl(pmd_ctx* ctx, const float* P, int rows_p, long ldp, const float* V, int n1, int n2, long ldv,
-                           float* R_out, long ldr, float* s_out, float* Vt_out, long ldvt, void* ws, size_t ws_bytes) {
+extern "C" int pmd_projected_svd(pmd_ctx* ctx, const float* P, int rows_p, long ldp, const float* V, int n1, int n2,
+                                 long ldv, float* R_out, long ldr, float* s_out, float* Vt_out, long ldvt, void* ws,
+                                 size_t ws_bytes) {
+  CTX_CHECK(ctx);
   const int nk = std::min(n1, n2);
   pmd_arena ar(ws, ws_bytes);
   const long ldc = pmd_round_up(nk, 4);  // the library's own tridiagonalisation wants 16-byte aligned rows
@@ -532,8 +539,10 @@ static int psvd_gram_rows(pmd_ctx* ctx, const float* V, int n1, int n2, long ldv
   return PMD_OK;
 }
 
-int pmd_psvd_vp_gram_impl(pmd_ctx* ctx, const float* Et, int rp, int m, long lde, const float* W1, int nc, long ldw, int et_lower,
-                          float* Vp, long ldv, float* C, long ldc) {
+extern "C" int pmd_psvd_vp_gram(pmd_ctx* ctx, const float* Et, int rp, int m, long lde, const float* W1, int nc,
+                                long ldw, int et_lower, float* Vp, long ldv, float* C, long ldc) {
+  CTX_CHECK(ctx);
+  if (rp < 1 || m < rp || nc < 0 || ldc < rp) return pmd_fail(ctx, PMD_ERR_ARG, "pmd_psvd_vp_gram", "bad shape");
   if (nc > 0) {
     // (a triangular product does half the flops in fp32; the full product from fp16 pieces is faster still where it applies)
     const bool tri = et_lower && rp == m && !pmd_f16x2_wanted(ctx, rp, nc, m);
@@ -549,14 +558,17 @@ int pmd_psvd_vp_gram_impl(pmd_ctx* ctx, const float* Et, int rp, int m, long lde
   return psvd_gram_rows(ctx, Vp, rp, nc, ldv, C, ldc);
 }
 
-size_t pmd_psvd_finish_workspace_bytes_impl(int rp) {
+extern "C" size_t pmd_psvd_finish_workspace_bytes(int rp) {
   return (size_t)rp * rp * sizeof(float) + (size_t)rp * (sizeof(float) * 5 + sizeof(int)) + 16384;
 }
 
 // C: summed Gram matrix (rp x rp, ld ldc >= round_up(rp, 4); overwritten), Vp: this rank's columns (rp x nc).
 // Outputs: W_out (rp x rp, row c' = component c' of the left vectors, i.e. W[c'][c]), s_out (rp), Vt_out (rp x nc).
-int pmd_psvd_finish_impl(pmd_ctx* ctx, float* C, long ldc, int rp, const float* Vp, int nc, long ldv, float* W_out, long ldw, float* s_out,
-                         float* Vt_out, long ldvt, void* ws, size_t ws_bytes) {
+extern "C" int pmd_psvd_finish(pmd_ctx* ctx, float* C, long ldc, int rp, const float* Vp, int nc, long ldv,
+                               float* W_out, long ldw, float* s_out, float* Vt_out, long ldvt, void* ws,
+                               size_t ws_bytes) {
+  CTX_CHECK(ctx);
+  if (rp < 1 || nc < 0 || ldc < rp) return pmd_fail(ctx, PMD_ERR_ARG, "pmd_psvd_finish", "bad shape");
   pmd_arena ar(ws, ws_bytes);
   float* Wt = ar.take_n<float>((size_t)rp * rp);
   float* w = ar.take_n<float>(rp);
@@ -611,13 +623,14 @@ __global__ void block_basis_kernel(const float* __restrict__ basis, long D, int 
   for (int k = 0; k < PMD_RPAD; ++k) At[blk * PMD_RPAD * BGP_BLK + (long)k * BGP_BLK + q] = (c < D && k < K) ? basis[c * kstride + k] : 0.f;
 }
 
-size_t pmd_bg_project_workspace_bytes_impl(long D, int T) {
+extern "C" size_t pmd_bg_project_workspace_bytes(long D, int T) {
   const size_t nblk = (size_t)((D + BGP_BLK - 1) / BGP_BLK);
   return nblk * 64 * BGP_BLK * sizeof(float) + nblk * 64 * (size_t)pmd_time_ld(T) * sizeof(float) + 8192;
 }
 
-int pmd_bg_project_impl(pmd_ctx* ctx, const float* xs, long D, int T, long ld, const float* basis, int K, float* out,
-                        long ldo, void* ws, size_t ws_bytes) {
+extern "C" int pmd_bg_project(pmd_ctx* ctx, const float* xs, long D, int T, long ld, const float* basis, int K,
+                              float* out, long ldo, void* ws, size_t ws_bytes) {
+  CTX_CHECK(ctx);
   if (K < 1) return pmd_fail(ctx, PMD_ERR_ARG, "pmd_bg_project", "background rank must be >= 1");
   const int nblk = (int)((D + BGP_BLK - 1) / BGP_BLK);
   const long ldt = pmd_time_ld(T);
@@ -630,10 +643,9 @@ int pmd_bg_project_impl(pmd_ctx* ctx, const float* xs, long D, int T, long ld, c
     const int kc = (K - k0 < 64) ? K - k0 : 64;
     hipLaunchKernelGGL(block_basis_kernel, dim3(nblk * (BGP_BLK / 256)), dim3(256), 0, ctx->stream, basis + k0, D, kc, At, K);
     PMD_LAUNCH_CHECK(ctx, "block_basis_kernel");
-    ctx->atx_rows = kc;   // (<= 16 columns - the default rank is 15 - run on one row tile: a quarter of the MFMA work)
-    const int rc_atx = pmd_launch_tile_atx(ctx, xs, ld, nullptr, 0, BGP_BLK, BGP_BLK, At, 64L * BGP_BLK, BGP_BLK, part, 64L * ldt, ldt, nblk, T, 8);
-    ctx->atx_rows = 0;
-    RUN(rc_atx);
+    // (<= 16 columns - the default rank is 15 - run on one row tile: a quarter of the MFMA work)
+    RUN(pmd_launch_tile_atx(ctx, xs, ld, nullptr, 0, BGP_BLK, BGP_BLK, At, 64L * BGP_BLK, BGP_BLK, part, 64L * ldt, ldt, nblk, T, 8,
+                            {"tile_atx", kc}));
     // sum the block partials row by row into out[k][0:T]
     for (int k = 0; k < kc; ++k)
       RUN(pmd_launch_reduce_slices(ctx, part + (long)k * ldt, 0, 64L * ldt, nblk, T, out + (long)(k0 + k) * ldo, 0, 1));
@@ -893,9 +905,11 @@ __global__ __launch_bounds__(256) void gram_apply_mfma_kernel(const float* __res
 }
 
 // blocks: Gblk [n_pairs][64][64], Gbg [n_tiles][64][64], Gstrip [K][ldgs] (ldgs >= Rt + K)
-int pmd_gram_blocks_impl(pmd_ctx* ctx, const float* Uw, int dpad, int b1, int b2, const int* pix, const int* pairs,
-                         int n_pairs, const int* origins, const int* col_off, const int* ranks, int n_tiles, int Rt,
-                         const float* basis, long D, int K, float* Gblk, float* Gbg, float* Gstrip, long ldgs) {
+extern "C" int pmd_gram_blocks(pmd_ctx* ctx, const float* Uw, int dpad, int b1, int b2, const int* pix,
+                               const int* pairs, int n_pairs, const int* origins, const int* col_off, const int* ranks,
+                               int n_tiles, int Rt, const float* basis, long D, int K, float* Gblk, float* Gbg,
+                               float* Gstrip, long ldgs) {
+  CTX_CHECK(ctx);
   pmd_prof_scope prof__(ctx, "gram_blocks");
   if (n_pairs > 0) {
     hipLaunchKernelGGL(gram_pair_blocks_kernel, dim3(n_pairs), dim3(256), 0, ctx->stream, Uw, dpad, b1, pairs, origins,
@@ -918,9 +932,10 @@ int pmd_gram_blocks_impl(pmd_ctx* ctx, const float* Uw, int dpad, int b1, int b2
 }
 
 // GM = G M for the block-sparse G (rows of the K background columns via one small GEMM).
-int pmd_gram_apply_impl(pmd_ctx* ctx, const float* Gblk, const float* Gbg, const float* Gstrip, long ldgs,
-                        const int* nbr_ptr, const int* nbr, const int* col_off, const int* ranks, int n_tiles, int Rt,
-                        int K, int max_rank, const float* M, long ldm, int ncols, float* GM, long ldgm) {
+extern "C" int pmd_gram_apply(pmd_ctx* ctx, const float* Gblk, const float* Gbg, const float* Gstrip, long ldgs,
+                              const int* nbr_ptr, const int* nbr, const int* col_off, const int* ranks, int n_tiles,
+                              int Rt, int K, int max_rank, const float* M, long ldm, int ncols, float* GM, long ldgm) {
+  CTX_CHECK(ctx);
   {
     pmd_prof_scope prof__(ctx, "gram_apply");
     dim3 grid((ncols + 255) / 256, n_tiles);
@@ -1025,8 +1040,9 @@ __global__ void csr_fill_kernel(int d1, int d2, int order_f, int b1, const int* 
   if (zeros) atomicAdd(zero_count, zeros);
 }
 
-int pmd_csr_count_impl(pmd_ctx* ctx, int d1, int d2, int order_f, const int* cover1, const int* cover2, int n2,
-                       const int* ranks, int K, long* row_nnz) {
+extern "C" int pmd_csr_count(pmd_ctx* ctx, int d1, int d2, int order_f, const int* cover1, const int* cover2, int n2,
+                             const int* ranks, int K, long* row_nnz) {
+  CTX_CHECK(ctx);
   pmd_prof_scope prof__(ctx, "csr_assembly");
   const long D = (long)d1 * d2;
   hipLaunchKernelGGL(csr_count_kernel, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, ctx->stream, d1, d2, order_f,
@@ -1035,10 +1051,12 @@ int pmd_csr_count_impl(pmd_ctx* ctx, int d1, int d2, int order_f, const int* cov
   return PMD_OK;
 }
 
-int pmd_csr_fill_impl(pmd_ctx* ctx, int d1, int d2, int order_f, int b1, const int* cover1, const int* cover2,
-                      const int* orig1, const int* orig2, int n2, const int* ranks, const int* col_off, const float* Ut,
-                      int dpad, const float* w, const double* inv_cumw, const float* basis, int K, int Rt,
-                      const long* indptr, double* data, int* indices, int* zero_count, int rpad) {
+extern "C" int pmd_csr_fill(pmd_ctx* ctx, int d1, int d2, int order_f, int b1, const int* cover1, const int* cover2,
+                            const int* orig1, const int* orig2, int n2, const int* ranks, const int* col_off,
+                            const float* Ut, int dpad, const float* w, const double* inv_cumw, const float* basis,
+                            int K, int Rt, const long* indptr, double* data, int* indices, int* zero_count, int rpad) {
+  CTX_CHECK(ctx);
+  if (rpad < 64 || rpad % 64) return pmd_fail(ctx, PMD_ERR_ARG, "pmd_csr_fill", "rpad must be a positive multiple of 64");
   pmd_prof_scope prof__(ctx, "csr_assembly");
   const long D = (long)d1 * d2;
   PMD_HIP(ctx, hipMemsetAsync(zero_count, 0, sizeof(int), ctx->stream));
@@ -1054,12 +1072,14 @@ int pmd_csr_fill_impl(pmd_ctx* ctx, int d1, int d2, int order_f, int b1, const i
 //   pmd_orthogonalize_factored: C = M^T (G M) -> Et (R' x m), rows = eigenvectors / sqrt(lambda)
 //   pmd_projected_svd_factored: V = Et (M^T Z); SVD of V; R_out = M (Et^T W)
 // =============================================================================================
-size_t pmd_orthogonalize_factored_workspace_bytes_impl(int m) {
+extern "C" size_t pmd_orthogonalize_factored_workspace_bytes(int m) {
   return (size_t)m * m * sizeof(float) + (size_t)m * (3 * sizeof(float) + sizeof(int)) + 8192;
 }
 
-int pmd_orthogonalize_factored_impl(pmd_ctx* ctx, const float* M, int Rc, int m, long ldm, const float* GM, long ldgm,
-                                    float* Et_out, long lde, int* rprime_out, void* ws, size_t ws_bytes) {
+extern "C" int pmd_orthogonalize_factored(pmd_ctx* ctx, const float* M, int Rc, int m, long ldm, const float* GM,
+                                          long ldgm, float* Et_out, long lde, int* rprime_out, void* ws,
+                                          size_t ws_bytes) {
+  CTX_CHECK(ctx);
   pmd_arena ar(ws, ws_bytes);
   float* C = ar.take_n<float>((size_t)m * m);
   float* w = ar.take_n<float>(m);
@@ -1103,26 +1123,27 @@ int pmd_orthogonalize_factored_impl(pmd_ctx* ctx, const float* M, int Rc, int m,
   return PMD_OK;
 }
 
-size_t pmd_projected_svd_factored_workspace_bytes_impl(int Rc, int m, int rp, int T) {
+extern "C" size_t pmd_projected_svd_factored_workspace_bytes(int Rc, int m, int rp, int T) {
   return (size_t)m * T * sizeof(float) + (size_t)rp * T * sizeof(float) + (size_t)m * rp * sizeof(float) +
-         (size_t)m * pmd_round_up(Rc, 64) * sizeof(float) + pmd_projected_svd_workspace_bytes_impl(1, rp, T) + 16384;
+         (size_t)m * pmd_round_up(Rc, 64) * sizeof(float) + pmd_projected_svd_workspace_bytes(1, rp, T) + 16384;
 }
 
 // M: Rc x m; Et: rp x m; Z: Rc x T.  Outputs R_out (Rc x nk), s (nk), Vt (nk x T), nk = min(rp, T);
 // Vp_out (rp x T, optional, may be NULL) receives V = P^T Z.
-int pmd_projected_svd_factored_impl(pmd_ctx* ctx, const float* M, int Rc, int m, long ldm, const float* Et, int rp,
-                                    long lde, const float* Z, int T, long ldz, float* R_out, long ldr, float* s_out,
-                                    float* Vt_out, long ldvt, float* Vp_out, long ldvp, float* X1_out,
-                                    const float* W1_in, int et_lower, void* ws, size_t ws_bytes) {
+extern "C" int pmd_projected_svd_factored(pmd_ctx* ctx, const float* M, int Rc, int m, long ldm, const float* Et,
+                                          int rp, long lde, const float* Z, int T, long ldz, float* R_out, long ldr,
+                                          float* s_out, float* Vt_out, long ldvt, float* Vp_out, long ldvp,
+                                          float* X1_out, const float* W1_in, int et_lower, void* ws, size_t ws_bytes) {
+  CTX_CHECK(ctx);
   if (rp > T) return pmd_fail(ctx, PMD_ERR_UNSUPPORTED, "pmd_projected_svd_factored", "needs R' <= T");
   pmd_arena ar(ws, ws_bytes);
   float* W1 = ar.take_n<float>((size_t)m * T);
   float* Vp = Vp_out ? Vp_out : ar.take_n<float>((size_t)rp * T);
   const long ldv = Vp_out ? ldvp : T;
   float* X1 = X1_out ? X1_out : ar.take_n<float>((size_t)m * rp);
-  const long ldt = pmd_round_up(Rc, 64);   // (rows of the transposed copy on 256-byte boundaries, see pmd_gram_mtgm_ld_impl)
+  const long ldt = pmd_round_up(Rc, 64);   // (rows of the transposed copy on 256-byte boundaries, see pmd_gram_mtgm_ld)
   float* Mt = ar.take_n<float>((size_t)m * ldt);
-  const size_t sub_bytes = pmd_projected_svd_workspace_bytes_impl(1, rp, T);
+  const size_t sub_bytes = pmd_projected_svd_workspace_bytes(1, rp, T);
   void* sub = ar.take(sub_bytes);
   if (ar.overflow) return pmd_fail(ctx, PMD_ERR_WORKSPACE, "pmd_projected_svd_factored", "workspace too small");
   // M^T Z as a plain (non-transposed) product of an explicit copy of M^T: rocBLAS' transposed-A kernels
@@ -1149,7 +1170,7 @@ int pmd_projected_svd_factored_impl(pmd_ctx* ctx, const float* M, int Rc, int m,
   }
   // SVD of V with the identity as projection: the "R" it returns is W (rp x rp), reuse W1's memory
   float* Wmat = W1;  // rp x rp  (rp <= m, T)
-  RUN(pmd_projected_svd_impl(ctx, nullptr, 0, 0, Vp, rp, T, ldv, Wmat, rp, s_out, Vt_out, ldvt, sub, sub_bytes));
+  RUN(pmd_projected_svd(ctx, nullptr, 0, 0, Vp, rp, T, ldv, Wmat, rp, s_out, Vt_out, ldvt, sub, sub_bytes));
   // R = M (Et^T W)
   if (tri_any && !pmd_f16x2_wanted(ctx, m, rp, rp)) {
     // row-major X1 = Et^T W  <=>  column-major X1^T = W^T (Et^T)^T
@@ -1358,8 +1379,8 @@ __global__ void tril_mask_kernel(float* __restrict__ A, long ld, int n) {
     if (j > i) A[(long)i * ld + j] = 0.f;
 }
 
-size_t pmd_orthogonalize_chol_workspace_bytes_impl(int Rc, int m) {
-  return std::max(pmd_gram_mtgm_workspace_bytes_impl(Rc, m), pmd_chol_inverse_workspace_bytes_impl(m)) + ((size_t)m + CHOL_NB) * CHOL_NB * sizeof(float) + 16384;
+extern "C" size_t pmd_orthogonalize_chol_workspace_bytes(int Rc, int m) {
+  return std::max(pmd_gram_mtgm_workspace_bytes(Rc, m), pmd_chol_inverse_workspace_bytes(m)) + ((size_t)m + CHOL_NB) * CHOL_NB * sizeof(float) + 16384;
 }
 
 // C (row-major lower block triangle, the part the Cholesky step reads) = M^T GM over `rows` rows of both.
@@ -1367,14 +1388,15 @@ size_t pmd_orthogonalize_chol_workspace_bytes_impl(int Rc, int m) {
 // The transposed copy M^T (m x rows) at the start of the workspace has leading dimension pmd_gram_mtgm_ld(rows): a multiple of
 // 64 floats.  (With ld = rows = 113 305 at BASELINE config 4 every row of the copy started off a 16-byte boundary and rocBLAS
 // fell back to element-wise loads: 51 TFLOP/s for this product instead of 130.)
-long pmd_gram_mtgm_ld_impl(int rows) { return pmd_round_up(rows, 64); }
-size_t pmd_gram_mtgm_workspace_bytes_impl(int rows, int m) { return (size_t)m * pmd_gram_mtgm_ld_impl(rows) * sizeof(float) + 4096; }
+extern "C" long pmd_gram_mtgm_ld(int rows) { return pmd_round_up(rows, 64); }
+extern "C" size_t pmd_gram_mtgm_workspace_bytes(int rows, int m) { return (size_t)m * pmd_gram_mtgm_ld(rows) * sizeof(float) + 4096; }
 
-int pmd_gram_mtgm_impl(pmd_ctx* ctx, const float* M, int rows, int m, long ldm, const float* GM, long ldgm, float* C,
-                       long ldc, void* ws, size_t ws_bytes) {
+extern "C" int pmd_gram_mtgm(pmd_ctx* ctx, const float* M, int rows, int m, long ldm, const float* GM, long ldgm,
+                             float* C, long ldc, void* ws, size_t ws_bytes) {
+  CTX_CHECK(ctx);
   if (rows <= 0) return PMD_OK;
   pmd_arena ar(ws, ws_bytes);
-  const long ldt = pmd_gram_mtgm_ld_impl(rows);
+  const long ldt = pmd_gram_mtgm_ld(rows);
   float* Mt = ar.take_n<float>((size_t)m * ldt);
   if (ar.overflow) return pmd_fail(ctx, PMD_ERR_WORKSPACE, "pmd_gram_mtgm", "workspace too small");
   // row blocks C[i0:i0+bs, 0:i0+bs] = Mt[i0:i0+bs, :] GM[:, 0:i0+bs]  (3/5 of the flops at 5 blocks)
@@ -1483,11 +1505,13 @@ __global__ void chol_last_pivot_kernel(double* __restrict__ U, long ld, int m, i
 }  // namespace
 
 // In place: C = U_c^T U_c (row-major lower triangle read) -> Et = U_c^{-T} (row-major lower, rest zeroed).
-size_t pmd_chol_inverse_workspace_bytes_impl(int m) {
+extern "C" size_t pmd_chol_inverse_workspace_bytes(int m) {
   return ((size_t)m + CHOL_NB) * CHOL_NB * sizeof(float) + (m <= CHOL_F64_MAX ? (size_t)m * m * sizeof(double) + 64 : 0) + 8192;
 }
 
-int pmd_chol_inverse_impl(pmd_ctx* ctx, float* C, int m, long ldc, int abs_last_pivot, int* ok_host, void* ws, size_t ws_bytes) {
+extern "C" int pmd_chol_inverse(pmd_ctx* ctx, float* C, int m, long ldc, int abs_last_pivot, int* ok_host, void* ws,
+                                size_t ws_bytes) {
+  CTX_CHECK(ctx);
   pmd_arena ar(ws, ws_bytes);
   int* info = ar.take_n<int>(4);
   float* chol_tmp = ar.take_n<float>((size_t)m * CHOL_NB);
@@ -1548,12 +1572,14 @@ int pmd_chol_inverse_impl(pmd_ctx* ctx, float* C, int m, long ldc, int abs_last_
   return PMD_OK;
 }
 
-int pmd_orthogonalize_chol_impl(pmd_ctx* ctx, const float* M, int Rc, int m, long ldm, const float* GM, long ldgm,
-                                float* Et_out, long lde, int* ok_host, void* ws, size_t ws_bytes) {
-  RUN(pmd_gram_mtgm_impl(ctx, M, Rc, m, ldm, GM, ldgm, Et_out, lde, ws, ws_bytes));
-  return pmd_chol_inverse_impl(ctx, Et_out, m, lde, 0, ok_host, ws, ws_bytes);
+extern "C" int pmd_orthogonalize_chol(pmd_ctx* ctx, const float* M, int Rc, int m, long ldm, const float* GM, long ldgm,
+                                      float* Et_out, long lde, int* ok_host, void* ws, size_t ws_bytes) {
+  CTX_CHECK(ctx);
+  RUN(pmd_gram_mtgm(ctx, M, Rc, m, ldm, GM, ldgm, Et_out, lde, ws, ws_bytes));
+  return pmd_chol_inverse(ctx, Et_out, m, lde, 0, ok_host, ws, ws_bytes);
 }
 
-int pmd_transpose_impl(pmd_ctx* ctx, const float* src, long lds_, int rows, int cols, float* dst, long ldd) {
+extern "C" int pmd_transpose(pmd_ctx* ctx, const float* src, long lds_, int rows, int cols, float* dst, long ldd) {
+  CTX_CHECK(ctx);
   return launch_transpose(ctx, src, lds_, rows, cols, dst, ldd);
 }

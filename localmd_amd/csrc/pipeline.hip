@@ -4,7 +4,7 @@
 #include "pmd_internal.h"
 #include <algorithm>
 
-int pmd_tile_dpad(int d) {
+extern "C" int pmd_tile_dpad(int d) {
   if (d > 65536) return -1;
   if (d > 1024) return (int)pmd_round_up(d, 1024);   // tile_atx splits the pixel axis over the grid in slices of 1024
   pmd_dvariant v;
@@ -12,13 +12,7 @@ int pmd_tile_dpad(int d) {
   return v.dpad;
 }
 
-long pmd_time_ld(long t) { return pmd_round_up(t, 64) + PMD_LD_SLACK; }
-
-#define RUN(call)                 \
-  do {                            \
-    int rc__ = (call);            \
-    if (rc__ != PMD_OK) return rc__; \
-  } while (0)
+extern "C" long pmd_time_ld(long t) { return pmd_round_up(t, 64) + PMD_LD_SLACK; }
 
 // Orthonormal basis of the sketch's column space (jnp.linalg.qr at decomposition.py:64 / pmd_loader.py:58).  Householder QR
 // in LDS while the P x l matrix fits a workgroup's 160 KB (every default configuration); beyond that - large tiles with
@@ -93,7 +87,9 @@ static int plan_tiles(pmd_arena& ar, tiles_plan& p, int n, int d, int P, int r, 
   return PMD_OK;
 }
 
-size_t pmd_tiles_workspace_bytes_impl(int n, int d, int P, int r, int a, int t_crop, long ldv, long n_rows) {
+extern "C" size_t pmd_tiles_workspace_bytes(int n, int b1, int b2, int P, int r, int a, int t_crop, long ldv,
+                                            long n_rows) {
+  const int d = b1 * b2;
   pmd_arena ar((void*)0x1000, ~size_t(0) >> 1);
   tiles_plan p;
   if (plan_tiles(ar, p, n, d, P, r, a, t_crop, ldv, n_rows) != PMD_OK) return 0;
@@ -149,9 +145,7 @@ static int tiles_decompose_wide(pmd_ctx* ctx, const tiles_plan& p, const float* 
     RUN(pmd_launch_wide_eig(ctx, p.gpart, 1, rp, p.nref, 0, 0.0, p.nmat, p.lam, n, p.eig_ws, p.eig_ws_bytes));
     RUN(pmd_launch_wide_rowmix(ctx, p.qt, srP, p.Ppad, p.nmat, rp2, rp, p.nref, r, p.udst, srP, p.Ppad, P, n));
     RUN(pmd_launch_expand_pooled(ctx, p.udst, srP, p.Ppad, pool_idx, pool_w, d, r, p.ut0, srd, p.dpad, n));
-    ctx->atx_label = "tile_atx_main";
-    RUN(pmd_launch_tile_atx_rp(ctx, Xf, ldx, tile_pix, d, 0, d, p.ut0, srd, p.dpad, p.outA, srv, ldv, n, t_crop, 2, r));
-    ctx->atx_label = nullptr;
+    RUN(pmd_launch_tile_atx_rp(ctx, Xf, ldx, tile_pix, d, 0, d, p.ut0, srd, p.dpad, p.outA, srv, ldv, n, t_crop, 2, r, {"tile_atx_main"}));
   }
   if (stages & 2) {
     RUN(pmd_launch_wide_gram(ctx, p.outA, srv, ldv, t_crop, n, GRAM_SLICES, rp, p.gpart));
@@ -163,9 +157,7 @@ static int tiles_decompose_wide(pmd_ctx* ctx, const tiles_plan& p, const float* 
     RUN(pmd_launch_wide_gram(ctx, p.sst, srd, p.dpad, d, n, 1, rp, p.gpart));
     RUN(pmd_launch_wide_eig(ctx, p.gpart, 1, rp, r, 1, 1e-10, p.nmat, p.lam, n, p.eig_ws, p.eig_ws_bytes));
     RUN(pmd_launch_wide_rowmix(ctx, p.sst, srd, p.dpad, p.nmat, rp2, rp, r, r, p.sst, srd, p.dpad, d, n));
-    ctx->atx_label = "tile_atx_main";
-    RUN(pmd_launch_tile_atx_rp(ctx, Xf, ldx, tile_pix, d, 0, d, p.sst, srd, p.dpad, V_out, srv, ldv, n, t_crop, 2, r));
-    ctx->atx_label = nullptr;
+    RUN(pmd_launch_tile_atx_rp(ctx, Xf, ldx, tile_pix, d, 0, d, p.sst, srd, p.dpad, V_out, srv, ldv, n, t_crop, 2, r, {"tile_atx_main"}));
     RUN(pmd_launch_wide_gram(ctx, V_out, srv, ldv, t_crop, n, GRAM_SLICES, rp, p.gpart));
     RUN(pmd_launch_wide_eig(ctx, p.gpart, GRAM_SLICES, rp, r, 0, 0.0, p.nmat, sing_out ? sing_out : p.lam, n, p.eig_ws, p.eig_ws_bytes));
     RUN(pmd_launch_wide_rowmix(ctx, p.sst, srd, p.dpad, p.nmat, rp2, rp, r, r, Ut_out, srd, p.dpad, d, n));
@@ -176,12 +168,15 @@ static int tiles_decompose_wide(pmd_ctx* ctx, const tiles_plan& p, const float* 
   return PMD_OK;
 }
 
-int pmd_tiles_decompose_impl(pmd_ctx* ctx, const float* Xf, long ldx, long n_rows, int t_crop, const int* tile_pix, int n, int b1,
-                             int b2, const int* pool_q, int pool_max, int P, const int* pool_idx, const float* pool_w,
-                             int r, int a, float thr_s, float thr_t, int max_fail, uint64_t seed, uint32_t omega_index0,
-                             uint32_t omega_index_step, float* Ut_out, float* V_out, long ldv, float* stats_out,
-                             int* good_out, int* keep_out, int* ranks_out, double* sing_out, void* ws, size_t ws_bytes,
-                             int stages) {
+extern "C" int pmd_tiles_decompose_staged(pmd_ctx* ctx, const float* Xf, long ldx, long n_rows, int t_crop,
+                                          const int* tile_pix, int n, int b1, int b2, const int* pool_q, int pool_max,
+                                          int P, const int* pool_idx, const float* pool_w, int r, int a, float thr_s,
+                                          float thr_t, int max_fail, uint64_t seed, uint32_t omega_index0,
+                                          uint32_t omega_index_step, float* Ut_out, float* V_out, long ldv,
+                                          float* stats_out, int* good_out, int* keep_out, int* ranks_out,
+                                          double* sing_out, void* ws, size_t ws_bytes, int stages) {
+  CTX_CHECK(ctx);
+  if (stages < 1 || stages > 7) return pmd_fail(ctx, PMD_ERR_ARG, "pmd_tiles_decompose_staged", "stages must be a mask of bits 0..2");
   const int d = b1 * b2;
   if (r < 1) return pmd_fail(ctx, PMD_ERR_ARG, "pmd_tiles_decompose", "max_components must be >= 1");
   if (a < 1 || t_crop % a != 0 || t_crop / a < 1) return pmd_fail(ctx, PMD_ERR_ARG, "pmd_tiles_decompose", "t_crop must be a positive multiple of temporal_avg_factor");
@@ -232,9 +227,7 @@ int pmd_tiles_decompose_impl(pmd_ctx* ctx, const float* Xf, long ldx, long n_row
   RUN(pmd_launch_expand_pooled(ctx, p.udst, s64P, p.Ppad, pool_idx, pool_w, d, r, p.ut0, s64d, p.dpad, n));
 
   // --- V_ds = U_ds^T X_ds; basis of its row space (decomposition.py:295-301)
-  ctx->atx_label = "tile_atx_main";
-  RUN(pmd_launch_tile_atx(ctx, Xf, ldx, tile_pix, d, 0, d, p.ut0, s64d, p.dpad, p.outA, s64v, ldv, n, t_crop, 2));
-  ctx->atx_label = nullptr;
+  RUN(pmd_launch_tile_atx(ctx, Xf, ldx, tile_pix, d, 0, d, p.ut0, s64d, p.dpad, p.outA, s64v, ldv, n, t_crop, 2, {"tile_atx_main"}));
   }
   if (stages & 2) {
   // (this Gram only conditions the basis change -- span(S) does not depend on it -- so fp32 MFMA is enough)
@@ -262,9 +255,7 @@ int pmd_tiles_decompose_impl(pmd_ctx* ctx, const float* Xf, long ldx, long n_row
   RUN(pmd_launch_tile_rowmix(ctx, p.sst, s64d, p.dpad, p.nmat, 4096, r, r, p.sst, s64d, p.dpad, d, n));
 
   // --- W = U0^T X, its SVD rotates U0 and gives sigma*V (decomposition.py:318-323)
-  ctx->atx_label = "tile_atx_main";
-  RUN(pmd_launch_tile_atx(ctx, Xf, ldx, tile_pix, d, 0, d, p.sst, s64d, p.dpad, V_out, s64v, ldv, n, t_crop, 2));
-  ctx->atx_label = nullptr;
+  RUN(pmd_launch_tile_atx(ctx, Xf, ldx, tile_pix, d, 0, d, p.sst, s64d, p.dpad, V_out, s64v, ldv, n, t_crop, 2, {"tile_atx_main"}));
   RUN(pmd_launch_tile_gram(ctx, V_out, s64v, ldv, t_crop, n, gs, p.gpart));
   RUN(pmd_launch_small_eig(ctx, p.gpart, gs, r, 0, 0.0, p.nmat, sing_out ? sing_out : p.lam, n));
   RUN(pmd_launch_tile_rowmix(ctx, p.sst, s64d, p.dpad, p.nmat, 4096, r, r, Ut_out, s64d, p.dpad, d, n));
@@ -277,8 +268,20 @@ int pmd_tiles_decompose_impl(pmd_ctx* ctx, const float* Xf, long ldx, long n_row
   return PMD_OK;
 }
 
-int pmd_tiles_hook_offsets_impl(int n, int d, int P, int r, int a, int t_crop, long ldv, long n_rows, size_t* vds_off,
-                                size_t* s_off) {
+extern "C" int pmd_tiles_decompose(pmd_ctx* ctx, const float* xf, long ldx, long n_rows, int t_crop, const int* tile_pix, int n_tiles,
+                                   int b1, int b2, const int* pool_q, int pool_max, int P, const int* pool_idx, const float* pool_w,
+                                   int r, int a, float thr_s, float thr_t, int max_fail, uint64_t seed, uint32_t omega_index0,
+                                   uint32_t omega_index_step, float* Ut_out, float* V_out, long ldv, float* stats_out, int* good_out,
+                                   int* keep_out, int* ranks_out, double* lam_out, void* ws, size_t ws_bytes) {
+  return pmd_tiles_decompose_staged(ctx, xf, ldx, n_rows, t_crop, tile_pix, n_tiles, b1, b2, pool_q, pool_max, P, pool_idx, pool_w, r,
+                                    a, thr_s, thr_t, max_fail, seed, omega_index0, omega_index_step, Ut_out, V_out, ldv, stats_out,
+                                    good_out, keep_out, ranks_out, lam_out, ws, ws_bytes, 7);
+}
+
+extern "C" int pmd_tiles_hook_offsets(int n, int b1, int b2, int P, int r, int a, int t_crop, long ldv, long n_rows,
+                                      size_t* vds_off, size_t* s_off) {
+  if (!vds_off || !s_off) return PMD_ERR_ARG;
+  const int d = b1 * b2;
   pmd_arena ar((void*)0x1000, ~size_t(0) >> 1);
   tiles_plan p;
   if (plan_tiles(ar, p, n, d, P, r, a, t_crop, ldv, n_rows) != PMD_OK) return PMD_ERR_UNSUPPORTED;
@@ -336,17 +339,20 @@ static int plan_resid(pmd_arena& ar, resid_plan& p, int n, int d, int r, int a, 
   return PMD_OK;
 }
 
-size_t pmd_tiles_residual_workspace_bytes_impl(int n, int d, int r, int a, int L, long n_rows) {
+extern "C" size_t pmd_tiles_residual_workspace_bytes(int n, int b1, int b2, int r, int a, int L, long n_rows) {
+  const int d = b1 * b2;
   pmd_arena ar((void*)0x1000, ~size_t(0) >> 1);
   resid_plan p;
   if (plan_resid(ar, p, n, d, r, a, L, n_rows) != PMD_OK) return 0;
   return ar.used + 4096;
 }
 
-int pmd_tiles_residual_impl(pmd_ctx* ctx, const float* Xw, long ldx, long n_rows, int L, const int* tile_pix, int n,
-                            int b1, int b2, int r, int a, float thr_s, float thr_t, int max_fail, uint64_t seed,
-                            uint32_t omega_index0, uint32_t omega_index_step, float* Ucur, int* counts, float* stats_out,
-                            int* good_out, int* keep_out, void* ws, size_t ws_bytes) {
+extern "C" int pmd_tiles_residual(pmd_ctx* ctx, const float* Xw, long ldx, long n_rows, int L, const int* tile_pix,
+                                  int n, int b1, int b2, int r, int a, float thr_s, float thr_t, int max_fail,
+                                  uint64_t seed, uint32_t omega_index0, uint32_t omega_index_step, float* Ucur,
+                                  int* counts, float* stats_out, int* good_out, int* keep_out, void* ws,
+                                  size_t ws_bytes) {
+  CTX_CHECK(ctx);
   const int d = b1 * b2;
   if (r < 1) return pmd_fail(ctx, PMD_ERR_ARG, "pmd_tiles_residual", "max_components must be >= 1");
   if (a < 1 || L % a != 0 || L / a < 1) return pmd_fail(ctx, PMD_ERR_ARG, "pmd_tiles_residual", "window length must be a positive multiple of temporal_avg_factor");
@@ -404,7 +410,7 @@ int pmd_tiles_residual_impl(pmd_ctx* ctx, const float* Xw, long ldx, long n_rows
   RUN(pmd_launch_tile_atx(ctx, p.ar, p.ld_b, nullptr, 0, d, d, p.qt, s64d, p.dpad, p.bm, s64b, p.ld_b, n, p.nb, 1));
   RUN(pmd_launch_tile_gram(ctx, p.bm, s64b, p.ld_b, p.nb, n, 1, p.gpart));
   RUN(pmd_launch_small_eig(ctx, p.gpart, 1, p.nref, 0, 0.0, p.nmat, p.lam, n));
-  // new components of this window: min(max_components, bins, pixels) of them exist (see pmd_tiles_decompose_impl)
+  // new components of this window: min(max_components, bins, pixels) of them exist (see pmd_tiles_decompose_staged)
   const int rn = std::min(r, std::min(p.nb, p.nref));
   RUN(pmd_launch_tile_rowmix(ctx, p.qt, s64d, p.dpad, p.nmat, 4096, p.nref, rn, p.unew, s64d, p.dpad, d, n));
   // v = u^T (I - E E^T) X = utilde^T X with utilde = u - E (E^T u)   (decomposition.py:370-371, :379)
@@ -453,7 +459,8 @@ static int plan_sim(pmd_arena& ar, sim_plan& p, int d, int t, int iters) {
   return PMD_OK;
 }
 
-size_t pmd_sim_workspace_bytes_impl(int d, int t, int iters) {
+extern "C" size_t pmd_threshold_sim_workspace_bytes(int b1, int b2, int t, int iters) {
+  const int d = b1 * b2;
   pmd_arena ar((void*)0x1000, ~size_t(0) >> 1);
   sim_plan p;
   if (plan_sim(ar, p, d, t, iters) != PMD_OK) return 0;
@@ -468,8 +475,9 @@ __global__ void copy_sim_stats_kernel(const float* __restrict__ stats, int nb, f
   }
 }
 
-int pmd_threshold_sim_impl(pmd_ctx* ctx, int b1, int b2, int t, int iters, uint64_t seed, float* stats_out, void* ws,
-                           size_t ws_bytes) {
+extern "C" int pmd_threshold_sim(pmd_ctx* ctx, int b1, int b2, int t, int iters, uint64_t seed, float* stats_out,
+                                 void* ws, size_t ws_bytes) {
+  CTX_CHECK(ctx);
   const int d = b1 * b2;
   const int l = 11;  // num_comps = 1, ten oversamples (decomposition.py:59, :708)
   if (t < 3) return pmd_fail(ctx, PMD_ERR_ARG, "pmd_threshold_sim", "need at least 3 frames");
@@ -604,7 +612,7 @@ static void plan_bg(pmd_arena& ar, bg_plan& p, long D, int n, int K) {
   }
 }
 
-size_t pmd_bg_workspace_bytes_impl(long D, int n, int K) {
+extern "C" size_t pmd_background_rsvd_workspace_bytes(long D, int n, int K) {
   pmd_arena ar((void*)0x1000, ~size_t(0) >> 1);
   bg_plan p;
   plan_bg(ar, p, D, n, K);
@@ -641,8 +649,9 @@ static int background_rsvd_wide(pmd_ctx* ctx, const bg_plan& p, const float* xs,
 
 // xs: standardised sample, pixel-major [c][f], leading dimension ld >= pmd_time_ld(n), with
 // round_up(D, 256) rows allocated (rows >= D zero).  basis_out: [c][k], K columns.
-int pmd_background_rsvd_impl(pmd_ctx* ctx, const float* xs, long D, int n, long ld, int K, uint64_t seed,
-                             float* basis_out, void* ws, size_t ws_bytes) {
+extern "C" int pmd_background_rsvd(pmd_ctx* ctx, const float* xs, long D, int n, long ld, int K, uint64_t seed,
+                                   float* basis_out, void* ws, size_t ws_bytes) {
+  CTX_CHECK(ctx);
   const int l = K + 10;
   if (K < 1 || l > 1024) return pmd_fail(ctx, PMD_ERR_UNSUPPORTED, "pmd_background_rsvd", "background_rank must be in [1, 1014]");
   if (ld < pmd_time_ld(n)) return pmd_fail(ctx, PMD_ERR_ARG, "pmd_background_rsvd", "leading dimension too small");

@@ -56,27 +56,24 @@ struct pmd_routes {
 };
 
 struct pmd_ctx {
-  int device;
-  hipStream_t stream;
-  rocblas_handle blas;
-  float* tables;  // device: Hann window + FFT twiddles, see prep.hip
-  char err[512];
-  const char* atx_label;             // profiling name of the next tile_atx launches (NULL: "tile_atx")
-  int atx_rows;                      // rows of A that carry data in the next tile_atx launches (0: all 64)
-  const int* atx_ranks;              // per-tile ranks of the next tile_atx launches (projection: rows >= rank of A are zero), or NULL
-  void* scratch;                     // library-owned device scratch of the eigensolver (sytrd.hip)
-  size_t scratch_bytes;
-  void* scratch2;                    // library-owned device scratch of the fp64 eigenvector refinement (sytrd.hip)
-  size_t scratch2_bytes;
+  int device = 0;
+  hipStream_t stream = nullptr;
+  rocblas_handle blas = nullptr;
+  float* tables = nullptr;           // device: Hann window + FFT twiddles, see prep.hip
+  char err[512] = "";
+  void* scratch = nullptr;           // library-owned device scratch of the eigensolver (sytrd.hip)
+  size_t scratch_bytes = 0;
+  void* scratch2 = nullptr;          // library-owned device scratch of the fp64 eigenvector refinement (sytrd.hip)
+  size_t scratch2_bytes = 0;
   pmd_routes routes;                 // the PMD_* route switches, as the environment had them when the context was created
-  void* f16x2;                       // state of gemm_f16x2.hip (hipBLASLt handle, plans), created on first use
-  void* split_ws;                    // library-owned device scratch of the split products (fp16 pieces, split-K partial sums)
-  size_t split_ws_bytes;
-  void* comm;                        // RCCL communicator (pmd_comm_init), NULL without one
-  int comm_rank, comm_world;
-  float null_cutoff;                 // < 0: keep every direction with lambda != 0, scaled by 1/sqrt(|lambda|) (decomposition.py:984-996);
+  void* f16x2 = nullptr;             // state of gemm_f16x2.hip (hipBLASLt handle, plans), created on first use
+  void* split_ws = nullptr;          // library-owned device scratch of the split products (fp16 pieces, split-K partial sums)
+  size_t split_ws_bytes = 0;
+  void* comm = nullptr;              // RCCL communicator (pmd_comm_init), NULL without one
+  int comm_rank = 0, comm_world = 0;
+  float null_cutoff = -1.f;          // < 0: keep every direction with lambda != 0, scaled by 1/sqrt(|lambda|) (decomposition.py:984-996);
                                      // >= 0: keep lambda > null_cutoff * lambda_max only (pmd_ctx_set_null_cutoff)
-  bool profile;                      // pmd_profile_enable: HIP events around every kernel group
+  bool profile = false;              // pmd_profile_enable: HIP events around every kernel group
   std::vector<pmd_prof_rec> recs;
 };
 
@@ -113,6 +110,17 @@ static inline int pmd_fail(pmd_ctx* ctx, int code, const char* what, const char*
   do {                                                                            \
     hipError_t e__ = hipGetLastError();                                           \
     if (e__ != hipSuccess) return pmd_fail(ctx, PMD_ERR_HIP, name, hipGetErrorString(e__)); \
+  } while (0)
+
+// first line of every entry point that takes a context
+#define CTX_CHECK(ctx) \
+  if (!(ctx)) return PMD_ERR_ARG;
+
+// passes a failed library call's return code on to the caller
+#define RUN(call)                    \
+  do {                               \
+    int rc__ = (call);               \
+    if (rc__ != PMD_OK) return rc__; \
   } while (0)
 
 static inline long pmd_round_up(long x, long m) { return (x + m - 1) / m * m; }

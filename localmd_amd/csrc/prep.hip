@@ -9,7 +9,6 @@
 // 128-B line whatever the tile origin is.
 #include "pmd_internal.h"
 #include "fft_tables.h"
-#include "../../include/pmd_hip.h"
 
 // ---- tables: [0,256) Hann window (periodic); [256,320) cos, [320,384) sin of 2*pi*k/128;
 //              [384,513) cos, [513,642) sin of 2*pi*k/256 (k = 0..128)
@@ -189,13 +188,14 @@ static int stats_finalize(pmd_ctx* ctx, const double* csum, const float* cnoise,
   return PMD_OK;
 }
 
-size_t pmd_stats_workspace_bytes(int T, long D, int frame_const) {
+extern "C" size_t pmd_stats_workspace_bytes(int T, long D, int frame_const) {
   const int nchunks = (T + frame_const - 1) / frame_const;
   return (size_t)nchunks * D * (sizeof(double) + sizeof(float)) + 1024;
 }
 
-int pmd_launch_stats(pmd_ctx* ctx, const float* movie, int T, long D, int frame_const, int do_noise, float* mean_out,
-                     float* std_out, void* ws, size_t ws_bytes) {
+extern "C" int pmd_stats(pmd_ctx* ctx, const float* movie, int T, long D, int frame_const, int do_noise,
+                         float* mean_out, float* std_out, void* ws, size_t ws_bytes) {
+  CTX_CHECK(ctx);
   pmd_prof_scope prof__(ctx, "stats_welch");
   const int nchunks = (T + frame_const - 1) / frame_const;
   pmd_arena ar(ws, ws_bytes);
@@ -216,7 +216,7 @@ int pmd_launch_stats(pmd_ctx* ctx, const float* movie, int T, long D, int frame_
 // the Welch pass compiled for 16-bit loads contracts its multiply-adds differently (last-bit differences in sigma seen),
 // and the promise is the bits of pmd_stats on the converted movie.  The extra fp32 write + read of a chunk is HBM
 // traffic, far below the host link that bounds the streamed passes.
-size_t pmd_stats_stream_workspace_bytes(int T, long D) {
+extern "C" size_t pmd_stats_stream_workspace_bytes(int T, long D) {
   return pmd_stats_workspace_bytes(T, D, PMD_STATS_CHUNK) + (size_t)PMD_STATS_CHUNK * D * sizeof(float) + 256;
 }
 
@@ -241,8 +241,9 @@ static int stats_chunks_widened(pmd_ctx* ctx, const E* batch, int nb, long D, in
   return PMD_OK;
 }
 
-int pmd_launch_stats_stream_accumulate(pmd_ctx* ctx, const void* batch, int elem, int t0, int nb, int T, long D,
-                                       int do_noise, void* ws, size_t ws_bytes) {
+extern "C" int pmd_stats_stream_accumulate(pmd_ctx* ctx, const void* batch, int elem, int t0, int nb, int T, long D,
+                                           int do_noise, void* ws, size_t ws_bytes) {
+  CTX_CHECK(ctx);
   pmd_prof_scope prof__(ctx, "stats_welch");
   if (T < 1 || D < 1 || nb < 1 || t0 < 0 || t0 % PMD_STATS_CHUNK != 0 || (long)t0 + nb > T ||
       (t0 + nb < T && nb % PMD_STATS_CHUNK != 0))
@@ -272,8 +273,9 @@ int pmd_launch_stats_stream_accumulate(pmd_ctx* ctx, const void* batch, int elem
   }
 }
 
-int pmd_launch_stats_stream_finish(pmd_ctx* ctx, int T, long D, int do_noise, float* mean_out, float* std_out, void* ws,
-                                   size_t ws_bytes) {
+extern "C" int pmd_stats_stream_finish(pmd_ctx* ctx, int T, long D, int do_noise, float* mean_out, float* std_out,
+                                       void* ws, size_t ws_bytes) {
+  CTX_CHECK(ctx);
   pmd_prof_scope prof__(ctx, "stats_welch");
   if (T < 1 || D < 1) return pmd_fail(ctx, PMD_ERR_ARG, "pmd_stats_stream_finish", "empty movie");
   const int nchunks = (T + PMD_STATS_CHUNK - 1) / PMD_STATS_CHUNK;
@@ -324,8 +326,9 @@ __global__ __launch_bounds__(256) void standardize_transpose_kernel(const E* __r
   }
 }
 
-int pmd_launch_standardize_transpose(pmd_ctx* ctx, const float* movie, long D, const int* frames, int nf,
-                                     const float* mean, const float* stdv, float* out, long ld) {
+extern "C" int pmd_standardize_transpose(pmd_ctx* ctx, const float* movie, long D, const int* frames, int nf,
+                                         const float* mean, const float* stdv, float* out, long ld) {
+  CTX_CHECK(ctx);
   pmd_prof_scope prof__(ctx, "standardize_transpose");
   dim3 grid((unsigned)((D + 63) / 64), (unsigned)((ld + 63) / 64));
   hipLaunchKernelGGL(standardize_transpose_kernel<float>, grid, dim3(256), 0, ctx->stream, movie, D, frames, nf, mean,
@@ -334,8 +337,9 @@ int pmd_launch_standardize_transpose(pmd_ctx* ctx, const float* movie, long D, c
   return PMD_OK;
 }
 
-int pmd_launch_standardize_transpose_typed(pmd_ctx* ctx, const void* movie, int elem, long D, const int* frames, int nf,
-                                           const float* mean, const float* stdv, float* out, long ld) {
+extern "C" int pmd_standardize_transpose_typed(pmd_ctx* ctx, const void* movie, int elem, long D, const int* frames,
+                                               int nf, const float* mean, const float* stdv, float* out, long ld) {
+  CTX_CHECK(ctx);
   pmd_prof_scope prof__(ctx, "standardize_transpose");
   if (D < 1 || nf < 1 || ld < nf)
     return pmd_fail(ctx, PMD_ERR_ARG, "pmd_standardize_transpose_typed", "empty input or leading dimension too small");
@@ -375,8 +379,9 @@ __global__ __launch_bounds__(256) void gather_frames_kernel(const E* __restrict_
   for (long c = (long)blockIdx.x * 256 + threadIdx.x; c < D; c += (long)gridDim.x * 256) o[c] = s[c];
 }
 
-int pmd_launch_gather_frames(pmd_ctx* ctx, const void* src, int elem, long D, const int* src_rows, const int* dst_rows,
-                             int n, void* dst) {
+extern "C" int pmd_gather_frames(pmd_ctx* ctx, const void* src, int elem, long D, const int* src_rows,
+                                 const int* dst_rows, int n, void* dst) {
+  CTX_CHECK(ctx);
   pmd_prof_scope prof__(ctx, "gather_frames");
   if (n <= 0) return PMD_OK;
   if (D < 1) return pmd_fail(ctx, PMD_ERR_ARG, "pmd_gather_frames", "empty frame");
@@ -444,8 +449,9 @@ __global__ __launch_bounds__(256) void filter_kernel(const float* in, float* out
   }
 }
 
-int pmd_launch_filter(pmd_ctx* ctx, const float* in, float* out, long D, int nf, long ld, const float* basis, int K,
-                      const float* pj, long ldp) {
+extern "C" int pmd_bg_filter(pmd_ctx* ctx, const float* in, float* out, long D, int nf, long ld, const float* basis,
+                             int K, const float* pj, long ldp) {
+  CTX_CHECK(ctx);
   pmd_prof_scope prof__(ctx, "bg_filter");
   const int bx = (int)((ld + 255) / 256);
   const long rows_per_launch = 65535L * 64;
@@ -476,7 +482,8 @@ __global__ void scale_rows_kernel(float* __restrict__ x, long D, int nf, long ld
   for (long f = (long)blockIdx.x * blockDim.x + threadIdx.x; f < nf; f += (long)gridDim.x * blockDim.x) x[c * ld + f] *= s;
 }
 
-int pmd_launch_scale_rows(pmd_ctx* ctx, float* x, long D, int nf, long ld, const float* w) {
+extern "C" int pmd_scale_rows(pmd_ctx* ctx, float* x, long D, int nf, long ld, const float* w) {
+  CTX_CHECK(ctx);
   for (long c0 = 0; c0 < D; c0 += 32768) {
     const long cn = (D - c0 < 32768) ? D - c0 : 32768;
     hipLaunchKernelGGL(scale_rows_kernel, dim3(8, (unsigned)cn), dim3(256), 0, ctx->stream, x + c0 * ld, D, nf, ld,
@@ -556,4 +563,11 @@ int pmd_launch_tile_pool_bin(pmd_ctx* ctx, const float* X, long ldx, long n_rows
     PMD_LAUNCH_CHECK(ctx, "tile_pool_kernel");
   }
   return PMD_OK;
+}
+
+extern "C" int pmdk_tile_pool_bin(pmd_ctx* ctx, const float* X, long ldx, long n_rows, const int* pix, int n_tiles, int d,
+                                  const int* pool_q, int pool_max, int P, int a, int nbins, float* xbar, float* abar, long ld_ab,
+                                  long tile_stride) {
+  CTX_CHECK(ctx);
+  return pmd_launch_tile_pool_bin(ctx, X, ldx, n_rows, pix, n_tiles, d, pool_q, pool_max, P, a, nbins, xbar, abar, ld_ab, tile_stride);
 }

@@ -137,7 +137,7 @@ size_t pmd_group_project_workspace_bytes(long n_partial_rows, int n) {
 int pmd_group_project(pmd_ctx* ctx, const void* Y, int elem, int n, long D, const float* mean, const float* std,
                       int n_groups, const long* groups, const int* pix, const float* A, long n_partial_rows,
                       int n_wide_rows, const long* wide, float* Z, long ldz, void* ws, size_t ws_bytes) {
-  if (!ctx) return PMD_ERR_ARG;
+  CTX_CHECK(ctx);
   const char* what = "pmd_group_project";
   if (n < 0 || D < 1 || n_groups < 0 || n_wide_rows < 0 || n_partial_rows < 0 || ldz < n)
     return pmd_fail(ctx, PMD_ERR_ARG, what, "bad scalar argument (n >= 0, D >= 1, counts >= 0, ldz >= n)");

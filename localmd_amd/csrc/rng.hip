@@ -3,7 +3,7 @@
 // pmd_loader.py:56.  Element e of logical array (stream, index) comes from Philox block
 // q = e/4, lane e%4, counter (q_lo, q_hi, index, stream), key (seed_lo, seed_hi); the result
 // is independent of launch geometry and GPU count.  oracle/philox.py restates it in NumPy.
-#include "pmd_common.h"
+#include "pmd_internal.h"
 
 __device__ __forceinline__ void philox_round(uint32_t c[4], uint32_t k0, uint32_t k1) {
   const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
@@ -75,5 +75,16 @@ int pmd_launch_rng(pmd_ctx* ctx, uint64_t seed, uint32_t stream, uint32_t index0
   hipLaunchKernelGGL(rng_normal_kernel, dim3(bx, batch), dim3(256), 0, ctx->stream, seed, stream, index0,
                      index_step, rows, cols, transpose, out, ld, batch_stride);
   PMD_LAUNCH_CHECK(ctx, "rng_normal_kernel");
+  return PMD_OK;
+}
+
+extern "C" int pmd_rng_normal(pmd_ctx* ctx, uint64_t seed, uint32_t stream, uint32_t index0, uint32_t index_step, int batch, long rows,
+                              int cols, int transpose, float* out, long ld, long batch_stride) {
+  CTX_CHECK(ctx);
+  for (int b0 = 0; b0 < batch; b0 += 32768) {
+    const int bn = (batch - b0 < 32768) ? batch - b0 : 32768;
+    RUN(pmd_launch_rng(ctx, seed, stream, index0 + (uint32_t)b0 * index_step, index_step, bn, rows, cols, transpose,
+                       out + (long)b0 * batch_stride, ld, batch_stride));
+  }
   return PMD_OK;
 }

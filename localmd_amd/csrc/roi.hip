@@ -129,7 +129,7 @@ size_t pmd_roi_gather_workspace_bytes(long n_partial_rows, int n) {
 int pmd_roi_gather(pmd_ctx* ctx, const void* Y, int elem, int n, long D, long n_segs, const long* segs, const int* pix,
                    const float* w, long n_partial_rows, int n_split, const long* split, float* out, long ldo, void* ws,
                    size_t ws_bytes) {
-  if (!ctx) return PMD_ERR_ARG;
+  CTX_CHECK(ctx);
   const char* what = "pmd_roi_gather";
   if (n < 0 || D < 1 || n_segs < 0 || n_split < 0 || n_partial_rows < 0 || ldo < n)
     return pmd_fail(ctx, PMD_ERR_ARG, what, "bad scalar argument (n >= 0, D >= 1, counts >= 0, ldo >= n)");
@@ -174,7 +174,7 @@ int pmd_roi_gather(pmd_ctx* ctx, const void* Y, int elem, int n, long D, long n_
 
 int pmd_roi_combine(pmd_ctx* ctx, long K, int n, const float* C, long ldc, const float* offset, const float* raw, long ldr,
                     float* den, long ldd, float* res, long lde) {
-  if (!ctx) return PMD_ERR_ARG;
+  CTX_CHECK(ctx);
   const char* what = "pmd_roi_combine";
   if (K < 0 || n < 0 || (C && ldc < n) || (den && ldd < n) || (res && (lde < n || ldr < n)))
     return pmd_fail(ctx, PMD_ERR_ARG, what, "bad scalar argument (K, n >= 0, leading dimensions >= n)");

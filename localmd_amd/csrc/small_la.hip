@@ -133,6 +133,12 @@ int pmd_launch_small_qr(pmd_ctx* ctx, const float* Yt, long y_tile_stride, int y
   return PMD_OK;
 }
 
+extern "C" int pmdk_small_qr(pmd_ctx* ctx, const float* Yt, long y_tile_stride, int y_ld, int P, int l, float* Qt, long q_tile_stride,
+                             int q_ld, int n_tiles) {
+  CTX_CHECK(ctx);
+  return pmd_launch_small_qr(ctx, Yt, y_tile_stride, y_ld, P, l, Qt, q_tile_stride, q_ld, n_tiles);
+}
+
 // ---------------------------------------------------------------- tridiagonal QL eigensolver, one wave per problem ----
 // G: [tile][slices][64][64] doubles (summed over the slices and symmetrised on load; only the leading n x n block is used).
 // Nout[tile][c'][c] = eigenvector c (descending eigenvalue), component c'.
@@ -361,6 +367,12 @@ int pmd_launch_small_eig(pmd_ctx* ctx, const double* G, int slices, int n, int m
   return PMD_OK;
 }
 
+extern "C" int pmdk_small_eig(pmd_ctx* ctx, const double* G, int slices, int n, int mode, double tol, double* Nout, double* lam_out,
+                              int n_tiles) {
+  CTX_CHECK(ctx);
+  return pmd_launch_small_eig(ctx, G, slices, n, mode, tol, Nout, lam_out, n_tiles);
+}
+
 // ---------------------------------------------------------------- batched Cholesky whitening
 // Same interface as small_eig mode 1 where only an ORTHONORMAL BASIS is wanted, not the eigenvectors: G = R^T R
 // (upper R), Nout[tile][c'][c] = (R^{-1})[c'][c], so that tile_rowmix turns rows with Gram matrix G into orthonormal
@@ -526,6 +538,12 @@ int pmd_launch_stats_roughness(pmd_ctx* ctx, const float* Ut, long u_tile_stride
     }
   }
   return PMD_OK;
+}
+
+extern "C" int pmdk_roughness(pmd_ctx* ctx, const float* Ut, long u_tile_stride, int u_ld, int b1, int b2, const float* V,
+                              long v_tile_stride, long v_ld, int T, int r, float* stats, int n_tiles) {
+  CTX_CHECK(ctx);
+  return pmd_launch_stats_roughness(ctx, Ut, u_tile_stride, u_ld, b1, b2, V, v_tile_stride, v_ld, T, r, stats, n_tiles, PMD_RPAD);
 }
 
 // evaluation.py:133-164 + :195-222.  keep[tile][c] in {0,1}; ranks[tile] = number kept (capped).
@@ -732,7 +750,9 @@ __global__ void tile_truncate_kernel(float* __restrict__ U, int ld, const int* _
     U[(long)tile * rp * ld + (long)k * ld + i] = 0.f;
 }
 
-int pmd_launch_tile_truncate(pmd_ctx* ctx, float* U, int ld, const int* counts, int n_tiles, int rp) {
+extern "C" int pmd_tiles_truncate(pmd_ctx* ctx, float* U, int ld, const int* counts, int n_tiles, int rp) {
+  CTX_CHECK(ctx);
+  if (rp < 64 || rp % 64) return pmd_fail(ctx, PMD_ERR_ARG, "pmd_tiles_truncate", "rpad must be a positive multiple of 64");
   for (int t0 = 0; t0 < n_tiles; t0 += 32768) {
     const int tn = (n_tiles - t0 < 32768) ? n_tiles - t0 : 32768;
     hipLaunchKernelGGL(tile_truncate_kernel, dim3(16, tn), dim3(256), 0, ctx->stream, U + (long)t0 * rp * ld, ld, counts + t0, rp);

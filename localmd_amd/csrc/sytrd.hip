@@ -803,18 +803,13 @@ __global__ void tinv_kernel(float* __restrict__ S, int kb, const float* __restri
 // Three GEMMs and one triangular solve per block (rocSOLVER's sormtr works in 64-column steps at ~20 TFLOP/s).
 constexpr int QB = 1024;
 
-size_t pmd_apply_q_workspace_bytes_impl(int n) {
+static size_t pmd_apply_q_workspace_bytes_impl(int n) {
   return ((size_t)QB * n + (size_t)QB * QB + (size_t)n * QB) * sizeof(float) + 4096;
 }
 
-int pmd_apply_q_impl(pmd_ctx* ctx, int n, const float* A, long lda, const float* tau, float* Z, long ldz, void* ws,
-                     size_t ws_bytes) {
-  return pmd_apply_q_off_impl(ctx, n, A, lda, tau, Z, ldz, ws, ws_bytes, 1);
-}
-
 // off: distance of a reflector's unit entry below the diagonal (reflector c = [1 at position c + off, A[c][c + off + 1 ..)])
-int pmd_apply_q_off_impl(pmd_ctx* ctx, int n, const float* A, long lda, const float* tau, float* Z, long ldz, void* ws,
-                         size_t ws_bytes, int off) {
+static int pmd_apply_q_off_impl(pmd_ctx* ctx, int n, const float* A, long lda, const float* tau, float* Z, long ldz,
+                                void* ws, size_t ws_bytes, int off) {
   pmd_prof_scope prof__(ctx, "apply_q");
   if (n < off + 1) return PMD_OK;
   pmd_arena ar(ws, ws_bytes);
@@ -844,8 +839,13 @@ int pmd_apply_q_off_impl(pmd_ctx* ctx, int n, const float* A, long lda, const fl
   return PMD_OK;
 }
 
+static int pmd_apply_q_impl(pmd_ctx* ctx, int n, const float* A, long lda, const float* tau, float* Z, long ldz, void* ws,
+                     size_t ws_bytes) {
+  return pmd_apply_q_off_impl(ctx, n, A, lda, tau, Z, ldz, ws, ws_bytes, 1);
+}
+
 // ---------------------------------------------------------------------------------------------
-size_t pmd_sytrd_workspace_bytes_impl(int n) {
+static size_t pmd_sytrd_workspace_bytes_impl(int n) {
   const size_t n4 = (size_t)pmd_round_up(n, 4);
   const size_t nq = (size_t)(n / 256 + 2), nbk = (size_t)(n / BR + 2);
   size_t b = 0;
@@ -861,7 +861,7 @@ size_t pmd_sytrd_workspace_bytes_impl(int n) {
 
 // Tridiagonalise the symmetric matrix held in A (memory-upper triangle read, see the header comment).
 // d[n], e[n-1], tau[n-1] on the device.  lda % 4 == 0, lda >= round_up(n, 4), A 16-byte aligned.
-int pmd_sytrd_impl(pmd_ctx* ctx, int n, float* A, long lda, float* d, float* e, float* tau, void* ws, size_t ws_bytes) {
+static int pmd_sytrd_impl(pmd_ctx* ctx, int n, float* A, long lda, float* d, float* e, float* tau, void* ws, size_t ws_bytes) {
   pmd_prof_scope prof__(ctx, "sytrd");
   if (n < 1) return PMD_OK;
   const long n4 = pmd_round_up(n, 4);
@@ -938,7 +938,7 @@ int pmd_sytrd_impl(pmd_ctx* ctx, int n, float* A, long lda, float* d, float* e, 
 }
 
 // rocSOLVER's own tridiagonalisation with the same conventions (tests, small matrices)
-int pmd_sytrd_rocsolver(pmd_ctx* ctx, int n, float* A, long lda, float* d, float* e, float* tau) {
+static int pmd_sytrd_rocsolver(pmd_ctx* ctx, int n, float* A, long lda, float* d, float* e, float* tau) {
   pmd_prof_scope prof__(ctx, "rocsolver_ssytrd");
   PMD_BLAS(ctx, rocsolver_ssytrd(ctx->blas, rocblas_fill_lower, n, A, (rocblas_int)lda, d, e, tau));
   return PMD_OK;
@@ -959,7 +959,8 @@ static int ctx_scratch(pmd_ctx* ctx, size_t bytes, void** out) {
 }
 
 // Tridiagonalisation alone (tests and probes): impl 0 = rocSOLVER ssytrd('L'), 1 = this file.
-int pmd_sytrd_auto(pmd_ctx* ctx, int n, float* A, long lda, float* d, float* e, float* tau, int impl) {
+extern "C" int pmdk_sytrd(pmd_ctx* ctx, int n, float* A, long lda, float* d, float* e, float* tau, int impl) {
+  CTX_CHECK(ctx);
   if (impl == 0) return pmd_sytrd_rocsolver(ctx, n, A, lda, d, e, tau);
   const size_t tb = pmd_sytrd_workspace_bytes_impl(n);
   void* scratch = nullptr;
@@ -970,7 +971,7 @@ int pmd_sytrd_auto(pmd_ctx* ctx, int n, float* A, long lda, float* d, float* e, 
 
 // Two-stage path (sytrd2.hip): A = Q1 B Q1^T (band), B = Q2 T Q2^T (tridiagonal), sstedc, E = Q1 (Q2 Z).  *done = 0 and A
 // untouched when a panel of stage 1 was numerically rank deficient.
-int pmd_syevd_two_stage(pmd_ctx* ctx, int n, float* A, long lda, float* w, int* info, int* done) {
+static int pmd_syevd_two_stage(pmd_ctx* ctx, int n, float* A, long lda, float* w, int* info, int* done) {
   *done = 0;
   const size_t b1 = pmd_sy2sb_workspace_bytes_impl(n), b2 = pmd_sb2st_workspace_bytes_impl(n);
   const size_t bq = pmd_apply_q_workspace_bytes_impl(n);
@@ -1159,6 +1160,11 @@ int pmd_syevd(pmd_ctx* ctx, int n, float* A, long lda, float* w, float* work, in
   rc0 = pmd_syevd_f32(ctx, n, A, lda, w, work, info);
   if (rc0 != PMD_OK) return rc0;
   return syevd_refine(ctx, n, Ad, A, lda, w, Ad + (size_t)n * n, steps);
+}
+
+extern "C" int pmdk_syevd(pmd_ctx* ctx, int n, float* A, long lda, float* w, float* work, int* info) {
+  CTX_CHECK(ctx);
+  return pmd_syevd(ctx, n, A, lda, w, work, info);
 }
 
 static int pmd_syevd_f32(pmd_ctx* ctx, int n, float* A, long lda, float* w, float* work, int* info) {

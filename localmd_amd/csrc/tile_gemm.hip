@@ -12,7 +12,7 @@
 // Every per-tile [comp][x] array has PMD_RPAD = 64 rows (rows >= rank are zero) so that four
 // waves each own one 16-row MFMA tile.  All fp32 products run on v_mfma_f32_16x16x4_f32
 // (exact fp32 fmaf chains, 64 FLOP/clk/SIMD).
-#include "pmd_common.h"
+#include "pmd_internal.h"
 #include <cstdlib>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -414,8 +414,8 @@ static int launch_atx_variant(pmd_ctx* ctx, const float* X, long ldx, const int*
 // a_ld must be the padded pixel count returned by pmd_tile_dpad(d); Out rows are PMD_RPAD.
 int pmd_launch_tile_atx(pmd_ctx* ctx, const float* X, long ldx, const int* pix, int pix_stride, long row0_stride, int d,
                         const float* A, long a_tile_stride, int a_ld, float* Out, long out_tile_stride, long ldo,
-                        int n_tiles, int T, int slices) {
-  pmd_prof_scope prof__(ctx, ctx->atx_label ? ctx->atx_label : "tile_atx");
+                        int n_tiles, int T, int slices, const pmd_atx_opts& opts) {
+  pmd_prof_scope prof__(ctx, opts.label);
   if (n_tiles <= 0 || T <= 0) return PMD_OK;
   int kz = 1;
   int dv = d;
@@ -439,10 +439,10 @@ int pmd_launch_tile_atx(pmd_ctx* ctx, const float* X, long ldx, const int* pix, 
     const bool dma_ok = ctx->routes.atx_dma && ldx >= 32L * ((T + 31) / 32 + 2) && (ldx % 4) == 0;
     if (v.kjw == 25 && v.ks == 1 && dma_ok)
       return launch_atx_dma<25>(ctx, X, ldx, pix, pix_stride, row0_stride, d, A, a_tile_stride, a_ld, Out, out_tile_stride,
-                                ldo, n_tiles, T, slices, ctx->atx_ranks);
+                                ldo, n_tiles, T, slices, opts.ranks);
   }
-  // rows < 16 only (ctx->atx_rows, set by the background projection) on a 1024-pixel tile: eight K slices of one row tile
-  if (ctx->atx_rows > 0 && ctx->atx_rows <= 16 && v.kjw == 32 && v.ks == 2 && kz == 1)
+  // rows < 16 only (opts.rows, set by the background projection) on a 1024-pixel tile: eight K slices of one row tile
+  if (opts.rows > 0 && opts.rows <= 16 && v.kjw == 32 && v.ks == 2 && kz == 1)
     return launch_atx_variant<8, 8, 1, 1>(ctx, X, ldx, pix, pix_stride, row0_stride, d, A, a_tile_stride, a_ld, Out, out_tile_stride, ldo,
                                           n_tiles, T, slices, kz);
   ATX_CASE(16, 1, 2)
@@ -452,6 +452,36 @@ int pmd_launch_tile_atx(pmd_ctx* ctx, const float* X, long ldx, const int* pix, 
   ATX_CASE(32, 2, 1)
 #undef ATX_CASE
   return pmd_fail(ctx, PMD_ERR_UNSUPPORTED, "tile_atx", "variant not built");
+}
+
+extern "C" int pmdk_tile_atx(pmd_ctx* ctx, const float* X, long ldx, const int* pix, int pix_stride, long row0_stride, int d,
+                             const float* A, long a_tile_stride, int a_ld, float* Out, long out_tile_stride, long ldo, int n_tiles,
+                             int T, int slices) {
+  CTX_CHECK(ctx);
+  return pmd_launch_tile_atx(ctx, X, ldx, pix, pix_stride, row0_stride, d, A, a_tile_stride, a_ld, Out, out_tile_stride, ldo, n_tiles, T,
+                             slices);
+}
+
+extern "C" int pmdk_tile_atx_rows(pmd_ctx* ctx, const float* X, long ldx, const int* pix, int pix_stride, long row0_stride, int d,
+                                  const float* A, long a_tile_stride, int a_ld, float* Out, long out_tile_stride, long ldo,
+                                  int n_tiles, int T, int slices, int rows) {
+  CTX_CHECK(ctx);
+  return pmd_launch_tile_atx(ctx, X, ldx, pix, pix_stride, row0_stride, d, A, a_tile_stride, a_ld, Out, out_tile_stride, ldo, n_tiles, T,
+                             slices, {"tile_atx", rows});
+}
+
+extern "C" int pmd_tiles_project(pmd_ctx* ctx, const float* x, long ldx, int T, const int* tile_pix, int n_tiles, int d, const float* A,
+                                 int dpad, float* Out, long ldo, int slices) {
+  CTX_CHECK(ctx);
+  return pmd_launch_tile_atx(ctx, x, ldx, tile_pix, d, 0, d, A, 64L * dpad, dpad, Out, 64L * ldo, ldo, n_tiles, T, slices,
+                             {"tile_atx_main"});
+}
+
+extern "C" int pmd_tiles_project_ranked(pmd_ctx* ctx, const float* x, long ldx, int T, const int* tile_pix, int n_tiles, int d,
+                                        const float* A, int dpad, float* Out, long ldo, int slices, const int* ranks) {
+  CTX_CHECK(ctx);
+  return pmd_launch_tile_atx(ctx, x, ldx, tile_pix, d, 0, d, A, 64L * dpad, dpad, Out, 64L * ldo, ldo, n_tiles, T, slices,
+                             {"tile_atx_proj", 0, ranks});
 }
 
 // ------------------------------------------------------------------------------------------
@@ -594,6 +624,14 @@ int pmd_launch_tile_xbt(pmd_ctx* ctx, const float* X, long ldx, const int* pix, 
   return PMD_OK;
 }
 
+extern "C" int pmdk_tile_xbt(pmd_ctx* ctx, const float* X, long ldx, const int* pix, int pix_stride, long row0_stride, int d,
+                             const float* B, long b_tile_stride, long ldb, float* S, long s_tile_stride, long s_slice_stride, int s_ld,
+                             int n_tiles, int T, int slices) {
+  CTX_CHECK(ctx);
+  return pmd_launch_tile_xbt(ctx, X, ldx, pix, pix_stride, row0_stride, d, B, b_tile_stride, ldb, S, s_tile_stride, s_slice_stride, s_ld,
+                             n_tiles, T, slices);
+}
+
 // ------------------------------------------------------------------------------------------
 // tile_gram (fp64 accumulation of fp32 inputs).  256 threads = 16 x 16, each a 4 x 4 block.
 // ------------------------------------------------------------------------------------------
@@ -715,6 +753,11 @@ int pmd_launch_tile_gram(pmd_ctx* ctx, const float* In, long tile_stride, long l
                        G, (long)slices * 4096);
   PMD_LAUNCH_CHECK(ctx, "tile_gram_kernel");
   return PMD_OK;
+}
+
+extern "C" int pmdk_tile_gram(pmd_ctx* ctx, const float* In, long tile_stride, long ld, int len, int n_tiles, int slices, double* G) {
+  CTX_CHECK(ctx);
+  return pmd_launch_tile_gram(ctx, In, tile_stride, ld, len, n_tiles, slices, G);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1008,6 +1051,12 @@ int pmd_launch_tile_rowmix(pmd_ctx* ctx, const float* In, long in_tile_stride, l
     PMD_LAUNCH_CHECK(ctx, "tile_rowmix_kernel");
   }
   return PMD_OK;
+}
+
+extern "C" int pmdk_tile_rowmix(pmd_ctx* ctx, const float* In, long in_tile_stride, long ld_in, const double* N, long n_tile_stride,
+                                int n_in, int n_out, float* Out, long out_tile_stride, long ld_out, int len, int n_tiles) {
+  CTX_CHECK(ctx);
+  return pmd_launch_tile_rowmix(ctx, In, in_tile_stride, ld_in, N, n_tile_stride, n_in, n_out, Out, out_tile_stride, ld_out, len, n_tiles);
 }
 
 // float partial Gram blocks (tile_xbt output, [tile][slice][64][ld]) -> double [tile][slice][64][64]

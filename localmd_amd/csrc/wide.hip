@@ -14,19 +14,13 @@
 #include "pmd_internal.h"
 #include <rocsolver/rocsolver.h>
 
-#define RUN(call)                    \
-  do {                               \
-    int rc__ = (call);               \
-    if (rc__ != PMD_OK) return rc__; \
-  } while (0)
-
 #define WIDE_BLAS(ctx, call)                                                                   \
   do {                                                                                         \
     rocblas_status s__ = (call);                                                               \
     if (s__ != rocblas_status_success) return pmd_fail(ctx, PMD_ERR_BLAS, #call, "rocBLAS / rocSOLVER call failed"); \
   } while (0)
 
-int pmd_tile_rpad(int r) {
+extern "C" int pmd_tile_rpad(int r) {
   const int l = r + 10;
   return l <= 64 ? 64 : (int)pmd_round_up(l, 64);
 }
@@ -236,10 +230,10 @@ int pmd_launch_wide_rowmix(pmd_ctx* ctx, const float* In, long in_tile_stride, l
 // caller's (rp * ld)
 int pmd_launch_tile_atx_rp(pmd_ctx* ctx, const float* X, long ldx, const int* pix, int pix_stride, long row0_stride, int d,
                            const float* A, long a_tile_stride, int a_ld, float* Out, long out_tile_stride, long ldo, int n_tiles,
-                           int T, int slices, int nrows) {
+                           int T, int slices, int nrows, const pmd_atx_opts& opts) {
   for (int h = 0; 64 * h < nrows; ++h)
     RUN(pmd_launch_tile_atx(ctx, X, ldx, pix, pix_stride, row0_stride, d, A + (long)64 * h * a_ld, a_tile_stride, a_ld,
-                            Out + (long)64 * h * ldo, out_tile_stride, ldo, n_tiles, T, slices));
+                            Out + (long)64 * h * ldo, out_tile_stride, ldo, n_tiles, T, slices, opts));
   return PMD_OK;
 }
 

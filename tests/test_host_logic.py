@@ -461,6 +461,41 @@ def test_library_exports_every_declared_symbol():
     lib = ctypes.CDLL(_lib.LIB_PATH)
     for name in declared:
         assert hasattr(lib, name), name
+    # the types: every prototype of the header against its row of the ctypes table, entry by entry
+    scalars = {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float, "double": ctypes.c_double,
+               "size_t": ctypes.c_size_t, "uint64_t": ctypes.c_uint64, "uint32_t": ctypes.c_uint32}
+
+    def c_type(text):
+        """(base type, pointer depth) of a return type or of one parameter with its name"""
+        depth = text.count("*")
+        words = [w for w in text.replace("*", " ").split() if w != "const"]
+        assert words, text
+        base = words[0]
+        assert len(words) <= 2 and (base in scalars or depth > 0), text   # at most "type name"; a struct only by pointer
+        return base, depth
+
+    def matches(bound, base, depth):
+        if depth == 0:
+            return bound is scalars.get(base)
+        if bound is ctypes.c_char_p:
+            return (base, depth) == ("char", 1)
+        if isinstance(bound, type) and issubclass(bound, ctypes._Pointer):   # a typed pointer: check the pointee
+            return matches(bound._type_, base, depth - 1)
+        return bound is ctypes.c_void_p
+
+    code = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
+    code = re.sub(r"//[^\n]*", " ", code)
+    code = re.sub(r"^\s*#[^\n]*", " ", code, flags=re.M)
+    protos = re.findall(r"([A-Za-z_][\w\s\*]*?)\b(pmdk?_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", code)
+    assert {name for _, name, _ in protos} == declared
+    assert len(protos) == len(declared)
+    for ret, name, params in protos:
+        restype, argtypes = _lib.SIGNATURES[name]
+        assert matches(restype, *c_type(ret)), (name, "return type", ret.strip())
+        params = [] if params.strip() in ("", "void") else params.split(",")
+        assert len(params) == len(argtypes), (name, len(params), len(argtypes))
+        for i, (par, bound) in enumerate(zip(params, argtypes)):
+            assert matches(bound, *c_type(par)), (name, i, " ".join(par.split()), bound)
     loaded = _lib.load()
     assert loaded.pmd_version() == 1
     # host-only helpers can be called without a device
