@@ -146,6 +146,18 @@ int pmd_roi_gather(pmd_ctx* ctx, const void* Y, int elem, int n, long D, long n_
 int pmd_roi_combine(pmd_ctx* ctx, long K, int n, const float* C, long ldc, const float* offset, const float* raw, long ldr,
                     float* den, long ldd, float* res, long lde);
 
+/* Per-pixel regressor maps (localmd_amd/maps.py): one block of n frames of a batch against K time courses. */
+#define PMD_REGRESS_BLOCK 1024
+/* acc[k][c] += sum_{f < n} X[k][f] * z[f][c]   for k < K, c < D,   z[f][c] = (float) Y[f][c] - mean[c]  (mean NULL: no shift)
+ * mom[c] += sum_f z[f][c],  mom[D + c] += sum_f z[f][c]^2          (mom NULL: not formed; K = 0 with mom is allowed)
+ * Y: frames-first batch, element type elem, frame f at Y + f ldy elements (ldy >= D); X: K rows, ld ldx >= n, column f =
+ * frame f of the call; n <= PMD_REGRESS_BLOCK.  Every sum of the call is formed in fp32 in an order fixed by n alone,
+ * converted to double and added to acc / mom once; one owner per element: no atomics.  The bits a call adds to acc[k][c]
+ * depend on row k of X, column c of Y and mean[c] only: not on K, on the other rows, on ldy / ldx / lda, nor on the element
+ * type holding the same values.  No synchronisation, no allocation, no workspace. */
+int pmd_regress_accumulate(pmd_ctx* ctx, const void* Y, int elem, long ldy, int n, long D, const float* mean,
+                           const float* X, long ldx, int K, double* acc, long lda, double* mom);
+
 /* A2: background basis = rank-K rSVD of the standardised sample (pmd_loader.py:46-68, :300-314).
  * xs: pixel-major sample with round_up(D,1024) rows allocated (rows >= D zero). basis_out[c][k]. */
 size_t pmd_background_rsvd_workspace_bytes(long D, int n, int K);

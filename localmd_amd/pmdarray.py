@@ -151,6 +151,13 @@ class PMDArray:
 
         return extract_traces(self, rois, movie, **kw)
 
+    def maps(self, regressors, movie=None, **kw):
+        """Per-pixel maps of the denoised / raw / residual movie against the time courses ``regressors`` ((K, T) or
+        (T,)): sums, weighted means or correlations, computed on the GPU (maps.regressor_maps; same keywords)."""
+        from .maps import regressor_maps
+
+        return regressor_maps(self, regressors, movie, **kw)
+
     @property
     def _combined_temporal(self):
         """(R * s) V, built on first use and cached: __getitem__ is then one sparse-dense product
