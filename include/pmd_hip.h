@@ -158,6 +158,31 @@ int pmd_roi_combine(pmd_ctx* ctx, long K, int n, const float* C, long ldc, const
 int pmd_regress_accumulate(pmd_ctx* ctx, const void* Y, int elem, long ldy, int n, long D, const float* mean,
                            const float* X, long ldx, int K, double* acc, long lda, double* mom);
 
+/* Per-pixel summary images (localmd_amd/summary.py): extrema and power sums of one block of n frames of a batch. */
+#define PMD_STATS_BLOCK 1024
+/* Y: frames-first batch, element type elem (converted to fp32 exactly), frame f of the call at Y + f ldy elements
+ * (ldy >= D); 1 <= n <= PMD_STATS_BLOCK; f0: the frame number of the call's first frame, a multiple of bin, f0 + n < 2^31;
+ * bin: a power of two <= PMD_STATS_BLOCK.  The call's frames are taken in four slices of 256, slice w = frames
+ * [256 w, min(n, 256 w + 256)); a slice from n on is empty.
+ * ext != NULL (ext[c] the minimum, ext[D + c] the maximum; arg, which may be NULL, the frame numbers in the same layout):
+ *   bin == 1: the value of frame f is (float) Y[f][c], no arithmetic.  Otherwise the values are those of the bins
+ *   [b, min(n, b + bin)), b a multiple of bin: the fp32 sum of the bin's frames divided (IEEE) by their count.  The sum of
+ *   a bin <= 256 is one chain over its frames in ascending order, starting from the first frame's value; for bin = 512
+ *   and 1024 every slice of the bin is summed so and the slice sums are added in ascending slice order, starting from the
+ *   first.  A value v replaces ext[c] only if v < ext[c] and ext[D + c] only if v > ext[D + c], values in ascending frame
+ *   order, and arg gets f0 + (first frame of the bin): the first frame that attains an extremum keeps arg, within a call
+ *   and across calls in frame order; a NaN value never becomes an extremum.
+ * mom != NULL: z = fl((float) Y[f][c] - centre[c]) (centre NULL: no shift), mom[p D + c] += sum_f z^(p + 1), p = 0 .. 3,
+ *   the powers as z2 = fl(z z), fl(z2 z), fl(z2 z2).  Each sum is formed in fp32: one chain per slice over its frames in
+ *   ascending order from 0, the slice sums added in ascending slice order; then converted to double and added once.
+ * One owner per pixel: no atomics.  The bits written for pixel c depend on column c of Y, centre[c], n, f0, bin and the
+ * previous state only: not on D, ldy, the element type holding the same values, the pixel's position, or on which of
+ * ext / arg / mom the call forms.  Errors (nothing is launched): n out of range, bin not a power of two or too large, f0
+ * not a multiple of bin, ext and mom both NULL, arg without ext, unknown elem, ldy < D.  No synchronisation, no
+ * allocation, no workspace. */
+int pmd_pixel_stats_accumulate(pmd_ctx* ctx, const void* Y, int elem, long ldy, int n, long D, long f0, int bin,
+                               const float* centre, float* ext, int* arg, double* mom);
+
 /* A2: background basis = rank-K rSVD of the standardised sample (pmd_loader.py:46-68, :300-314).
  * xs: pixel-major sample with round_up(D,1024) rows allocated (rows >= D zero). basis_out[c][k]. */
 size_t pmd_background_rsvd_workspace_bytes(long D, int n, int K);

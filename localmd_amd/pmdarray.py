@@ -158,6 +158,13 @@ class PMDArray:
 
         return regressor_maps(self, regressors, movie, **kw)
 
+    def summary(self, movie=None, **kw):
+        """Per-pixel summary images of the denoised / raw / residual movie: mean, std, skewness, kurtosis, extrema with
+        their frames and peak-to-noise, computed on the GPU (summary.summary_images; same keywords)."""
+        from .summary import summary_images
+
+        return summary_images(self, movie, **kw)
+
     @property
     def _combined_temporal(self):
         """(R * s) V, built on first use and cached: __getitem__ is then one sparse-dense product
