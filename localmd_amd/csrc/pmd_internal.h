@@ -46,11 +46,12 @@ int pmd_launch_expand_pooled(pmd_ctx* ctx, const float* In, long in_tile_stride,
                              int n_tiles);
 int pmd_launch_stats_roughness(pmd_ctx* ctx, const float* Ut, long u_tile_stride, int u_ld, int b1, int b2,
                                const float* V, long v_tile_stride, long v_ld, int T, int r, float* stats, int n_tiles,
-                               int rp = PMD_RPAD);
+                               int rp);
 int pmd_launch_decide(pmd_ctx* ctx, const float* stats, int r, float thr_s, float thr_t, int max_fail, int cap,
-                      int n_tiles, int* good, int* keep, int* ranks, int rp = PMD_RPAD);
+                      int n_tiles, int* good, int* keep, int* ranks, int rp);
 
-// wide.hip: generic-width forms (per-tile arrays [tile][rp][x], rp = pmd_tile_rpad(r) > 64)
+// wide.hip: generic-width forms of the small dense algebra (per-tile arrays [tile][rp][x], rp = pmd_tile_rpad(r) > 64),
+// and the contractions in row blocks of 64 (any rp: nrows <= 64 is one launch of pmd_launch_tile_atx / _xbt)
 int pmd_launch_wide_gram(pmd_ctx* ctx, const float* In, long tile_stride, long ld, int len, int n_tiles, int slices, int rp,
                          double* G, const float* In2 = nullptr);
 size_t pmd_wide_eig_workspace_bytes(int n, int n_tiles);
@@ -100,8 +101,8 @@ int pmd_launch_tile_cross_gram(pmd_ctx* ctx, const float* A, const float* B, lon
                                double* G, int n_tiles);
 int pmd_launch_tile_residual_rows(pmd_ctx* ctx, const float* X, long ldx, const int* pix, int d, const float* E,
                                   int e_ld, const float* W, long w_ld, int r, int len, float* out, long out_ld,
-                                  int n_tiles, int rp = PMD_RPAD);
-int pmd_launch_tile_sub(pmd_ctx* ctx, float* a, const float* b, long tile_stride, int ld, int len, int n_tiles, int rp = PMD_RPAD);
+                                  int n_tiles, int rp);
+int pmd_launch_tile_sub(pmd_ctx* ctx, float* a, const float* b, long tile_stride, int ld, int len, int n_tiles, int rp);
 int pmd_launch_tile_append(pmd_ctx* ctx, const float* stats, int r, float thr_s, float thr_t, int max_fail, int cap,
                            const float* Unew, float* Ucur, int ld, int* counts, int* good, int* keep, int n_tiles,
-                           int rp = PMD_RPAD);
+                           int rp);

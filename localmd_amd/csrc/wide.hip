@@ -2,15 +2,17 @@
 // tile kernels are built on (max_components + 10 > 64, background_rank + 10 > 64; the reference's arguments are
 // unbounded: decomposition.py:643-665, :59-67).  Per-tile arrays are [tile][rp][x] with rp = a multiple of 64
 // (pmd_tile_rpad); the streaming contractions run as row blocks of 64 through tile_atx / tile_xbt (pmd_launch_tile_*_rp
-// below), the small dense algebra through the kernels of this file:
+// below, which pipeline.hip calls at every width: one launch at 64 rows), the small dense algebra through the kernels of
+// this file, which `tile_la` of pipeline.hip selects for rp > 64 step by step:
 //   wide_gram   : G[tile][slice][rp][rp] = In In^T over a slice of positions, fp64 accumulation of fp32 inputs
 //   wide_eig    : symmetric eigendecomposition of the summed n x n Gram matrices (rocSOLVER dsyevd, strided batch),
 //                 vectors ordered by descending eigenvalue; mode 1 = scaled by 1/sqrt(lambda) with the null rule of
 //                 small_eig (lambda <= tol * lambda_max -> zero column)
 //   wide_rowmix : Out[tile][c][x] = sum_c' N[tile][c'][c] In[tile][c'][x], fp64 accumulation, in-place safe
 // Same numerical policy as the 64-row path: every Gram matrix behind an SVD in fp64 from the fp32
-// data, eigenvectors in fp64.  This path is sized for correctness at any width, not tuned: the default arguments
-// (max_components = 50, background_rank = 15) never reach it.
+// data, eigenvectors in fp64.  The sequences of steps are those of the 64-row path, written once in pipeline.hip; there
+// is no Householder QR and no Cholesky whitening at these widths: eigen-whitening serves both.  This path is sized for
+// correctness at any width, not tuned: the default arguments (max_components = 50, background_rank = 15) never reach it.
 #include "pmd_internal.h"
 #include <rocsolver/rocsolver.h>
 

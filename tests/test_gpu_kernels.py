@@ -853,3 +853,52 @@ def test_comm_entry_points_single_rank(gpu_ctx):
             ctx.call("pmd_comm_init", uid, 0, 1)     # one communicator per context
     finally:
         ctx.call("pmd_comm_destroy")
+
+
+_LAUNCH_GROUPS = ("tile_xbt", "tile_atx", "tile_atx_main", "tile_gram", "tile_rowmix", "tile_cross_gram", "small_qr", "small_eig",
+                  "small_chol", "reduce_slices", "wide_gram", "wide_eig", "wide_rowmix", "rng_normal", "roughness", "decide")
+# case: ((frames, d1, d2, movie seed), frame_range, arguments, launches per group in the order of _LAUNCH_GROUPS)
+_LAUNCH_CASES = {
+    # test_full_pipeline_max_components_80: generic-width tiles, 64-row background
+    "max_components_80": ((1200, 40, 50, 21), 1200, dict(max_components=80, background_rank=3, sim_iters=10),
+                          (5, 4, 4, 3, 3, 0, 0, 1, 0, 5, 6, 6, 7, 2, 1, 1)),
+    # test_full_pipeline_multi_window_residual_max_components_70: generic-width tiles and residual window
+    "residual_max_components_70": ((1700, 40, 44, 31), 1600, dict(max_components=70, background_rank=2, sim_iters=10, window_chunks=800),
+                                   (7, 11, 5, 3, 3, 0, 0, 1, 0, 6, 10, 9, 11, 3, 2, 1)),
+    # test_full_pipeline_background_rank_60: generic-width background, 64-row tiles
+    "background_rank_60": ((800, 60, 60, 24), 800, dict(max_components=6, background_rank=60, sim_iters=10),
+                           (5, 4, 2, 3, 5, 0, 1, 2, 2, 62, 3, 3, 3, 2, 1, 1)),
+    # the small 64-row configuration, one window and with residual windows
+    "rows_64": ((600, 40, 50, 1), 600, dict(max_components=6, background_rank=2, sim_iters=10),
+                (4, 3, 2, 6, 8, 0, 1, 3, 2, 5, 0, 0, 0, 2, 1, 1)),
+    "rows_64_residual": ((600, 40, 50, 1), 600, dict(max_components=6, background_rank=2, sim_iters=10, window_chunks=200),
+                         (6, 9, 3, 8, 12, 2, 3, 5, 2, 5, 0, 0, 0, 4, 3, 1)),
+}
+
+
+@pytest.mark.parametrize("case", sorted(_LAUNCH_CASES))
+def test_tile_stage_launch_table(gpu_ctx, case):
+    """The tile stage, the residual window and the background rSVD are each sequenced once on the host for the 64-row and
+    the generic-width layout (csrc/pipeline.hip); which launcher a step takes is decided from shapes and
+    route switches alone.  So the number of launches of every group below is a fixed property of a configuration, and any
+    difference means that a sequence changed: the margin is zero.  The table was recorded with the library built from the
+    sources of the commit before the two copies of each sequence were merged (PMD_HIP_LIB selects the library), by running
+    this same decomposition with profiling on; it is not derived from the merged code."""
+    import localmd_amd
+    from localmd_amd import decomposition as Dm
+    from localmd_amd.synthetic import make_movie
+
+    (T, d1, d2, movie_seed), frame_range, kw, table = _LAUNCH_CASES[case]
+    Dm.QUIET = True
+    mov = make_movie(T, d1, d2, seed=movie_seed)
+    np.random.seed(7)
+    gpu_ctx.profile_enable(True)
+    try:
+        localmd_amd.localmd_decomposition(mov, (20, 20), frame_range, seed=123, ctx=gpu_ctx, **kw)
+        gpu_ctx.sync()
+        prof = gpu_ctx.profile_summary()
+    finally:
+        gpu_ctx.profile_enable(False)
+    counts = {g: (prof[g][1] if g in prof else 0) for g in _LAUNCH_GROUPS}
+    print(case, counts)
+    assert counts == dict(zip(_LAUNCH_GROUPS, table))

@@ -612,7 +612,7 @@ def test_full_pipeline_denoiser_hooks(gpu_ctx, which):
 
 def test_full_pipeline_denoiser_hooks_generic_width(gpu_ctx):
     """Both hooks on the generic-width tile path (max_components = 60: 128 component rows; the three resumable stages of
-    tiles_decompose_wide with the hook arrays at their rp-row offsets)."""
+    pmd_tiles_decompose_staged with the hook arrays at their rp-row offsets)."""
     mov = _movie(900, 40, 50, seed=33)
     kw = dict(max_components=60, background_rank=2, sim_iters=10, temporal_denoiser=_smooth_time, spatial_denoiser=_smooth_space)
     pmd, diag, ref = _compare_full(gpu_ctx, mov, (20, 20), 900, **kw)
