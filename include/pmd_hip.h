@@ -183,6 +183,27 @@ int pmd_regress_accumulate(pmd_ctx* ctx, const void* Y, int elem, long ldy, int 
 int pmd_pixel_stats_accumulate(pmd_ctx* ctx, const void* Y, int elem, long ldy, int n, long D, long f0, int bin,
                                const float* centre, float* ext, int* arg, double* mom);
 
+/* Exact per-pixel order statistics over time (localmd_amd/quantiles.py): a radix select over per-pixel histograms, most
+ * significant 8-bit digit first.  Key of element y of pixel c: v = (float) Y[f][c]; centre != NULL: v = |v - centre[c]|
+ * (one fp32 subtraction, round to nearest, no contraction; denormal differences are kept, not flushed).  key = ~bits(v)
+ * when the sign bit of v is set, bits(v) | 0x80000000 otherwise, 0xFFFFFFFF for every NaN: keys order as the values do,
+ * -0 before +0 and NaN last.
+ * hist: uint32 [ceil(D / 64)][256][64] indexed (pixel group, bin, pixel in group), 16-byte aligned, zero before the first
+ * call of a pass.
+ * pmd_pixel_hist_accumulate: for the n >= 1 frames of a frames-first batch (element type elem, frame f at Y + f ldy
+ * elements, ldy >= D; any n < 2^31, no block discipline: counting is order-free) element (f, c) is counted when pass == 0
+ * or key >> (32 - 8 pass) == prefix[c], in bin (key >> (24 - 8 pass)) & 255 of pixel c; pass in 0 .. 3, prefix may be NULL
+ * for pass 0.  One workgroup owns a pixel group: no global atomics.
+ * pmd_pixel_hist_select: per pixel c < D the first bin b whose cumulative count exceeds rank[c] (0 <= rank[c] < the
+ * pixel's count); rank[c] -= the count below b, prefix[c] = prefix[c] << 8 | b; a pixel whose rank is not below its count
+ * keeps rank and prefix.  Every count of hist is set to zero.  After the last pass prefix[c] is the key of the
+ * order statistic.
+ * Errors (nothing is launched): n < 1, D < 1, ldy < D, pass outside 0 .. 3, unknown elem, a NULL Y / hist / rank, prefix
+ * NULL where it is read, hist not 16-byte aligned.  No synchronisation, no allocation, no workspace. */
+int pmd_pixel_hist_accumulate(pmd_ctx* ctx, const void* Y, int elem, long ldy, long n, long D, const float* centre,
+                              int pass, const uint32_t* prefix, uint32_t* hist);
+int pmd_pixel_hist_select(pmd_ctx* ctx, long D, uint32_t* hist, int* rank, uint32_t* prefix);
+
 /* A2: background basis = rank-K rSVD of the standardised sample (pmd_loader.py:46-68, :300-314).
  * xs: pixel-major sample with round_up(D,1024) rows allocated (rows >= D zero). basis_out[c][k]. */
 size_t pmd_background_rsvd_workspace_bytes(long D, int n, int K);

@@ -12,6 +12,7 @@ from .export import export_movie
 from .traces import extract_traces
 from .maps import regressor_maps, event_regressors
 from .summary import summary_images
+from .quantiles import quantile_images
 
 PMDDataset = lazy_data_loader  # the name the reference's README uses (README.md:67)
 
@@ -19,5 +20,5 @@ __all__ = [
     "localmd_decomposition", "compute_lowrank_factorized_svd", "projected_svd", "PMDArray", "TiffArray",
     "lazy_data_loader", "PMDDataset", "ArrayDataset", "save_npz", "load_npz",
     "project_movie", "make_pmd_diagnostic_images", "export_movie", "extract_traces",
-    "regressor_maps", "event_regressors", "summary_images",
+    "regressor_maps", "event_regressors", "summary_images", "quantile_images",
 ]

@@ -46,6 +46,8 @@ SIGNATURES = {
     "pmd_roi_combine": (c_i, [c_p, c_l, c_i, c_p, c_l, c_p, c_p, c_l, c_p, c_l, c_p, c_l]),
     "pmd_regress_accumulate": (c_i, [c_p, c_p, c_i, c_l, c_i, c_l, c_p, c_p, c_l, c_i, c_p, c_l, c_p]),
     "pmd_pixel_stats_accumulate": (c_i, [c_p, c_p, c_i, c_l, c_i, c_l, c_l, c_i, c_p, c_p, c_p, c_p]),
+    "pmd_pixel_hist_accumulate": (c_i, [c_p, c_p, c_i, c_l, c_l, c_l, c_p, c_i, c_p, c_p]),
+    "pmd_pixel_hist_select": (c_i, [c_p, c_l, c_p, c_p, c_p]),
     "pmd_background_rsvd_workspace_bytes": (c_sz, [c_l, c_i, c_i]),
     "pmd_background_rsvd": (c_i, [c_p, c_p, c_l, c_i, c_l, c_i, c_u64, c_p, c_p, c_sz]),
     "pmd_bg_project_workspace_bytes": (c_sz, [c_l, c_i]),

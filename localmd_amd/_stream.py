@@ -1,6 +1,6 @@
 """
 One pass over a movie against a stored decomposition: what project_frames / project_movie, make_pmd_diagnostic_images,
-export_movie, extract_traces, regressor_maps and summary_images share.  The device context of a PMDArray, how a source is read (host sources through the
+export_movie, extract_traces, regressor_maps, summary_images and quantile_images share.  The device context of a PMDArray, how a source is read (host sources through the
 pinned staging ring of the streamed decomposition, device tensors sliced in place), the 1024-frame reconstruction blocks
 and the Vt columns of one, the uploaded statistics and R s, the host ring that results leave the device through, and
 the argument and device-memory checks the callers have in common.  No helper knows its caller.

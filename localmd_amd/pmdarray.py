@@ -165,6 +165,13 @@ class PMDArray:
 
         return summary_images(self, movie, **kw)
 
+    def quantiles(self, movie=None, **kw):
+        """Exact per-pixel quantile images over the frames of the denoised / raw / residual movie (median, baseline
+        percentiles) and the MAD noise image, computed on the GPU (quantiles.quantile_images; same keywords)."""
+        from .quantiles import quantile_images
+
+        return quantile_images(self, movie, **kw)
+
     @property
     def _combined_temporal(self):
         """(R * s) V, built on first use and cached: __getitem__ is then one sparse-dense product
