@@ -104,7 +104,7 @@ def test_overlap_pairs_cover_exactly_the_intersections():
 
 def test_sparse_assembly_is_bitwise_the_reference_construction():
     from localmd_amd.decomposition import _sparse_u
-    from scipy.sparse import coo_matrix, diags
+    from tests.util import reference_sparse_u
 
     rng = np.random.default_rng(0)
     for order in ("F", "C"):
@@ -124,21 +124,7 @@ def test_sparse_assembly_is_bitwise_the_reference_construction():
         inv[fov.reshape(-1)] = 1 / cumw.reshape(-1)
         mine, off = _sparse_u(ut, ranks, fov.reshape(-1)[pix], bw, inv, d1 * d2)
         # the reference's construction (decomposition.py:812-853), literally
-        rows_l, cols_l, vals_l, col, cw = [], [], [], 0, np.zeros((d1, d2))
-        for t, (k, j) in enumerate(origins):
-            sp = ut[t, :ranks[t], :].T.reshape((b, b, ranks[t]), order="F").astype(np.float64) * bw[:, :, None]
-            cw[k:k + b, j:j + b] += bw
-            ridx = fov[k:k + b, j:j + b][:, :, None] + np.zeros((1, 1, ranks[t]))
-            cidx = np.zeros_like(ridx) + np.arange(col, col + ranks[t])[None, None, :]
-            rows_l += ridx.flatten().tolist()
-            cols_l += cidx.flatten().tolist()
-            vals_l += sp.flatten().tolist()
-            col += ranks[t]
-        ref = coo_matrix((vals_l, (rows_l, cols_l)), shape=(d1 * d2, col))
-        wnd = np.zeros(d1 * d2)
-        wnd[fov.flatten(order=order)] = cw.flatten(order=order)
-        ref = diags([(1 / wnd).ravel()], [0]).dot(ref).tocsr()
-        ref.sort_indices()
+        ref = reference_sparse_u(ut, ranks, origins, (d1, d2), (b, b), order, bw)
         a = mine.tocsr()
         a.sort_indices()
         assert a.shape == ref.shape

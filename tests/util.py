@@ -51,6 +51,36 @@ class DeviceSource:
         return z.reshape(d2, d1, t).transpose(1, 0, 2)
 
 
+def reference_sparse_u(ut, ranks, origins, fov_shape, block, order, block_weights):
+    """The reference's sparse assembly (decomposition.py:812-853), literally: per tile the float64 components times the
+    pyramid weights as COO triplets, the accumulated weights, then the row normalisation as a diagonal product (which drops
+    exact zeros).  ut: (n_tiles, component rows, >= b1 * b2) float32, tile pixel q = il + b1 * jl.  Returns the CSR matrix
+    (D x sum(ranks), sorted indices) with rows in `order` of the field of view."""
+    from scipy.sparse import coo_matrix, diags
+
+    d1, d2 = fov_shape
+    b1, b2 = block
+    d = b1 * b2
+    fov = np.arange(d1 * d2).reshape((d1, d2), order=order)
+    rows_l, cols_l, vals_l, col, cw = [], [], [], 0, np.zeros((d1, d2))
+    for t, (k, j) in enumerate(origins):
+        rk = int(ranks[t])
+        sp = ut[t, :rk, :d].T.reshape((b1, b2, rk), order="F").astype(np.float64) * block_weights[:, :, None]
+        cw[k:k + b1, j:j + b2] += block_weights
+        ridx = fov[k:k + b1, j:j + b2][:, :, None] + np.zeros((1, 1, rk))
+        cidx = np.zeros_like(ridx) + np.arange(col, col + rk)[None, None, :]
+        rows_l += ridx.flatten().tolist()
+        cols_l += cidx.flatten().tolist()
+        vals_l += sp.flatten().tolist()
+        col += rk
+    ref = coo_matrix((vals_l, (rows_l, cols_l)), shape=(d1 * d2, col))
+    wnd = np.zeros(d1 * d2)
+    wnd[fov.flatten(order=order)] = cw.flatten(order=order)
+    ref = diags([(1 / wnd).ravel()], [0]).dot(ref).tocsr()
+    ref.sort_indices()
+    return ref
+
+
 def sign_align(a, b, axis=0):
     """Flip the sign of each column (axis=0) / row (axis=1) of ``a`` to best match ``b``."""
     dots = np.sum(a * b, axis=axis, keepdims=True)
