@@ -1,9 +1,11 @@
 """
 One pass over a movie against a stored decomposition: what project_frames / project_movie, make_pmd_diagnostic_images,
-export_movie, extract_traces, regressor_maps, summary_images and quantile_images share.  The device context of a PMDArray, how a source is read (host sources through the
-pinned staging ring of the streamed decomposition, device tensors sliced in place), the 1024-frame reconstruction blocks
-and the Vt columns of one, the uploaded statistics and R s, the host ring that results leave the device through, and
-the argument and device-memory checks the callers have in common.  No helper knows its caller.
+export_movie, extract_traces, regressor_maps, summary_images and quantile_images share.  The device context of a
+PMDArray, how a source is read (host sources through the pinned staging ring of the streamed decomposition, device
+tensors sliced in place), the 1024-frame reconstruction blocks, the walk over the blocks of a batch and the Vt columns
+of one, the uploaded statistics and R s, the host ring that results leave the device through, and the argument and
+device-memory checks the callers have in common.  Rebuilding a block of the denoised or residual movie from these is
+_expand's.  No helper knows its caller.
 """
 import contextlib
 
@@ -52,6 +54,30 @@ def block_plan(T, frame_batch_size, block=BLOCK):
 
     return [(b0, b1, [(c0, min(b1, c0 + block)) for c0 in range(b0, b1, block)])
             for b0, b1 in _stream_batches(T, frame_batch_size)]
+
+
+def factor_bytes(n_cols, rank, factors_on_device):
+    """Device bytes of the factors a block product reads: one block of Vt columns (VtBlocks), and R s (scaled_r) unless
+    the PMDArray already holds it on the device; nothing for a decomposition without columns or rank."""
+    if rank <= 0 or n_cols <= 0:
+        return 0
+    return 4 * rank * BLOCK + (0 if factors_on_device else 4 * n_cols * rank)
+
+
+def block_walk(plan, D):
+    """walk(batch, b0) for the ``consume`` of read_batches: yields (c0, m, yp) for every reconstruction block of the
+    batch of ``plan`` (block_plan) that starts at frame b0: its m frames from c0 on and the device address of frame c0
+    in the batch of D-pixel frames, None without a movie."""
+    import ctypes as C
+
+    blocks_of = {b0: blocks for b0, _, blocks in plan}
+
+    def walk(batch, b0):
+        for c0, c1 in blocks_of[b0]:
+            yield c0, c1 - c0, (C.c_void_p(batch.data_ptr() + (c0 - b0) * D * batch.element_size())
+                                if batch is not None else None)
+
+    return walk
 
 
 def _device_elem(t):

@@ -12,29 +12,29 @@ Hot path: the movie is read once in the frame batches of the streamed decomposit
 block (blocks start on multiples of 1024 whatever the batch size, so every product has the same shape and every output
 bit is the same for every batching and source) goes through ``pmd_gemm`` (C = (R s) Vt[:, block]) and one fused kernel,
 ``pmd_group_expand`` (csrc/expand_fused.hip), from C to finished output frames.  The kernel walks, per 64-pixel patch,
-the groups of U's columns that touch it (projection.group_tables, cached on the PMDArray and shared with
-project_frames; the per-patch lists are built here).  Reading the movie, the block plan and the Vt columns of a block
-are those of _stream, shared with extract_traces.  Host destinations get each block through a ring of two device
-and two page-locked buffers: the copy to the host runs on a side stream and a writer thread puts the frames into the
-file or array while the next block computes.  Device memory and host memory do not grow with the movie's length.
+the groups of U's columns that touch it (projection.group_tables, cached on the PMDArray and shared with project_frames;
+the per-patch lists are built here).  Reading the movie and the block plan are those of _stream, the two calls of a
+block those of _expand.Expander, shared with regressor_maps, summary_images and quantile_images.  Host destinations get
+each block through a ring of two device and two page-locked buffers: the copy to the host runs on a side stream and a
+writer thread puts the frames into the file or array while the next block computes.  Device memory and host memory do
+not grow with the movie's length.
 """
+import itertools
 import os
 import queue
 import threading
 
 import numpy as np
 
+from ._expand import ENTRY_FIELDS, EXPORT_PATCH, _PANEL_CODE, Expander, expander_bytes, panel_code  # noqa: F401
 from ._stream import BLOCK as EXPORT_BLOCK, block_plan as export_plan
-from ._stream import (VtBlocks, batch_buffer_bytes, check_fit, device_context, mean_std, name_tuple, read_batches, scaled_r,
-                      source_info, upload_f32)
+from ._stream import (batch_buffer_bytes, block_walk, check_fit, device_context, name_tuple, read_batches,
+                      source_info)
 from .projection import MAX_ROWS, P_MAX, ROW_PAD, _pad, tables_for
 
-EXPORT_PATCH = 64       # pixels per patch of pmd_group_expand
-ENTRY_FIELDS = 4        # {a_off, p64, r, c_row0}
 HOST_SLOTS = 2          # device + page-locked output buffers of a host destination
 COPY_THREADS = 8        # threads that copy a block into a NumPy destination
 PANELS = ("raw", "denoised", "residual")
-_PANEL_CODE = {"raw": 0, "denoised": 1, "residual": 2}
 _OUT_DTYPES = {"float32": np.float32, "uint16": np.uint16, "int16": np.int16}
 _ELEM = {np.dtype(np.float32): 0, np.dtype(np.uint16): 1, np.dtype(np.int16): 2}   # PMD_ELEM_F32 / _U16 / _I16
 
@@ -256,18 +256,13 @@ def export_device_bytes(D, nb, esize, n_panels, out_esize, n_cols, rank, n_entri
     """Device bytes export_movie holds for a movie of D pixels read in batches of nb frames; no term grows with the
     movie's length.  Batch buffers (two for a host source, a converted copy at most for a device tensor), one block of
     Vt columns and of C, the output ring of a host destination, the tables, mean and std, and R s unless the PMDArray
-    already holds it on the device."""
-    B = EXPORT_BLOCK
-    need = 0
+    already holds it on the device (expander_bytes; C is counted only where a product fills it)."""
+    need = expander_bytes(D=D, n_cols=n_cols, rank=rank, n_entries=n_entries, n_a=n_a, n_patches=n_patches,
+                          factors_on_device=factors_on_device, own_ct=rank > 0)
     if needs_movie:
         need += batch_buffer_bytes(nb, D, esize, host_source, n_batches)
-    if rank > 0 and n_cols > 0:
-        need += 4 * (rank * B + n_cols * B)
-        if not factors_on_device:
-            need += 4 * n_cols * rank
     if host_dest:
-        need += HOST_SLOTS * B * D * n_panels * out_esize
-    need += 8 * (n_patches + 1) + n_entries * (8 * ENTRY_FIELDS + 4 * EXPORT_PATCH) + 4 * n_a + 2 * 4 * D
+        need += HOST_SLOTS * EXPORT_BLOCK * D * n_panels * out_esize
     return need + (1 << 20)     # the allocator's rounding of the small arrays
 
 
@@ -428,50 +423,25 @@ class _DeviceSink:
 def _export(ctx, pmd, dv, tabs, xt, movie, plan, panels, out_dtype, dest, frame_batch_size, num_workers):
     import ctypes as C
 
-    import torch
-    from ._lib import ptr
-
     T, d1, d2 = (int(x) for x in pmd.shape)
     D = d1 * d2
-    dev = ctx.device
-    n_cols, rank = (int(x) for x in pmd.r.shape)
     P = len(panels)
-    code = 0
-    for k, p in enumerate(panels):
-        code |= _PANEL_CODE[p] << (2 * k)
+    code = panel_code(panels)
     out_elem = _ELEM[out_dtype]
     frame_bytes = D * P * out_dtype.itemsize
-    mean, std = mean_std(ctx, pmd)
-    n_ent = len(xt["entries"])
-    patch_ptr = torch.from_numpy(xt["patch_ptr"]).to(dev)
-    entries = torch.from_numpy(np.ascontiguousarray(xt["entries"]).reshape(-1)).to(dev) if n_ent else None
-    qmap = torch.from_numpy(xt["qmap"]).to(dev) if n_ent else None
-    A = upload_f32(ctx, tabs["a"]) if n_ent else None
-    expand = n_cols > 0 and n_ent > 0
-    B = EXPORT_BLOCK
-    ct = torch.zeros((n_cols, B), dtype=torch.float32, device=dev) if expand else None
-    if expand and rank > 0:
-        rs = scaled_r(ctx, pmd, dv)
-        vt = VtBlocks(ctx, pmd, dv)
+    ex = Expander(ctx, pmd, dv, tabs, xt)
 
     if dest.kind == "device":
         sink = _DeviceSink(dest.target, frame_bytes)
     else:
-        sink = _HostSink(ctx, dest, frame_bytes, (d1, P * d2), out_dtype, max(1, min(T, B)))
-    kb = {"k": 0}
-    blocks_of = {b0: blocks for b0, _, blocks in plan}
+        sink = _HostSink(ctx, dest, frame_bytes, (d1, P * d2), out_dtype, max(1, min(T, EXPORT_BLOCK)))
+    walk, count = block_walk(plan, D), itertools.count()
 
     def consume(batch, elem, b0, n):
-        for c0, c1 in blocks_of[b0]:
-            m = c1 - c0
-            if expand and rank > 0:
-                vt.load(c0, m)
-                ctx.call("pmd_gemm", 0, 0, n_cols, m, rank, 1.0, ptr(rs), rank, ptr(vt.buf), B, 0.0, ptr(ct), B)
-            k = kb["k"]
-            kb["k"] += 1
-            yp = C.c_void_p(batch.data_ptr() + (c0 - b0) * D * batch.element_size()) if batch is not None else None
-            ctx.call("pmd_group_expand", ptr(ct), B, m, d1, d2, ptr(mean), ptr(std), int(xt["n_patches"]), ptr(patch_ptr),
-                     n_ent, ptr(entries), ptr(qmap), ptr(A), yp, int(elem), D, P, code, C.c_void_p(sink.dst(k, c0)), out_elem)
+        for c0, m, yp in walk(batch, b0):
+            ex.coefficients(c0, m)
+            k = next(count)
+            ex.expand(m, P, code, yp, elem, out=C.c_void_p(sink.dst(k, c0)), out_elem=out_elem)
             sink.done(k, c0, m)
 
     try:

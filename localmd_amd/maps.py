@@ -21,12 +21,12 @@ source.  The movie is read once through the scaffold of _stream; device memory d
 """
 import numpy as np
 
-from ._stream import (BLOCK, VtBlocks, batch_buffer_bytes, block_plan, check_fit, device_context, mean_std, name_tuple,
-                      read_batches, scaled_r, source_info, upload_f32)
+from ._expand import Expander, expander_bytes, interleave, panel_code, split_panels
+from ._stream import (BLOCK, batch_buffer_bytes, block_plan, block_walk, check_fit, device_context, name_tuple,
+                      read_batches, source_info, upload_f32)
 
 KINDS = ("denoised", "raw", "residual")
 STATS = ("sum", "mean", "correlation")
-_PANEL_CODE = {"denoised": 1, "residual": 2}     # panel codes of pmd_group_expand
 GAMMA = (BLOCK + 8) * 2.0 ** -24                  # forward error of one block's fp32 sums, relative to the sum of magnitudes
 
 
@@ -122,14 +122,12 @@ def maps_device_bytes(*, D, nb, esize, K, n_acc, n_expand, n_cols, rank, n_entri
     need = 8 * n_acc * (K + 2) * D + 4 * K * BLOCK + 2 * 4 * D
     if needs_movie:
         need += batch_buffer_bytes(nb, D, esize, host_source, n_batches)
-    if n_expand or factor_sums:
-        need += 8 * (n_patches + 1) + n_entries * (8 * 4 + 4 * 64) + 4 * n_a
-        if rank > 0 and n_cols > 0:
-            need += 4 * rank * BLOCK
-            if not factors_on_device:
-                need += 4 * n_cols * rank
+    if n_expand or factor_sums:     # the mean and std images are counted above, whatever runs
+        need += expander_bytes(D=D, n_cols=n_cols, rank=rank, n_entries=n_entries, n_a=n_a, n_patches=n_patches,
+                               factors_on_device=factors_on_device, stats=False, own_ct=bool(n_expand),
+                               block_panels=n_expand)
     if n_expand:
-        need += 4 * n_expand * BLOCK * D + 4 * n_expand * D + 4 * n_cols * BLOCK
+        need += 4 * n_expand * D
     if factor_sums:
         need += 16 * rank * K + 4 * n_cols * K + 4 * K * D + 4 * D
     return need + (1 << 20)     # the allocator's rounding of the small arrays
@@ -206,38 +204,8 @@ def regressor_maps(pmd, regressors, movie=None, *, kinds="denoised", stat="sum",
     return Maps(**{k: out[k].reshape(K, d1, d2) for k in kinds})
 
 
-class _Expander:
-    """The tables of pmd_group_expand on the device and the coefficient block C = (R s) Vt[:, block]."""
-
-    def __init__(self, ctx, pmd, dv, tabs, xt):
-        import torch
-
-        dev = ctx.device
-        self.ctx = ctx
-        _, self.d1, self.d2 = (int(x) for x in pmd.shape)
-        self.n_cols, self.rank = (int(x) for x in pmd.r.shape)
-        self.n_patches, self.n_ent = int(xt["n_patches"]), len(xt["entries"])
-        self.patch_ptr = torch.from_numpy(xt["patch_ptr"]).to(dev)
-        self.entries = torch.from_numpy(np.ascontiguousarray(xt["entries"]).reshape(-1)).to(dev) if self.n_ent else None
-        self.qmap = torch.from_numpy(xt["qmap"]).to(dev) if self.n_ent else None
-        self.A = upload_f32(ctx, tabs["a"]) if self.n_ent else None
-        self.active = self.n_cols > 0 and self.n_ent > 0
-        self.product = self.active and self.rank > 0
-        self.rs = scaled_r(ctx, pmd, dv) if self.product else None
-
-    def expand(self, C, ldc, n, mean, std, Y, elem, n_panels, code, out):
-        """out (n frames of n_panels side-by-side panels, fp32) from the coefficients C (n_cols x ldc, column f = frame f)."""
-        from ._lib import ptr
-
-        self.ctx.call("pmd_group_expand", ptr(C), int(ldc), int(n), self.d1, self.d2, ptr(mean), ptr(std), self.n_patches,
-                      ptr(self.patch_ptr), self.n_ent, ptr(self.entries), ptr(self.qmap), ptr(self.A), Y, int(elem),
-                      self.d1 * self.d2, int(n_panels), int(code), ptr(out), 0)
-
-
 def _maps(ctx, pmd, dv, tabs, xt, x64, movie, plan, kinds, stat, do_raw, panels, factor_sums, frame_batch_size,
           num_workers):
-    import ctypes as C
-
     import torch
     from ._lib import ptr
 
@@ -251,55 +219,41 @@ def _maps(ctx, pmd, dv, tabs, xt, x64, movie, plan, kinds, stat, do_raw, panels,
     x32 = np.ascontiguousarray(xdev64, dtype=np.float32)              # what the device multiplies with
     x_host = torch.from_numpy(x32)
     xb = torch.zeros((K, BLOCK), dtype=torch.float32, device=dev)     # the regressors of one block
-    mean, std = mean_std(ctx, pmd)
     mean32 = np.asarray(pmd.mean_img, dtype=np.float32).reshape(-1).astype(np.float64)
     centre32 = centring_vector(pmd)
     centre = upload_f32(ctx, centre32) if do_raw else None
 
     acc_raw = torch.zeros((K, D), dtype=torch.float64, device=dev) if do_raw else None
     mom_raw = torch.zeros(2 * D, dtype=torch.float64, device=dev) if do_raw and corr else None
-    ex = _Expander(ctx, pmd, dv, tabs, xt) if (P or factor_sums) else None
-    vt = VtBlocks(ctx, pmd, dv) if ex is not None and ex.product else None
+    ex = Expander(ctx, pmd, dv, tabs, xt, own_ct=bool(P), block_panels=P) if (P or factor_sums) else None
+    code = panel_code(panels)
     if P:
-        code = 0
-        for j, k in enumerate(panels):
-            code |= _PANEL_CODE[k] << (2 * j)
-        # the expanded block: frame f holds its panels side by side, pixel (i, j) of panel p at i P d2 + p d2 + j; the
-        # kernel takes it as a batch of P D "pixels" whose centring vector is the mean image under the denoised panel
-        # and 0 under the residual panel
-        block = torch.empty((BLOCK, P * D), dtype=torch.float32, device=dev)
-        shift = np.zeros((d1, P, d2), dtype=np.float32)
-        if "denoised" in panels:
-            shift[:, panels.index("denoised"), :] = np.asarray(pmd.mean_img, dtype=np.float32).reshape(d1, d2)
-        shift = upload_f32(ctx, shift.reshape(-1))
+        # the kernel takes the expanded block as a batch of P D "pixels" whose centring vector is the mean image under
+        # the denoised panel and 0 under the residual panel
+        centres = {"denoised": mean32.astype(np.float32), "residual": np.zeros(D, np.float32)}
+        shift = upload_f32(ctx, interleave([centres[k] for k in panels], d1, d2))
         acc_ex = torch.zeros((K, P * D), dtype=torch.float64, device=dev)
         mom_ex = torch.zeros(2 * P * D, dtype=torch.float64, device=dev)
-        ct = torch.zeros((ex.n_cols, BLOCK), dtype=torch.float32, device=dev) if ex.active else None
     if factor_sums and ex.product:
         g64 = torch.zeros((ex.rank, K), dtype=torch.float64, device=dev)
         gb = torch.empty((ex.rank, K), dtype=torch.float32, device=dev)
-    blocks_of = {b0: blocks for b0, _, blocks in plan}
+    walk = block_walk(plan, D)
 
     def consume(batch, elem, b0, n):
-        for c0, c1 in blocks_of[b0]:
-            m = c1 - c0
-            xb[:, :m].copy_(x_host[:, c0:c1])         # a blocking copy from pageable memory, once per block
-            if vt is not None:
-                vt.load(c0, m)
-            yp = C.c_void_p(batch.data_ptr() + (c0 - b0) * D * batch.element_size()) if batch is not None else None
+        for c0, m, yp in walk(batch, b0):
+            xb[:, :m].copy_(x_host[:, c0:c0 + m])         # a blocking copy from pageable memory, once per block
             if do_raw:
-                ctx.call("pmd_regress_accumulate", yp, int(elem), D, m, D, ptr(centre), ptr(xb), BLOCK, K, ptr(acc_raw), D,
-                         ptr(mom_raw))
+                ctx.call("pmd_regress_accumulate", yp, int(elem), D, m, D, ptr(centre), ptr(xb), BLOCK, K, ptr(acc_raw),
+                         D, ptr(mom_raw))
             if P:
-                if ex.product:
-                    ctx.call("pmd_gemm", 0, 0, ex.n_cols, m, ex.rank, 1.0, ptr(ex.rs), ex.rank, ptr(vt.buf), BLOCK, 0.0,
-                             ptr(ct), BLOCK)
-                ex.expand(ct, BLOCK, m, mean, std, yp, elem, P, code, block)
-                ctx.call("pmd_regress_accumulate", ptr(block), 0, P * D, m, P * D, ptr(shift), ptr(xb), BLOCK, K,
+                ex.coefficients(c0, m)
+                ex.expand(m, P, code, yp, elem)
+                ctx.call("pmd_regress_accumulate", ptr(ex.block), 0, P * D, m, P * D, ptr(shift), ptr(xb), BLOCK, K,
                          ptr(acc_ex), P * D, ptr(mom_ex))
             if factor_sums and ex.product:
                 # G += Vt[:, block] X[:, block]^T: every block product has the same shape; fp64 across the blocks
-                ctx.call("pmd_gemm", 0, 1, ex.rank, K, m, 1.0, ptr(vt.buf), BLOCK, ptr(xb), BLOCK, 0.0, ptr(gb), K)
+                ex.vt.load(c0, m)
+                ctx.call("pmd_gemm", 0, 1, ex.rank, K, m, 1.0, ptr(ex.vt.buf), BLOCK, ptr(xb), BLOCK, 0.0, ptr(gb), K)
                 g64.add_(gb)
 
     read_batches(ctx, movie, [(b0, b1) for b0, b1, _ in plan], frame_batch_size, num_workers, consume)
@@ -313,7 +267,7 @@ def _maps(ctx, pmd, dv, tabs, xt, x64, movie, plan, kinds, stat, do_raw, panels,
             ctx.call("pmd_gemm", 0, 0, ex.n_cols, K, ex.rank, 1.0, ptr(ex.rs), ex.rank, ptr(g32), K, 0.0, ptr(cm), K)
             img = torch.empty((K, D), dtype=torch.float32, device=dev)
             zero = torch.zeros(D, dtype=torch.float32, device=dev)
-            ex.expand(cm, K, K, zero, std, None, 0, 1, _PANEL_CODE["denoised"], img)
+            ex.expand(K, 1, panel_code(("denoised",)), None, 0, out=ptr(img), coeff=cm, ldc=K, mean=zero)
             ctx.sync()
             den_img = img.cpu().numpy().astype(np.float64)
         else:
@@ -342,11 +296,10 @@ def _maps(ctx, pmd, dv, tabs, xt, x64, movie, plan, kinds, stat, do_raw, panels,
         m = mom_raw.cpu().numpy()
         out["raw"] = _pearson(acc_raw.cpu().numpy(), m[:D], m[D:], sx, sxx, T)
     if P:
-        a = acc_ex.cpu().numpy().reshape(K, d1, P, d2)
-        m = mom_ex.cpu().numpy().reshape(2, d1, P, d2)
+        a = split_panels(acc_ex.cpu().numpy(), d1, P, d2)
+        m = split_panels(mom_ex.cpu().numpy().reshape(2, P * D), d1, P, d2)
         for j, k in enumerate(panels):
-            out[k] = _pearson(np.ascontiguousarray(a[:, :, j, :]).reshape(K, D), m[0, :, j, :].reshape(-1),
-                              m[1, :, j, :].reshape(-1), sx, sxx, T)
+            out[k] = _pearson(a[j], m[j][0], m[j][1], sx, sxx, T)
     return out
 
 

@@ -12,8 +12,8 @@ movie along time needs all of it at once; on the device an exact answer is a rad
   (``pmd_pixel_hist_accumulate``, the whole batch in one call), and ``pmd_pixel_hist_select`` then picks the bin that
   holds the rank looked for.  Four passes, most significant digit first, leave the key of the order statistic.
 * raw: the batch goes to the kernel in place and in its own dtype.  denoised and residual: the 1024-frame blocks are
-  expanded on the device by the recipe of summary_images and the expanded block goes to the same kernel as a batch of
-  P D pixels.
+  expanded on the device by _expand.Expander, as in summary_images, and the expanded block goes to the same kernel as a
+  batch of P D pixels.
 * the first pass counts every element, so one histogram per kind serves every rank; later passes count once per
   distinct rank, on the batch already on the device.
 * the host turns the keys back into floats (key_floats) and finishes the interpolation in float64 (finish_linear).
@@ -22,9 +22,10 @@ The device only counts integers, so every output bit is the same for every batch
 """
 import numpy as np
 
-from ._stream import (BLOCK, VtBlocks, batch_buffer_bytes, block_plan, check_fit, device_context, mean_std, name_tuple,
+from ._expand import Expander, expander_bytes, interleave, panel_code, split_panels
+from ._stream import (batch_buffer_bytes, block_plan, block_walk, check_fit, device_context, name_tuple,
                       read_batches, source_info, upload_f32)
-from .maps import _PANEL_CODE, KINDS, _Expander
+from .maps import KINDS
 
 INTERPOLATIONS = ("linear", "lower", "higher", "nearest")
 MAD_TO_STD = 1.4826          # std of a normal variable = MAD_TO_STD * its MAD
@@ -127,12 +128,8 @@ def quantile_device_bytes(*, D, nb, esize, n_raw, n_expand, n_pos, centred, n_co
     if needs_movie:
         need += batch_buffer_bytes(nb, D, esize, host_source, n_batches)
     if n_expand:
-        need += 8 * (n_patches + 1) + n_entries * (8 * 4 + 4 * 64) + 4 * n_a + 2 * 4 * D
-        need += 4 * n_expand * BLOCK * D + 4 * n_cols * BLOCK
-        if rank > 0 and n_cols > 0:
-            need += 4 * rank * BLOCK
-            if not factors_on_device:
-                need += 4 * n_cols * rank
+        need += expander_bytes(D=D, n_cols=n_cols, rank=rank, n_entries=n_entries, n_a=n_a, n_patches=n_patches,
+                               factors_on_device=factors_on_device, block_panels=n_expand)
     return need + (1 << 20)     # the allocator's rounding of the small arrays
 
 
@@ -263,67 +260,43 @@ class _Select:
 
 
 class _Rounds:
-    """What the selection rounds of one quantile_images call share: the expansion tables and buffers, the plan."""
+    """What the selection rounds of one quantile_images call share: the expander with its block, the plan."""
 
     def __init__(self, ctx, pmd, dv, tabs, xt, movie, plan, do_raw, panels, sixteen, frame_batch_size, num_workers):
-        import torch
-
         self.ctx, self.pmd, self.movie, self.plan = ctx, pmd, movie, plan
         self.do_raw, self.panels, self.sixteen = do_raw, panels, sixteen
         self.fbs, self.nw = frame_batch_size, num_workers
         _, self.d1, self.d2 = (int(x) for x in pmd.shape)
         self.D, self.P = self.d1 * self.d2, len(panels)
-        if self.P:
-            dev = ctx.device
-            self.mean, self.std = mean_std(ctx, pmd)
-            self.ex = _Expander(ctx, pmd, dv, tabs, xt)
-            self.vt = VtBlocks(ctx, pmd, dv) if self.ex.product else None
-            self.code = 0
-            for j, k in enumerate(panels):
-                self.code |= _PANEL_CODE[k] << (2 * j)
-            # the expanded block: frame f holds its panels side by side, pixel (i, j) of panel p at i P d2 + p d2 + j;
-            # the kernel takes it as a batch of P D "pixels"
-            self.block = torch.empty((BLOCK, self.P * self.D), dtype=torch.float32, device=dev)
-            self.ct = torch.zeros((self.ex.n_cols, BLOCK), dtype=torch.float32, device=dev) if self.ex.active else None
+        # the histogram kernel takes the expanded block as a batch of P D "pixels"
+        self.ex = Expander(ctx, pmd, dv, tabs, xt, block_panels=self.P) if self.P else None
 
     def select(self, ranks, centres):
         """{kind: (len(ranks), D) float32}: the order statistics ``ranks`` of every kind, of |y - centres[kind]| when
         ``centres`` is given."""
-        import ctypes as C
-
         from ._lib import ptr
 
-        ctx, D, P, d1, d2, panels = self.ctx, self.D, self.P, self.d1, self.d2, self.panels
+        ctx, D, P, d1, d2, panels, ex = self.ctx, self.D, self.P, self.d1, self.d2, self.panels, self.ex
+        code = panel_code(panels)
         raw = expanded = None
         raw_passes = 3 if self.sixteen and centres is None else 4
         if self.do_raw:
             raw = _Select(ctx, D, ranks, None if centres is None else centres["raw"])
         if P:
-            shift = None
-            if centres is not None:
-                shift = np.empty((d1, P, d2), dtype=np.float32)
-                for j, k in enumerate(panels):
-                    shift[:, j, :] = centres[k].reshape(d1, d2)
-                shift = shift.reshape(-1)
+            shift = None if centres is None else interleave([centres[k] for k in panels], d1, d2)
             expanded = _Select(ctx, P * D, ranks, shift)
-        blocks_of = {b0: blocks for b0, _, blocks in self.plan}
-        ex = self.ex if P else None
+        walk = block_walk(self.plan, D)
 
         for p in range(4 if P else raw_passes):
             def consume(batch, elem, b0, n):
                 if raw is not None and p < raw_passes:
-                    raw.accumulate(ctx, ptr(batch), elem, n, p)
+                    raw.accumulate(ctx, ptr(batch), elem, n, p)      # the whole batch in one call
                 if not P:
                     return
-                for c0, c1 in blocks_of[b0]:
-                    m = c1 - c0
-                    yp = C.c_void_p(batch.data_ptr() + (c0 - b0) * D * batch.element_size()) if batch is not None else None
-                    if ex.product:
-                        self.vt.load(c0, m)
-                        ctx.call("pmd_gemm", 0, 0, ex.n_cols, m, ex.rank, 1.0, ptr(ex.rs), ex.rank, ptr(self.vt.buf), BLOCK,
-                                 0.0, ptr(self.ct), BLOCK)
-                    ex.expand(self.ct, BLOCK, m, self.mean, self.std, yp, elem, P, self.code, self.block)
-                    expanded.accumulate(ctx, ptr(self.block), 0, m, p)
+                for c0, m, yp in walk(batch, b0):
+                    ex.coefficients(c0, m)
+                    ex.expand(m, P, code, yp, elem)
+                    expanded.accumulate(ctx, ptr(ex.block), 0, m, p)
 
             # a pass that only the denoised panel still needs reads no movie
             movie = self.movie if (raw is not None and p < raw_passes) or "residual" in panels else None
@@ -338,7 +311,5 @@ class _Rounds:
         if raw is not None:
             out["raw"] = raw.values(raw_passes)
         if P:
-            v = expanded.values(4).reshape(len(ranks), d1, P, d2)
-            for j, k in enumerate(panels):
-                out[k] = np.ascontiguousarray(v[:, :, j, :]).reshape(len(ranks), D)
+            out.update(zip(panels, split_panels(expanded.values(4), d1, P, d2)))
         return out

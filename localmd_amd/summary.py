@@ -10,9 +10,8 @@ so every pixel of every frame is looked at, once:
 * raw: every 1024-frame block of every batch, in the movie's own dtype and from the batch in place, goes through
   ``pmd_pixel_stats_accumulate`` (csrc/stats.hip), which keeps the running extrema (fp32, with int32 frame numbers) and
   the four power sums about a centring vector (fp32 within a block, fp64 across blocks) on the device.
-* denoised and residual: the block is expanded on the device by the recipe of export_movie and regressor_maps
-  (``pmd_gemm`` of R s with the Vt block, ``pmd_group_expand``) and the same kernel takes the expanded buffer as a batch
-  of P D pixels.
+* denoised and residual: the block is expanded on the device by _expand.Expander, as in export_movie (``pmd_gemm`` of
+  R s with the Vt block, ``pmd_group_expand``), and the same kernel takes the expanded buffer as a batch of P D pixels.
 * the host finishes in float64 (finish_moments, finish_pnr) and rounds every image once.
 
 Blocks start on multiples of 1024 whatever the batch size, so every output bit is the same for every batching and
@@ -20,9 +19,10 @@ source.  The movie is read once through the scaffold of _stream; device memory d
 """
 import numpy as np
 
-from ._stream import (BLOCK, VtBlocks, batch_buffer_bytes, block_plan, check_fit, device_context, mean_std, name_tuple,
+from ._expand import Expander, expander_bytes, interleave, panel_code, split_panels
+from ._stream import (batch_buffer_bytes, block_plan, block_walk, check_fit, device_context, name_tuple,
                       read_batches, source_info, upload_f32)
-from .maps import _PANEL_CODE, GAMMA, KINDS, _Expander, centring_vector
+from .maps import GAMMA, KINDS, centring_vector
 
 STATS = ("mean", "std", "min", "max", "argmin", "argmax", "skewness", "kurtosis", "pnr")
 _EXT_STATS = ("min", "max", "argmin", "argmax", "pnr")             # what needs the running extrema,
@@ -88,12 +88,8 @@ def summary_device_bytes(*, D, nb, esize, n_raw, n_expand, need_ext, need_arg, n
     if needs_movie:
         need += batch_buffer_bytes(nb, D, esize, host_source, n_batches)
     if n_expand:
-        need += 8 * (n_patches + 1) + n_entries * (8 * 4 + 4 * 64) + 4 * n_a + 2 * 4 * D
-        need += 4 * n_expand * BLOCK * D + 4 * n_cols * BLOCK
-        if rank > 0 and n_cols > 0:
-            need += 4 * rank * BLOCK
-            if not factors_on_device:
-                need += 4 * n_cols * rank
+        need += expander_bytes(D=D, n_cols=n_cols, rank=rank, n_entries=n_entries, n_a=n_a, n_patches=n_patches,
+                               factors_on_device=factors_on_device, block_panels=n_expand)
     return need + (1 << 20)     # the allocator's rounding of the small arrays
 
 
@@ -203,49 +199,31 @@ class _State:
 
 def _summary(ctx, pmd, dv, tabs, xt, movie, plan, stats, do_raw, panels, need, temporal_bin, frame_batch_size,
              num_workers):
-    import ctypes as C
-
-    import torch
     from ._lib import ptr
 
     T, d1, d2 = (int(x) for x in pmd.shape)
     D = d1 * d2
-    dev = ctx.device
     P = len(panels)
     mean32 = np.asarray(pmd.mean_img, dtype=np.float32).reshape(-1)
     centre32 = centring_vector(pmd)
     raw = _State(ctx, D, need, centre32) if do_raw else None
     if P:
-        mean, std = mean_std(ctx, pmd)
-        ex = _Expander(ctx, pmd, dv, tabs, xt)
-        vt = VtBlocks(ctx, pmd, dv) if ex.product else None
-        code = 0
-        for j, k in enumerate(panels):
-            code |= _PANEL_CODE[k] << (2 * j)
-        # the expanded block: frame f holds its panels side by side, pixel (i, j) of panel p at i P d2 + p d2 + j; the
-        # kernel takes it as a batch of P D "pixels" whose centring vector is the mean image under the denoised panel
-        # and 0 under the residual panel
-        block = torch.empty((BLOCK, P * D), dtype=torch.float32, device=dev)
-        shift = np.zeros((d1, P, d2), dtype=np.float32)
-        if "denoised" in panels:
-            shift[:, panels.index("denoised"), :] = mean32.reshape(d1, d2)
-        expanded = _State(ctx, P * D, need, shift.reshape(-1))
-        ct = torch.zeros((ex.n_cols, BLOCK), dtype=torch.float32, device=dev) if ex.active else None
-    blocks_of = {b0: blocks for b0, _, blocks in plan}
+        ex = Expander(ctx, pmd, dv, tabs, xt, block_panels=P)
+        code = panel_code(panels)
+        # the kernel takes the expanded block as a batch of P D "pixels" whose centring vector is the mean image under
+        # the denoised panel and 0 under the residual panel
+        centres = {"denoised": mean32, "residual": np.zeros(D, np.float32)}
+        expanded = _State(ctx, P * D, need, interleave([centres[k] for k in panels], d1, d2))
+    walk = block_walk(plan, D)
 
     def consume(batch, elem, b0, n):
-        for c0, c1 in blocks_of[b0]:
-            m = c1 - c0
-            yp = C.c_void_p(batch.data_ptr() + (c0 - b0) * D * batch.element_size()) if batch is not None else None
+        for c0, m, yp in walk(batch, b0):
             if do_raw:
                 raw.accumulate(ctx, yp, elem, m, c0, temporal_bin)
             if P:
-                if ex.product:
-                    vt.load(c0, m)
-                    ctx.call("pmd_gemm", 0, 0, ex.n_cols, m, ex.rank, 1.0, ptr(ex.rs), ex.rank, ptr(vt.buf), BLOCK, 0.0,
-                             ptr(ct), BLOCK)
-                ex.expand(ct, BLOCK, m, mean, std, yp, elem, P, code, block)
-                expanded.accumulate(ctx, ptr(block), 0, m, c0, temporal_bin)
+                ex.coefficients(c0, m)
+                ex.expand(m, P, code, yp, elem)
+                expanded.accumulate(ctx, ptr(ex.block), 0, m, c0, temporal_bin)
 
     read_batches(ctx, movie, [(b0, b1) for b0, b1, _ in plan], frame_batch_size, num_workers, consume)
     ctx.sync()
@@ -255,11 +233,10 @@ def _summary(ctx, pmd, dv, tabs, xt, movie, plan, stats, do_raw, panels, need, t
     if do_raw:
         out["raw"] = _finish(stats, raw.host(), T, centre32, noise, (d1, d2))
     if P:
-        ext, arg, mom = (None if a is None else a.reshape(a.shape[0], d1, P, d2) for a in expanded.host())
+        state = [None if a is None else split_panels(a, d1, P, d2) for a in expanded.host()]
         for j, k in enumerate(panels):
-            one = tuple(None if a is None else np.ascontiguousarray(a[:, :, j, :]).reshape(a.shape[0], D)
-                        for a in (ext, arg, mom))
-            out[k] = _finish(stats, one, T, mean32 if k == "denoised" else np.zeros(D, np.float32), noise, (d1, d2))
+            one = tuple(None if a is None else a[j] for a in state)
+            out[k] = _finish(stats, one, T, centres[k], noise, (d1, d2))
     return out
 
 

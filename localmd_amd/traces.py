@@ -20,8 +20,8 @@ device tensors sliced in place); the traces leave the device batch by batch thro
 import numpy as np
 import scipy.sparse
 
-from ._stream import (BLOCK, ToHost, VtBlocks, batch_buffer_bytes, block_plan, check_fit, device_context, name_tuple,
-                      read_batches, scaled_r, source_info, upload_f32)
+from ._stream import (BLOCK, ToHost, VtBlocks, batch_buffer_bytes, block_plan, block_walk, check_fit, device_context,
+                      factor_bytes, name_tuple, read_batches, scaled_r, source_info, upload_f32)
 
 KINDS = ("denoised", "raw", "residual")
 REDUCE = ("mean", "sum")
@@ -235,10 +235,7 @@ def traces_device_bytes(D, nb, esize, K, n_out, n_scratch, nnz_w, n_segs, n_spli
         need += 8 * nnz_w + 8 * (SEG_FIELDS * n_segs + SPLIT_FIELDS * n_split) + 4 * n_partial_rows * nb
     need += 4 * K * nb * (2 * n_out + n_scratch)
     need += 4 * (K * BLOCK + K * rank + K) + 12 * nnz_b + 8 * (K + 1)
-    if rank > 0 and n_cols > 0:
-        need += 4 * rank * BLOCK
-        if not factors_on_device:
-            need += 4 * n_cols * rank
+    need += factor_bytes(n_cols, rank, factors_on_device)
     return need + (1 << 20)     # the allocator's rounding of the small arrays
 
 
@@ -356,7 +353,7 @@ def _extract(ctx, pmd, dv, tabs, B, offset, movie, plan, kinds, frame_batch_size
     scratch = (torch.empty(K * nb, dtype=torch.float32, device=dev)
                if "residual" in kinds and "raw" not in kinds else None)
     F = 4   # bytes per output value
-    blocks_of = {b0: blocks for b0, _, blocks in plan}
+    walk = block_walk(plan, tabs["D"])
 
     def consume(batch, elem, b0, n):
         buf, ld = sink.dst(b0, n)
@@ -366,8 +363,8 @@ def _extract(ctx, pmd, dv, tabs, B, offset, movie, plan, kinds, frame_batch_size
             rt.gather(batch, elem, n, _Ptr(raw_p), ld, ws)
         if needs_den:
             den_p, res_p = row.get("denoised"), row.get("residual")
-            for c0, c1 in blocks_of[b0]:
-                m, o = c1 - c0, F * (c0 - b0)
+            for c0, m, _ in walk(None, b0):      # the traces are addressed in the output buffer, not in the batch
+                o = F * (c0 - b0)
                 if product:
                     vt.load(c0, m)
                     ctx.call("pmd_gemm", 0, 0, K, m, rank, 1.0, ptr(wk), rank, ptr(vt.buf), BL, 0.0, ptr(ct), BL)

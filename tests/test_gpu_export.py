@@ -18,6 +18,7 @@ from localmd_amd.dataset import TiffArray, lazy_data_loader
 from localmd_amd.pmdarray import PMDArray, load_npz, save_npz
 from localmd_amd.synthetic import make_movie
 from tests.test_export_host import _random_tiled_u
+from tests.util import degenerate_pmds
 
 pytestmark = pytest.mark.gpu
 Dm.QUIET = True
@@ -92,6 +93,22 @@ class _Kernel:
     def host(self, out, out_dtype, panels, n):
         self.ctx.sync()
         return out.cpu().numpy().view(np.dtype(out_dtype)).reshape(n, self.d1, len(panels) * self.d2)
+
+
+@pytest.mark.parametrize("which", ["no_columns", "rank_zero"])
+def test_decomposition_without_columns_or_rank_exports_the_mean_image(gpu_ctx, case, which):
+    """Nothing to expand (no entries) and nothing to multiply (rank 0, C stays zero): x = mean, r = y - mean."""
+    mov, pmds = case
+    pmd = degenerate_pmds(pmds["C"])[which]
+    mean = np.asarray(pmd.mean_img, np.float32)
+    want = np.concatenate([mov, np.broadcast_to(mean, mov.shape), mov - mean[None]], axis=2)
+    for src in (mov, mov.astype(np.uint16)):
+        got = np.empty_like(want)
+        localmd_amd.export_movie(pmd, got, src, panels=TRIPTYCH, frame_batch_size=1024, ctx=gpu_ctx)
+        assert got.tobytes() == want.tobytes()
+    den = np.empty((T, D1, D2), np.uint16)
+    localmd_amd.export_movie(pmd, den, panels="denoised", dtype="uint16", ctx=gpu_ctx)
+    assert np.array_equal(den, np.broadcast_to(E.quantize(mean, np.uint16), den.shape))
 
 
 def _tables_case(kind, gpu_ctx, case):

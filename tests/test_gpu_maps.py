@@ -17,6 +17,7 @@ from localmd_amd.dataset import TiffArray, lazy_data_loader
 from localmd_amd.pmdarray import PMDArray, load_npz, save_npz
 from localmd_amd.synthetic import make_movie
 from tests.test_export_host import _random_tiled_u
+from tests.util import degenerate_pmds
 
 pytestmark = pytest.mark.gpu
 Dm.QUIET = True
@@ -380,6 +381,28 @@ def test_correlation_against_fp64_pearson(gpu_ctx, case, order):
     keep = np.ones((D1, D2), bool)
     keep[7, 9] = False
     assert np.array_equal(mc.raw[:2][:, keep], m.raw[:2][:, keep])
+
+
+@pytest.mark.parametrize("which", ["no_columns", "rank_zero"])
+def test_decomposition_without_columns_or_rank(gpu_ctx, case, which):
+    """The denoised movie is the mean image: its sums are mean sum x, it correlates with nothing, and the residual is
+    the movie minus the mean image."""
+    mov, pmds = case
+    pmd = degenerate_pmds(pmds["C"])[which]
+    X64den, absX = _den64(pmd)
+    mean32 = np.asarray(pmd.mean_img, np.float32).reshape(-1)
+    assert np.array_equal(X64den, np.repeat(mean32.astype(np.float64)[:, None], T, axis=1))
+    X64 = _regressors(3, seed=5)
+    m = localmd_amd.regressor_maps(pmd, X64, mov, kinds=ALL, stat="sum", frame_batch_size=1024, ctx=gpu_ctx)
+    _check_sums(m, X64, mov.reshape(T, D).astype(np.float64), X64den, absX, mean32.astype(np.float64), "sum")
+    m = localmd_amd.regressor_maps(pmd, X64, mov, kinds=ALL, stat="correlation", frame_batch_size=1024, ctx=gpu_ctx)
+    assert np.array_equal(m.denoised, np.zeros((3, D1, D2), np.float32))
+    Z = (mov.reshape(T, D) - mean32[None, :]).astype(np.float64)        # the fp32 residual frames
+    xhat = MP.normalized_regressors(X64).astype(np.float32).astype(np.float64)
+    r64, kappa = _pearson64(xhat, Z)
+    var = np.isfinite(kappa)                                     # pixels whose fp32 values vary at all
+    assert var.sum() > 0.9 * D and np.all(m.residual.reshape(3, D)[:, ~var] == 0)
+    assert np.all(np.abs(m.residual.reshape(3, D)[:, var] - r64[:, var]) <= _corr_bound(kappa[var])[None, :])
 
 
 # ---- invariance ----------------------------------------------------------------------------------------------------

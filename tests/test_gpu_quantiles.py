@@ -17,6 +17,7 @@ from localmd_amd._lib import PMDLibraryError, ptr
 from localmd_amd._minitiff import write_tiff
 from localmd_amd.dataset import TiffArray, lazy_data_loader
 from tests.test_gpu_maps import _CountingU16, _decompose, _int_movie, _long_pmd
+from tests.util import degenerate_pmds
 
 pytestmark = pytest.mark.gpu
 Dm.QUIET = True
@@ -336,6 +337,23 @@ def test_mad_against_np_sort(gpu_ctx, case, sorted_panels):
 
 
 # ---- invariance ----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("which", ["no_columns", "rank_zero"])
+def test_decomposition_without_columns_or_rank(gpu_ctx, case, which):
+    """The denoised movie is the mean image in every frame; quantiles and MAD against np.sort of the exported panels."""
+    mov, pmds = case
+    pmd = degenerate_pmds(pmds["F"])[which]
+    panels = _exported(gpu_ctx, pmd, mov)
+    mean32 = np.asarray(pmd.mean_img, np.float32).reshape(-1)
+    assert np.array_equal(panels["denoised"], np.broadcast_to(mean32, (T, D)))
+    assert np.array_equal(panels["residual"], mov.reshape(T, D) - mean32[None, :])
+    r = localmd_amd.quantile_images(pmd, mov, kinds=ALL, q=(0.08, 0.5), mad=True, frame_batch_size=1024, ctx=gpu_ctx)
+    for kind in ALL:
+        S = np.sort(panels[kind], axis=0)
+        assert getattr(r, kind).tobytes() == _reference(S, (0.08, 0.5), "linear").tobytes(), kind
+        assert r.mad[kind].tobytes() == _mad_reference(panels[kind], S).reshape(D1, D2).tobytes(), kind
+    assert not r.mad["denoised"].any()
+
+
 def _bytes(r, kinds=ALL):
     return b"".join(getattr(r, k).tobytes() + r.mad[k].tobytes() for k in kinds)
 

@@ -18,6 +18,7 @@ from localmd_amd.dataset import TiffArray, lazy_data_loader
 from localmd_amd.pmdarray import load_npz, save_npz
 from tests.test_gpu_maps import _CountingU16, _decompose, _den64, _int_movie, _long_pmd
 from tests.test_summary_host import emulate_bins
+from tests.util import degenerate_pmds
 
 pytestmark = pytest.mark.gpu
 Dm.QUIET = True
@@ -343,6 +344,20 @@ def test_background_rank_zero(gpu_ctx, case):
     _check_extrema_against_export(gpu_ctx, pmd, mov)
     s = localmd_amd.summary_images(pmd, mov, kinds=ALL, stats=_MOMENTS, ctx=gpu_ctx)
     _check_moments(s, pmd, mov)
+
+
+@pytest.mark.parametrize("which", ["no_columns", "rank_zero"])
+def test_decomposition_without_columns_or_rank(gpu_ctx, case, which):
+    """The denoised movie is the mean image: extrema against the export as for any decomposition, and a constant pixel's
+    moments."""
+    mov, pmds = case
+    pmd = degenerate_pmds(pmds["C"])[which]
+    mean32 = np.asarray(pmd.mean_img, np.float32)
+    s = _check_extrema_against_export(gpu_ctx, pmd, mov)
+    assert np.array_equal(s.denoised["min"], mean32) and np.array_equal(s.denoised["max"], mean32)
+    assert not s.denoised["argmin"].any() and not s.denoised["argmax"].any()
+    m = localmd_amd.summary_images(pmd, mov, kinds="denoised", stats=("mean", "std"), ctx=gpu_ctx).denoised
+    assert np.array_equal(m["mean"], mean32) and not m["std"].any()
 
 
 def _moment_bounds(Z):

@@ -90,3 +90,19 @@ def sign_align(a, b, axis=0):
 def rel_err(a, b):
     return float(np.linalg.norm(np.asarray(a, dtype=np.float64) - np.asarray(b, dtype=np.float64)) /
                  max(np.linalg.norm(np.asarray(b, dtype=np.float64)), 1e-300))
+
+
+def degenerate_pmds(pmd):
+    """{"no_columns", "rank_zero"}: PMDArrays with the shape, order and statistics of ``pmd`` whose denoised movie is the
+    mean image in every frame: a U without columns, and the U of ``pmd`` with factors of rank 0."""
+    import scipy.sparse
+    from localmd_amd.pmdarray import PMDArray
+
+    T, d1, d2 = pmd.shape
+    n_cols, f32 = pmd.u.shape[1], np.float32
+
+    def make(u, k):
+        return PMDArray(u, np.zeros((k, 0), f32), np.zeros(0, f32), np.zeros((0, T), f32), (T, d1, d2), pmd.order,
+                        pmd.mean_img, pmd.var_img)
+
+    return {"no_columns": make(scipy.sparse.csr_matrix((d1 * d2, 0), dtype=f32), 0), "rank_zero": make(pmd.u, n_cols)}
