@@ -65,7 +65,9 @@ long pmd_time_ld(long t);       /* leading dimension of a time-contiguous row of
 int pmd_rng_normal(pmd_ctx* ctx, uint64_t seed, uint32_t stream, uint32_t index0, uint32_t index_step, int batch,
                    long rows, int cols, int transpose, float* out, long ld, long batch_stride);
 
-/* A1: per-pixel mean and Welch noise sigma (pmd_loader.py:203-291; preprocessing_utils.py:10-40). */
+/* A1: per-pixel mean and Welch noise sigma (pmd_loader.py:203-291; preprocessing_utils.py:10-40).  frame_const: frames per
+ * Welch chunk (the reference's 1024), any value >= 1; a chunk of fewer than 256 frames enters the mean only.  T, D or
+ * frame_const below 1: PMD_ERR_ARG, and a workspace size of 0. */
 size_t pmd_stats_workspace_bytes(int T, long D, int frame_const);
 int pmd_stats(pmd_ctx* ctx, const float* movie, int T, long D, int frame_const, int compute_normalizer,
               float* mean_out, float* std_out, void* ws, size_t ws_bytes);

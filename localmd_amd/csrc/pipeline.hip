@@ -570,8 +570,9 @@ extern "C" size_t pmd_background_rsvd_workspace_bytes(long D, int n, int K) {
   return ar.used + 4096;
 }
 
-// xs: standardised sample, pixel-major [c][f], leading dimension ld >= pmd_time_ld(n), with
-// round_up(D, 256) rows allocated (rows >= D zero).  basis_out: [c][k], K columns.
+// xs: standardised sample, pixel-major [c][f], leading dimension ld >= pmd_time_ld(n), with the rows of the header's
+// contract: round_up(D, 1024) allocated, rows >= D zero (the blocks walked here are BG_BLK = 256 rows, which that covers).
+// basis_out: [c][k], K columns.
 extern "C" int pmd_background_rsvd(pmd_ctx* ctx, const float* xs, long D, int n, long ld, int K, uint64_t seed,
                                    float* basis_out, void* ws, size_t ws_bytes) {
   CTX_CHECK(ctx);

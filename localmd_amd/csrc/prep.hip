@@ -189,6 +189,7 @@ static int stats_finalize(pmd_ctx* ctx, const double* csum, const float* cnoise,
 }
 
 extern "C" size_t pmd_stats_workspace_bytes(int T, long D, int frame_const) {
+  if (T < 1 || D < 1 || frame_const < 1) return 0;   // (pmd_stats refuses these)
   const int nchunks = (T + frame_const - 1) / frame_const;
   return (size_t)nchunks * D * (sizeof(double) + sizeof(float)) + 1024;
 }
@@ -197,6 +198,8 @@ extern "C" int pmd_stats(pmd_ctx* ctx, const float* movie, int T, long D, int fr
                          float* mean_out, float* std_out, void* ws, size_t ws_bytes) {
   CTX_CHECK(ctx);
   pmd_prof_scope prof__(ctx, "stats_welch");
+  // any chunk length >= 1 is honoured (chunks shorter than a 256-frame window only enter the mean)
+  if (T < 1 || D < 1 || frame_const < 1) return pmd_fail(ctx, PMD_ERR_ARG, "pmd_stats", "empty movie or chunk length below 1");
   const int nchunks = (T + frame_const - 1) / frame_const;
   pmd_arena ar(ws, ws_bytes);
   double* csum = ar.take_n<double>((size_t)nchunks * D);
