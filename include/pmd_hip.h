@@ -206,6 +206,49 @@ int pmd_pixel_hist_accumulate(pmd_ctx* ctx, const void* Y, int elem, long ldy, l
                               int pass, const uint32_t* prefix, uint32_t* hist);
 int pmd_pixel_hist_select(pmd_ctx* ctx, long D, uint32_t* hist, int* rank, uint32_t* prefix);
 
+/* Rolling baseline and dF/F along time (localmd_amd/baseline.py, csrc/baseline.hip): the series of a pixel is reduced to
+ * knots (bin means), the knots are filtered by a sliding minimum and / or maximum, and the baseline of a frame is
+ * interpolated between the knots.  All matrices are frames-first with a leading dimension in elements; every fp32
+ * operation below is rounded on its own (no contraction).  The bits written for pixel c depend on column c of the inputs
+ * and the scalar arguments only: not on N, the leading dimensions, alignment, the element type holding the same values
+ * or the pixel's position.  None of the three synchronises or allocates; an argument error returns PMD_ERR_ARG with
+ * nothing launched.
+ *
+ * pmd_bin_means: Y holds the n frames f0 .. f0 + n of a series (1 <= n <= PMD_STATS_BLOCK, element type elem, ldy >= N);
+ *   bin is a power of two in 1 .. PMD_BASELINE_MAX_BIN, f0 >= 0 a multiple of it, f0 + n < 2^31.  Bins start at
+ *   multiples of bin; the bins [b, min(n, b + bin)) of the call are written to the rows f0 / bin + b / bin of K (fp32,
+ *   ldk >= N): the fp32 chain over the bin's frames in ascending order starting from the first frame's value, divided
+ *   (IEEE) by the frame count (the call's last bin may be short); bin == 1: (float) Y[f][c], no arithmetic.  The
+ *   definition of pmd_pixel_stats_accumulate for bin <= 256.
+ *   Errors: n or bin out of range, f0 negative or not a multiple of bin, N < 1, ldy < N, ldk < N, unknown elem, NULL Y / K.
+ *
+ * pmd_sliding_extremum: out[j][c] = fminf (is_max = 0) or fmaxf (is_max = 1) over X[max(0, j - half) .. min(n - 1,
+ *   j + half)][c], for the n >= 1 rows of X (n x N fp32, ldx >= N) into out (n x N, ldo >= N, no overlap with X); half >= 0
+ *   may exceed n.  A NaN is dropped unless every frame of the window is NaN; -0 and +0 compare equal and either may come
+ *   out.  The work per output does not depend on half (segment prefix / suffix extrema).  work: at least
+ *   pmd_sliding_extremum_work_floats(n, N) = n * round_up(N, 4) floats of device memory that overlap neither matrix; a
+ *   caller bounds it by calling once per range of Nc columns (X + c0, out + c0, N = Nc, the same leading dimensions).
+ *   Errors: n < 1, N < 1, N > 65535 * 256, ldx < N, ldo < N, half < 0, is_max not 0 / 1, a NULL pointer, work_floats too
+ *   small, X and out overlapping.
+ *
+ * pmd_baseline_apply: frames f0 .. f0 + n (1 <= n <= PMD_STATS_BLOCK, f0 >= 0, f0 + n <= T) of a series of T frames,
+ *   1 <= T < PMD_BASELINE_MAX_FRAMES, whose ceil(T / bin) knots are the rows of K (ldk >= N).  Bin j has n_j = min(bin,
+ *   T - j bin) frames and the centre c_j = j bin + (n_j - 1) / 2 (exact in fp32).  The baseline F0 of frame t: K_0 for
+ *   t <= c_0, K_last for t >= c_last; else with j the last bin with c_j <= t: K_j when t == c_j (no arithmetic), otherwise
+ *   w = (t - c_j) / (c_{j+1} - c_j) (one fp32 division of exact operands), F0 = K_j + w (K_{j+1} - K_j).  With
+ *   x = (float) X[t - f0][c]: out (fp32, ldo >= N) gets F0 (mode 0; X may be NULL and is not read), x - F0 (mode 1), or
+ *   (x - F0) / F0 where F0 > min_baseline and 0 elsewhere, a NaN F0 included (mode 2).
+ *   Errors: n, bin, T or mode out of range, frames outside 0 .. T, N < 1, a leading dimension below N, unknown elem, NULL
+ *   K / out, NULL X with mode 1 or 2. */
+#define PMD_BASELINE_MAX_BIN 256
+#define PMD_BASELINE_MAX_FRAMES (1L << 23)
+int pmd_bin_means(pmd_ctx* ctx, const void* Y, int elem, long ldy, int n, long N, long f0, int bin, float* K, long ldk);
+long pmd_sliding_extremum_work_floats(long n, long Nc);
+int pmd_sliding_extremum(pmd_ctx* ctx, const float* X, long ldx, long n, long N, long half, int is_max, float* out,
+                         long ldo, float* work, long work_floats);
+int pmd_baseline_apply(pmd_ctx* ctx, const void* X, int elem, long ldx, int n, long N, long f0, long T, int bin,
+                       const float* K, long ldk, int mode, float min_baseline, float* out, long ldo);
+
 /* A2: background basis = rank-K rSVD of the standardised sample (pmd_loader.py:46-68, :300-314).
  * xs: pixel-major sample with round_up(D,1024) rows allocated (rows >= D zero). basis_out[c][k]. */
 size_t pmd_background_rsvd_workspace_bytes(long D, int n, int K);

@@ -1,6 +1,7 @@
 """
 The second half of the movie-pass scaffold: one 1024-frame block of the denoised and / or residual movie, rebuilt on the
-device.  export_movie, regressor_maps (correlation), summary_images and quantile_images all do, per block,
+device.  export_movie, regressor_maps (correlation), summary_images, quantile_images and the two passes of the rolling
+baseline (baseline.py) all do, per block,
 
     C = (R s) Vt[:, block]                       pmd_gemm, n_cols x 1024, leading dimension 1024
     frames = mean + std * (U C), y - that, y     pmd_group_expand (csrc/expand_fused.hip), panels side by side

@@ -1,6 +1,7 @@
 """
 One pass over a movie against a stored decomposition: what project_frames / project_movie, make_pmd_diagnostic_images,
-export_movie, extract_traces, regressor_maps, summary_images and quantile_images share.  The device context of a
+export_movie, extract_traces, regressor_maps, summary_images, quantile_images and the rolling baseline (baseline.py)
+share.  The device context of a
 PMDArray, how a source is read (host sources through the pinned staging ring of the streamed decomposition, device
 tensors sliced in place), the 1024-frame reconstruction blocks, the walk over the blocks of a batch and the Vt columns
 of one, the uploaded statistics and R s, the host ring that results leave the device through, and the argument and

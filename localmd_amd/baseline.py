@@ -1,0 +1,452 @@
+"""
+Rolling-baseline dF/F: a baseline F0 that follows bleaching and slow drift along time, and the movie (or a set of
+traces) detrended or normalised by it.
+
+``rolling_baseline(pmd, movie, window=...)`` returns the baseline of every pixel at knots ``temporal_bin`` frames apart;
+``dff_movie(pmd, out, movie, window=...)`` writes ``(x - F0) / F0`` (or ``x - F0``, or F0) frame by frame to the
+destinations of export_movie; ``trace_baseline(traces, window=...)`` does the same for (K, T) time courses.  A sliding
+filter is neither a running reduction nor linear in the movie, so every pixel of every frame is looked at:
+
+1. knots: the means of bins of ``temporal_bin`` frames (``pmd_bin_means``, csrc/baseline.hip), written into a resident
+   (n_bins x D) device buffer.  Denoised blocks come from _expand.Expander and read no movie; raw blocks are taken from
+   the batch in place, in their own dtype.
+2. the sliding minimum over ``2 h + 1`` knots, and for "maximin" (the morphological opening, as in Suite2p) the sliding
+   maximum of the result (``pmd_sliding_extremum``, work per knot independent of h), in ranges of pixel columns so that
+   the workspace stays within WORK_BYTES.
+3. dff_movie only: a second pass rebuilds every block and writes it through ``pmd_baseline_apply``, which interpolates
+   the baseline between the knots, into the sink.  The knots stay on the device between the passes.
+
+The bins divide the 1024-frame reconstruction block, so a bin never straddles a block and every output bit is the same
+for every frame_batch_size, source and residency.  This is the one consumer whose device memory grows with the movie's
+length T: the knots and the filter's output are ``4 D ceil(T / temporal_bin)`` bytes each.  Raise temporal_bin when they
+do not fit.
+"""
+import itertools
+
+import numpy as np
+
+from ._expand import Expander, expander_bytes, panel_code
+from ._stream import BLOCK, batch_buffer_bytes, block_plan, block_walk, device_context, read_batches, source_info
+
+KINDS = ("denoised", "raw")
+METHODS = ("maximin", "minimum")
+OUTPUTS = ("baseline", "detrended", "dff")
+MAX_BIN = 256                # PMD_BASELINE_MAX_BIN: a bin lies inside one reconstruction block
+MAX_FRAMES = 1 << 23         # PMD_BASELINE_MAX_FRAMES: frame numbers and bin centres (multiples of 1/2) are exact in fp32
+WORK_BYTES = 256 << 20       # the most workspace one pmd_sliding_extremum call gets
+
+
+# ---- host side: the knot grid, the filter plan, the interpolation (no device work) ----------------------------------
+def half_window(window, temporal_bin):
+    """The smallest h >= 0 with (2 h + 1) temporal_bin >= window."""
+    return -(-int(window) // int(temporal_bin)) // 2
+
+
+def bin_centres(T, temporal_bin):
+    """The centres c_j = j b + (n_j - 1) / 2 (float64) of the ceil(T / b) bins of T frames; the last bin may be short."""
+    T, b = int(T), int(temporal_bin)
+    j = np.arange(-(-T // b), dtype=np.int64)
+    return j * b + (np.minimum(b, T - j * b) - 1) / 2.0
+
+
+def interpolate(knots, centres, t):
+    """The baseline at the frames ``t`` (integers) from ``knots`` ((n_bins, ...) float32) at ``centres``, with the fp32
+    arithmetic of pmd_baseline_apply: K_0 up to the first centre, K_last from the last on, K_j at a centre, else
+    K_j + w (K_{j+1} - K_j) with w = (t - c_j) / (c_{j+1} - c_j), every operation rounded to float32 on its own."""
+    knots = np.asarray(knots, dtype=np.float32)
+    c = np.asarray(centres, dtype=np.float64)
+    t = np.asarray(t, dtype=np.int64).reshape(-1)
+    nb = len(c)
+    j = np.searchsorted(c, t, side="right") - 1              # the last bin whose centre is at or before t
+    ja, jb = np.clip(j, 0, nb - 1), np.clip(j + 1, 0, nb - 1)
+    inside = (j >= 0) & (j < nb - 1)
+    num = (t - c[ja]).astype(np.float32)
+    den = np.where(inside, c[jb] - c[ja], 1.0).astype(np.float32)
+    w = (num / den).astype(np.float32)
+    exact = ~inside | (t == c[ja])
+    shape = (-1,) + (1,) * (knots.ndim - 1)
+    ka, kb = knots[ja], knots[jb]
+    with np.errstate(invalid="ignore", over="ignore"):       # inf - inf and the like: NaN, as on the device
+        f = ka + w.reshape(shape) * (kb - ka)
+    return np.where(exact.reshape(shape), ka, f).astype(np.float32)
+
+
+def filter_plan(n_bins, N):
+    """([(c0, c1), ...], work_floats): the ranges of pixel columns one pmd_sliding_extremum call takes each, multiples
+    of 256 columns (of 4 when the series is very long) whose workspace of n_bins * round_up(columns, 4) floats stays
+    within WORK_BYTES, and the floats of the largest."""
+    n_bins, N = int(n_bins), int(N)
+    cols = WORK_BYTES // (4 * n_bins)
+    cols = cols // 256 * 256 if cols >= 256 else max(4, cols // 4 * 4)
+    cols = min(cols, -(-N // 4) * 4)
+    return [(c0, min(N, c0 + cols)) for c0 in range(0, N, cols)], n_bins * cols
+
+
+def knot_bytes(T, D, temporal_bin):
+    """Device bytes that grow with the movie's length: the knots, the filter's output and its workspace."""
+    n_bins = -(-int(T) // int(temporal_bin))
+    return 2 * 4 * n_bins * int(D) + 4 * filter_plan(n_bins, D)[1]
+
+
+def baseline_device_bytes(*, T, D, temporal_bin, nb, esize, kind, n_cols, rank, n_entries, n_a, n_patches, host_source,
+                          n_batches, factors_on_device, host_dest=False):
+    """Device bytes rolling_baseline (and dff_movie: ``host_dest`` adds the output ring of a host destination) holds on
+    a movie of T frames of D pixels read in batches of nb frames.  Unlike every other consumer of a decomposition this
+    one grows with the movie's length, as T / temporal_bin: the knots are 4 D ceil(T / temporal_bin) bytes, the filter's
+    output as much again, and the filter's workspace up to the same, bounded by WORK_BYTES (knot_bytes).  On top of
+    them the batch buffers of a raw pass, or for the denoised movie the expander with one expanded block."""
+    from .export import HOST_SLOTS
+
+    need = knot_bytes(T, D, temporal_bin)
+    if kind == "raw":
+        need += batch_buffer_bytes(nb, D, esize, host_source, n_batches)
+    else:
+        need += expander_bytes(D=D, n_cols=n_cols, rank=rank, n_entries=n_entries, n_a=n_a, n_patches=n_patches,
+                               factors_on_device=factors_on_device, block_panels=1)
+    if host_dest:
+        need += HOST_SLOTS * BLOCK * D * 4
+    return need + (1 << 20)     # the allocator's rounding of the small arrays
+
+
+def check_fit(what, need, free):
+    if need > free:
+        raise ValueError("{} needs about {:.2f} GB of device memory, {:.2f} GB are free; the knots grow with the "
+                         "movie's length: raise temporal_bin (or lower frame_batch_size)".format(what, need / 1e9,
+                                                                                                  free / 1e9))
+
+
+def _check_bin(temporal_bin):
+    ok = isinstance(temporal_bin, (int, np.integer)) and not isinstance(temporal_bin, (bool, np.bool_))
+    if not ok or not 1 <= int(temporal_bin) <= MAX_BIN or int(temporal_bin) & (int(temporal_bin) - 1):
+        raise ValueError("temporal_bin must be a power of two from 1 to {}, got {!r}".format(MAX_BIN, temporal_bin))
+    return int(temporal_bin)
+
+
+def _check_window(window):
+    ok = isinstance(window, (int, np.integer)) and not isinstance(window, (bool, np.bool_))
+    if not ok or int(window) < 1:
+        raise ValueError("window must be a number of frames >= 1, got {!r}".format(window))
+    return int(window)
+
+
+def _check_name(value, allowed, word):
+    if not isinstance(value, str) or value not in allowed:
+        raise ValueError("unknown {} {!r}; choose from {}".format(word, value, allowed))
+    return value
+
+
+def _check_frames(T, what):
+    if T == 0:
+        raise ValueError("{} has no frames: there is no baseline".format(what))
+    if T >= MAX_FRAMES:
+        raise ValueError("{} frames are too many: the bin centres are exact in fp32 below 2^23 frames".format(T))
+
+
+class Baseline:
+    """Result of rolling_baseline: ``knots`` ((n_bins, d1, d2) float32, the baseline at the bin centres), ``centres``
+    ((n_bins,) float64 frame positions), ``temporal_bin``, ``window_frames`` = (2 h + 1) temporal_bin, ``method``,
+    ``kind`` and ``n_frames``."""
+
+    def __init__(self, knots, temporal_bin, window_frames, method, kind, n_frames):
+        self.knots = knots
+        self.temporal_bin, self.window_frames = int(temporal_bin), int(window_frames)
+        self.method, self.kind, self.n_frames = method, kind, int(n_frames)
+        self.centres = bin_centres(self.n_frames, self.temporal_bin)
+
+    def frames(self, t0=0, t1=None):
+        """The baseline of frames t0 .. t1 ((t1 - t0, d1, d2) float32), interpolated on the host with the fp32 formula
+        of the device (interpolate): the bits of dff_movie(..., output="baseline")."""
+        t1 = self.n_frames if t1 is None else int(t1)
+        t0 = int(t0)
+        if not 0 <= t0 <= t1 <= self.n_frames:
+            raise ValueError("frames {} .. {} lie outside 0 .. {}".format(t0, t1, self.n_frames))
+        return interpolate(self.knots, self.centres, np.arange(t0, t1))
+
+    def __repr__(self):
+        return "Baseline({}; {} knots of {} frames; {} over {} frames)".format(
+            self.kind, len(self.centres), self.temporal_bin, self.method, self.window_frames)
+
+
+def _check_baseline(b, shape, kind):
+    T, d1, d2 = shape
+    if not isinstance(b, Baseline):
+        raise TypeError("baseline must be a localmd_amd.Baseline, got {}".format(type(b).__name__))
+    if b.kind != kind:
+        raise ValueError("the baseline is that of the {} movie, kind is {!r}".format(b.kind, kind))
+    _check_bin(b.temporal_bin)
+    _check_name(b.method, METHODS, "method")
+    if b.n_frames != T:
+        raise ValueError("the baseline covers {} frames, the decomposition {}".format(b.n_frames, T))
+    want = (-(-T // b.temporal_bin), d1, d2)
+    k = b.knots
+    if not isinstance(k, np.ndarray) or k.dtype != np.float32 or k.shape != want:
+        raise ValueError("the baseline's knots must be a float32 array of shape {}".format(want))
+
+
+# ---- device side ----------------------------------------------------------------------------------------------------
+def _offset(t, c0):
+    import ctypes as C
+
+    return C.c_void_p(t.data_ptr() + 4 * int(c0))
+
+
+def _filter(ctx, K, half, method):
+    """The sliding minimum (and for "maximin" then the maximum) over ``2 half + 1`` rows of the (n_bins, N) device
+    tensor K, column range by column range; returns the tensor that holds the result (K or the second buffer)."""
+    import torch
+    from ._lib import ptr
+
+    n_bins, N = (int(x) for x in K.shape)
+    ranges, work_floats = filter_plan(n_bins, N)
+    src, dst = K, torch.empty_like(K)
+    work = torch.empty(work_floats, dtype=torch.float32, device=K.device)
+    for is_max in ((0, 1) if method == "maximin" else (0,)):
+        for c0, c1 in ranges:
+            ctx.call("pmd_sliding_extremum", _offset(src, c0), N, n_bins, c1 - c0, int(half), is_max, _offset(dst, c0), N,
+                     ptr(work), work_floats)
+        src, dst = dst, src
+    return src
+
+
+class _Passes:
+    """What the two passes of one call share: the plan, the source, and for the denoised movie the expander with its
+    block."""
+
+    def __init__(self, ctx, pmd, dv, movie, kind, temporal_bin, frame_batch_size, num_workers):
+        self.ctx, self.movie, self.kind, self.bin = ctx, movie, kind, temporal_bin
+        self.fbs, self.nw = frame_batch_size, num_workers
+        self.T, d1, d2 = (int(x) for x in pmd.shape)
+        self.D = d1 * d2
+        self.plan = block_plan(self.T, frame_batch_size)
+        self.walk = block_walk(self.plan, self.D)
+        self.ex = None
+        if kind == "denoised":
+            from .export import expand_tables_for
+
+            tabs, xt = expand_tables_for(pmd)
+            self.ex = Expander(ctx, pmd, dv, tabs, xt, block_panels=1)
+            self.code = panel_code(("denoised",))
+
+    def run(self, each):
+        """each(X, elem, c0, m): the m frames from c0 on of every reconstruction block, fp32 from the expander or the
+        batch's own frames in place."""
+        from ._lib import ptr
+
+        def consume(batch, elem, b0, n):
+            for c0, m, yp in self.walk(batch, b0):
+                if self.ex is not None:
+                    self.ex.coefficients(c0, m)
+                    self.ex.expand(m, 1, self.code, None, 0)
+                    each(ptr(self.ex.block), 0, c0, m)
+                else:
+                    each(yp, elem, c0, m)
+
+        read_batches(self.ctx, self.movie if self.ex is None else None, [(b0, b1) for b0, b1, _ in self.plan], self.fbs,
+                     self.nw, consume)
+
+    def knots(self, half, method):
+        """Pass 1 and the filters: the (n_bins, D) device tensor of the filtered knots."""
+        import torch
+        from ._lib import ptr
+
+        ctx, D = self.ctx, self.D
+        K = torch.empty((-(-self.T // self.bin), D), dtype=torch.float32, device=ctx.device)
+        self.run(lambda X, elem, c0, m: ctx.call("pmd_bin_means", X, int(elem), D, int(m), D, int(c0), self.bin, ptr(K), D))
+        return _filter(ctx, K, half, method)
+
+    def apply(self, K, mode, min_baseline, sink):
+        """Pass 2: every block through pmd_baseline_apply into the sink."""
+        import ctypes as C
+        from ._lib import ptr
+
+        ctx, D, count = self.ctx, self.D, itertools.count()
+
+        def each(X, elem, c0, m):
+            k = next(count)
+            ctx.call("pmd_baseline_apply", X, int(elem), D, int(m), D, int(c0), self.T, self.bin, ptr(K), D, mode,
+                     float(min_baseline), C.c_void_p(sink.dst(k, c0)), D)
+            sink.done(k, c0, m)
+
+        self.run(each)
+
+
+def _check_common(pmd, movie, kind, temporal_bin, method):
+    from .pmdarray import PMDArray
+
+    if not isinstance(pmd, PMDArray):
+        raise TypeError("pmd must be a localmd_amd.PMDArray, got {}".format(type(pmd).__name__))
+    if kind == "residual":
+        raise ValueError("the residual's baseline is about 0 and dF/F of it means nothing; choose from {}".format(KINDS))
+    _check_name(kind, KINDS, "kind")
+    _check_name(method, METHODS, "method")
+    b = _check_bin(temporal_bin)
+    if kind == "raw" and movie is None:
+        raise ValueError("kind 'raw' needs the movie: pass movie=")
+    on_device, esize = source_info(movie, pmd.shape) if kind == "raw" else (False, 4)
+    _check_frames(int(pmd.shape[0]), "the decomposition")
+    return b, on_device, esize
+
+
+def _fit(what, pmd, kind, b, esize, on_device, frame_batch_size, dv_active, host_dest, free):
+    """check_fit before anything is allocated on the device."""
+    T, d1, d2 = (int(x) for x in pmd.shape)
+    n_cols, rank = (int(x) for x in pmd.r.shape)
+    plan = block_plan(T, frame_batch_size)
+    n_ent = n_a = n_patches = 0
+    if kind == "denoised":
+        from .export import expand_tables_for
+
+        tabs, xt = expand_tables_for(pmd)
+        n_ent, n_a, n_patches = len(xt["entries"]), int(tabs["a"].size), int(xt["n_patches"])
+    need = baseline_device_bytes(T=T, D=d1 * d2, temporal_bin=b, nb=plan[0][1] - plan[0][0], esize=esize, kind=kind,
+                                 n_cols=n_cols, rank=rank, n_entries=n_ent, n_a=n_a, n_patches=n_patches,
+                                 host_source=not on_device, n_batches=len(plan), factors_on_device=dv_active,
+                                 host_dest=host_dest)
+    check_fit(what, need, free)
+
+
+# ---- public entry points -------------------------------------------------------------------------------------------
+def rolling_baseline(pmd, movie=None, *, kind="denoised", window, temporal_bin=16, method="maximin",
+                     frame_batch_size=10000, num_workers=0, device=None, ctx=None):
+    """The rolling baseline of every pixel of the ``kind`` movie ("denoised": ``mean_img + var_img * (U R diag(s) Vt)``,
+    which reads no movie; "raw": ``movie``, read once; the residual has no baseline to speak of and is refused), as a
+    Baseline whose ``knots`` are (n_bins, d1, d2) float32 on the host.
+
+    The series of a pixel is averaged over bins of ``temporal_bin`` frames (a power of two from 1 to 256; bins start at
+    frame 0, the last may be short; each mean is an fp32 chain in frame order divided by the count).  ``method``
+    "minimum" takes the minimum of the bin means over the 2 h + 1 bins around each bin, the window cut at both ends of
+    the series; "maximin" (the default, the morphological opening) then takes the maximum of that over the same window,
+    so that a baseline under transients shorter than the window is not pulled below the signal's floor.  ``window`` is
+    in frames; h is the smallest integer with (2 h + 1) temporal_bin >= window, and the result says what was used in
+    ``window_frames``.  NaN bin means are ignored unless a whole window is NaN.
+
+    Sources, batching and residency are those of summary_images; the knots have the same bits for every
+    frame_batch_size, source and residency.  Device memory grows with the movie's length: 8 D ceil(T / temporal_bin)
+    bytes of knots and filter output plus a workspace of up to 256 MB (baseline_device_bytes); a plan that does not fit
+    raises ValueError and says to raise temporal_bin.  Argument errors are raised before any device work."""
+    from .decomposition import _device_free_bytes
+
+    window = _check_window(window)
+    b, on_device, esize = _check_common(pmd, movie, kind, temporal_bin, method)
+    half = half_window(window, b)
+    T, d1, d2 = (int(x) for x in pmd.shape)
+    with device_context(pmd, device, ctx) as (ctx, dv):
+        _fit("rolling_baseline", pmd, kind, b, esize, on_device, frame_batch_size, dv is not None, False,
+             _device_free_bytes(ctx.device))
+        ps = _Passes(ctx, pmd, dv, movie, kind, b, frame_batch_size, num_workers)
+        K = ps.knots(half, method)
+        ctx.sync()
+        knots = K.cpu().numpy().reshape(-1, d1, d2)
+    return Baseline(knots, b, (2 * half + 1) * b, method, kind, T)
+
+
+def dff_movie(pmd, out, movie=None, *, kind="denoised", output="dff", baseline=None, window=None, temporal_bin=16,
+              method="maximin", min_baseline=0.0, frame_batch_size=10000, num_workers=0, bigtiff=None, device=None,
+              ctx=None):
+    """Write the ``kind`` movie ("denoised" or "raw") relative to its rolling baseline F0 to ``out`` (the destinations of
+    export_movie: a .tif / .tiff or .npy path, a host array, a contiguous device tensor), (T, d1, d2) float32:
+    ``output`` "dff" is (x - F0) / F0, 0 where F0 > ``min_baseline`` does not hold (a NaN F0 included); "detrended" is
+    x - F0; "baseline" is F0 itself.  Returns the path or the array.
+
+    F0 at a frame is interpolated linearly (fp32, every operation rounded on its own) between the knots of
+    rolling_baseline at the bin centres, and constant before the first and after the last centre.  The knots are built
+    with ``window``, ``temporal_bin`` and ``method`` as in rolling_baseline, or taken from ``baseline``, a Baseline of
+    this decomposition and kind (then ``window`` must be None; its bin and method apply).  They stay on the device
+    while a second pass rebuilds every block and writes it out: the raw movie is read twice, the denoised movie never.
+    Every output bit is the same for every frame_batch_size, source, destination and residency.  Argument errors are
+    raised before any device work and before a file is created; a file this call created is removed when it fails
+    midway.  Device memory grows with the movie's length as in rolling_baseline."""
+    from .decomposition import _device_free_bytes
+    from .export import _destination, _DeviceSink, _HostSink
+
+    _check_name(output, OUTPUTS, "output")
+    if baseline is None:
+        if window is None:
+            raise ValueError("dff_movie needs window= (in frames) or baseline=")
+        window = _check_window(window)
+    elif window is not None:
+        raise ValueError("pass window= or baseline=, not both")
+    if bigtiff is not None and not isinstance(bigtiff, bool):
+        raise ValueError("bigtiff must be None, True or False")
+    try:
+        min_baseline = float(min_baseline)
+    except (TypeError, ValueError):
+        raise ValueError("min_baseline must be a number, got {!r}".format(min_baseline)) from None
+    if baseline is not None and not isinstance(baseline, Baseline):
+        raise TypeError("baseline must be a localmd_amd.Baseline, got {}".format(type(baseline).__name__))
+    if baseline is not None:
+        temporal_bin, method = baseline.temporal_bin, baseline.method
+    b, on_device, esize = _check_common(pmd, movie, kind, temporal_bin, method)
+    T, d1, d2 = (int(x) for x in pmd.shape)
+    if baseline is not None:
+        _check_baseline(baseline, (T, d1, d2), kind)
+    dv = getattr(pmd, "_dev", None)
+    dev_index = dv["ctx"].device_index if dv is not None else (ctx.device_index if ctx is not None else
+                                                               (0 if device is None else int(device)))
+    dest = _destination(out, (T, d1, d2), np.dtype(np.float32), bigtiff, dev_index)
+    mode = OUTPUTS.index(output)
+
+    with device_context(pmd, dev_index, ctx) as (ctx, dv):
+        _fit("dff_movie", pmd, kind, b, esize, on_device, frame_batch_size, dv is not None, dest.kind != "device",
+             _device_free_bytes(ctx.device))
+        dest.open()
+        try:
+            ps = _Passes(ctx, pmd, dv, movie, kind, b, frame_batch_size, num_workers)
+            if baseline is None:
+                K = ps.knots(half_window(window, b), method)
+            else:
+                import torch
+
+                K = torch.from_numpy(np.ascontiguousarray(baseline.knots).reshape(-1, d1 * d2)).to(ctx.device)
+            if dest.kind == "device":
+                sink = _DeviceSink(dest.target, 4 * d1 * d2)
+            else:
+                sink = _HostSink(ctx, dest, 4 * d1 * d2, (d1, d2), np.dtype(np.float32), min(T, BLOCK))
+            try:
+                ps.apply(K, mode, min_baseline, sink)
+                sink.finish()
+                ctx.sync()
+            except BaseException:
+                sink.abort()
+                raise
+        except BaseException:
+            dest.abort()
+            raise
+        finally:
+            dest.shutdown()
+        return dest.close()
+
+
+def trace_baseline(traces, *, window, temporal_bin=16, method="maximin", output="dff", min_baseline=0.0, device=None,
+                   ctx=None):
+    """The rows of ``traces`` ((K, T), for instance those of extract_traces) relative to their rolling baseline:
+    (K, T) float32, ``output`` "dff", "detrended" or "baseline" as in dff_movie, the baseline built with ``window``,
+    ``temporal_bin`` and ``method`` as in rolling_baseline.  The three kernels of dff_movie run on the transposed
+    (T, K) matrix in 1024-frame blocks, so a trace gets the bits the same series gets as a pixel of a movie."""
+    import torch
+    from ._lib import ptr
+
+    window = _check_window(window)
+    b = _check_bin(temporal_bin)
+    _check_name(method, METHODS, "method")
+    mode = OUTPUTS.index(_check_name(output, OUTPUTS, "output"))
+    min_baseline = float(min_baseline)
+    a = np.asarray(traces)
+    if a.ndim != 2 or a.dtype.kind not in "iuf" or a.shape[0] < 1:
+        raise ValueError("traces must be a (K, T) array of numbers with K >= 1")
+    Kn, T = (int(x) for x in a.shape)
+    _check_frames(T, "a trace")
+    half = half_window(window, b)
+    with device_context(None, device, ctx) as (ctx, _):
+        X = torch.from_numpy(np.ascontiguousarray(a.T, dtype=np.float32)).to(ctx.device)
+        knots = torch.empty((-(-T // b), Kn), dtype=torch.float32, device=ctx.device)
+        blocks = [(c0, min(T, c0 + BLOCK) - c0) for c0 in range(0, T, BLOCK)]
+        for c0, m in blocks:
+            ctx.call("pmd_bin_means", ptr(X[c0]), 0, Kn, m, Kn, c0, b, ptr(knots), Kn)
+        knots = _filter(ctx, knots, half, method)
+        out = torch.empty((T, Kn), dtype=torch.float32, device=ctx.device)
+        for c0, m in blocks:
+            ctx.call("pmd_baseline_apply", ptr(X[c0]), 0, Kn, m, Kn, c0, T, b, ptr(knots), Kn, mode, min_baseline,
+                     ptr(out[c0]), Kn)
+        ctx.sync()
+        return np.ascontiguousarray(out.cpu().numpy().T)
