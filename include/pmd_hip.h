@@ -249,6 +249,32 @@ int pmd_sliding_extremum(pmd_ctx* ctx, const float* X, long ldx, long n, long N,
 int pmd_baseline_apply(pmd_ctx* ctx, const void* X, int elem, long ldx, int n, long N, long f0, long T, int bin,
                        const float* K, long ldk, int mode, float min_baseline, float* out, long ldo);
 
+/* Demixing of overlapping ROIs (localmd_amd/demix.py, csrc/hals.hip): the two non-negative Gauss-Seidel (HALS) sweeps
+ * of x ~ A c + b.  Every fp32 operation is rounded on its own (no contraction), in the order written here.  Neither
+ * synchronises or allocates; an argument error returns PMD_ERR_ARG with nothing launched.
+ *
+ * pmd_hals_sweep: over the columns t < n of C (K rows, ldc >= n; updated in place) with P (K rows, ldp >= n) and the CSR
+ *   matrix G = (indptr[K + 1], indices, data) whose rows hold their diagonal entry.  For every t, and for k = 0 .. K - 1
+ *   in order: acc = P[k][t]; for the nonzeros i of row k in stored order acc = acc - data[i] * C[indices[i]][t] (the
+ *   newest values: rows below k are those of this sweep); C[k][t] = max(lo[k], C[k][t] + acc * invd[k]), with invd[k] =
+ *   1 / G[k][k] and lo[k] = 0 or -inf.  A row with invd[k] == 0 is not touched, nor is anything beyond column n.  The
+ *   bits of column t depend on column t alone: a call may be split into column ranges.  n == 0 does nothing.
+ *   Errors: K < 1, n < 0, ldc < n, ldp < n, a NULL pointer.
+ *
+ * pmd_hals_pixels: over n_px pixels.  Pixel q is row px_row[q] of the CSR matrix U = (u_indptr, u_indices, u_data) and
+ *   is covered by the pairs j in [cov_ptr[q], cov_ptr[q + 1]), at most PMD_HALS_MAX_COVER of them, of ROI cov_k[j] and
+ *   footprint value a[j].  Sy_j = scale[q] * sum_i u_data[i] * Mt[cov_k[j]][u_indices[i]] over the nonzeros of the row
+ *   (Mt: K rows, ld ldm), then for the pairs in ascending j, each reading the newest values,
+ *   a[j] = max(0, a[j] + (Sy_j - sum_j' a[j'] H[cov_k[j']][cov_k[j]]) / H[cov_k[j]][cov_k[j]]) (H: K x K, ld ldh).  A
+ *   pair whose H[k][k] == 0 or frozen[k] != 0 is not written.  The tables are trusted (the caller validates them); a
+ *   pixel with more than PMD_HALS_MAX_COVER pairs is skipped.  Errors: n_px < 0, a NULL pointer. */
+#define PMD_HALS_MAX_COVER 64
+int pmd_hals_sweep(pmd_ctx* ctx, float* C, long ldc, const float* P, long ldp, int K, long n, const int64_t* indptr,
+                   const int* indices, const float* data, const float* invd, const float* lo);
+int pmd_hals_pixels(pmd_ctx* ctx, long n_px, const int* px_row, const int64_t* cov_ptr, const int* cov_k, float* a,
+                    const int64_t* u_indptr, const int* u_indices, const float* u_data, const float* scale,
+                    const float* Mt, long ldm, const float* H, long ldh, const int* frozen);
+
 /* A2: background basis = rank-K rSVD of the standardised sample (pmd_loader.py:46-68, :300-314).
  * xs: pixel-major sample with round_up(D,1024) rows allocated (rows >= D zero). basis_out[c][k]. */
 size_t pmd_background_rsvd_workspace_bytes(long D, int n, int K);

@@ -14,6 +14,7 @@ from .maps import regressor_maps, event_regressors
 from .summary import summary_images
 from .quantiles import quantile_images
 from .baseline import Baseline, rolling_baseline, dff_movie, trace_baseline
+from .demix import Demixed, demix
 
 PMDDataset = lazy_data_loader  # the name the reference's README uses (README.md:67)
 
@@ -22,5 +23,5 @@ __all__ = [
     "lazy_data_loader", "PMDDataset", "ArrayDataset", "save_npz", "load_npz",
     "project_movie", "make_pmd_diagnostic_images", "export_movie", "extract_traces",
     "regressor_maps", "event_regressors", "summary_images", "quantile_images",
-    "Baseline", "rolling_baseline", "dff_movie", "trace_baseline",
+    "Baseline", "rolling_baseline", "dff_movie", "trace_baseline", "Demixed", "demix",
 ]

@@ -52,6 +52,8 @@ SIGNATURES = {
     "pmd_sliding_extremum_work_floats": (c_l, [c_l, c_l]),
     "pmd_sliding_extremum": (c_i, [c_p, c_p, c_l, c_l, c_l, c_l, c_i, c_p, c_l, c_p, c_l]),
     "pmd_baseline_apply": (c_i, [c_p, c_p, c_i, c_l, c_i, c_l, c_l, c_l, c_i, c_p, c_l, c_i, c_f, c_p, c_l]),
+    "pmd_hals_sweep": (c_i, [c_p, c_p, c_l, c_p, c_l, c_i, c_l, c_p, c_p, c_p, c_p, c_p]),
+    "pmd_hals_pixels": (c_i, [c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_p, c_l, c_p]),
     "pmd_background_rsvd_workspace_bytes": (c_sz, [c_l, c_i, c_i]),
     "pmd_background_rsvd": (c_i, [c_p, c_p, c_l, c_i, c_l, c_i, c_u64, c_p, c_p, c_sz]),
     "pmd_bg_project_workspace_bytes": (c_sz, [c_l, c_i]),

@@ -186,6 +186,13 @@ class PMDArray:
 
         return dff_movie(self, out, movie, **kw)
 
+    def demix(self, rois, **kw):
+        """Non-negative footprints and demixed traces of the overlapping ROIs ``rois`` and the static background, fitted
+        to the denoised movie on the GPU without expanding it (demix.demix; same keywords)."""
+        from .demix import demix
+
+        return demix(self, rois, **kw)
+
     @property
     def _combined_temporal(self):
         """(R * s) V, built on first use and cached: __getitem__ is then one sparse-dense product
