@@ -337,7 +337,7 @@ int pmd_tiles_residual(pmd_ctx* ctx, const float* xw, long ldx, long n_rows, int
                        int* good_out, int* keep_out, void* ws, size_t ws_bytes);
 int pmd_tiles_truncate(pmd_ctx* ctx, float* U, int dpad, const int* counts, int n_tiles, int rpad);
 
-/* A13: weight and normalise tile bases: Uw = Ut * w[q] / cumw[pix]  (decomposition.py:812-853). */
+/* A13: weight and normalise tile bases: Uw = Ut * w[q] / cumw[pix]  (decomposition.py:812-853; csrc/gram.hip). */
 int pmd_weight_tiles(pmd_ctx* ctx, const float* Ut, int dpad, const int* tile_pix, int d, const float* w,
                      const float* cumw, const int* ranks, float* Uw_out, int n_tiles);
 
@@ -354,7 +354,7 @@ int pmd_tiles_project_ranked(pmd_ctx* ctx, const float* x, long ldx, int T, cons
 int pmd_compact_rows(pmd_ctx* ctx, const float* Out, long ldo, const int* col_off, const int* ranks, int T, float* Z,
                      long ldz, int n_tiles);
 
-/* A15: G = U^T U for the block-sparse U (decomposition.py:974); pairs[p] = (tile a, tile b, i0, i1,
+/* A15: G = U^T U for the block-sparse U (decomposition.py:974; csrc/gram.hip); pairs[p] = (tile a, tile b, i0, i1,
  * j0, j1) overlap rectangles, origins[tile] = (k, j).  G is (Rt+K) x (Rt+K), row-major, ldg. */
 int pmd_gram_u(pmd_ctx* ctx, const float* Uw, int dpad, int b1, int b2, const int* tile_pix, const int* pairs,
                int n_pairs, const int* origins, const int* col_off, const int* ranks, int n_tiles, int Rt,
@@ -375,7 +375,7 @@ int pmd_comm_all_gather(pmd_ctx* ctx, const void* send, void* recv, size_t bytes
  * (decomposition.py:988) keeps every direction whose eigenvalue is not exactly zero, numerically null ones included.
  * rel_cutoff >= 0: keep lambda > rel_cutoff * lambda_max only ("expose a relative cutoff option"). */
 int pmd_ctx_set_null_cutoff(pmd_ctx* ctx, float rel_cutoff);
-/* A15: P with (U P)^T (U P) = I (decomposition.py:976-999, only_left=True).  M = right matrix
+/* A15: P with (U P)^T (U P) = I (decomposition.py:976-999, only_left=True; csrc/global.hip).  M = right matrix
  * (R x m, NULL = identity, then m = R).  G is overwritten.  *rprime_host = columns kept. */
 size_t pmd_orthogonalize_workspace_bytes(int R, int m, int has_m);
 int pmd_orthogonalize(pmd_ctx* ctx, float* G, int R, const float* M, int m, long ldm, float* P_out, long ldp,
@@ -384,7 +384,8 @@ int pmd_orthogonalize(pmd_ctx* ctx, float* G, int R, const float* M, int m, long
 size_t pmd_projected_svd_workspace_bytes(int rows_p, int n1, int n2);
 int pmd_projected_svd(pmd_ctx* ctx, const float* P, int rows_p, long ldp, const float* V, int n1, int n2, long ldv,
                       float* R_out, long ldr, float* s_out, float* Vt_out, long ldvt, void* ws, size_t ws_bytes);
-/* Block-sparse form of the same Gram matrix, used when R > frames (right_mat = v, decomposition.py:976-981):
+/* Block-sparse form of the same Gram matrix, used when R > frames (right_mat = v, decomposition.py:976-981; csrc/gram.hip,
+ * the same tile-pair and tile x background sums as pmd_gram_u, stored as blocks):
  * Gblk[pair][64][64], Gbg[kb][tile][64][64] (tile x block kb of 64 background columns; ceil(K / 64) blocks), Gstrip[K][ldgs]
  * (background rows of G).
  * pmd_gram_apply: GM = G M without densifying G.  nbr_ptr[n_tiles+1], nbr[e] = (first M row of the
@@ -401,7 +402,7 @@ int pmd_gram_apply(pmd_ctx* ctx, const float* Gblk, const float* Gbg, const floa
 size_t pmd_orthogonalize_factored_workspace_bytes(int m);
 int pmd_orthogonalize_factored(pmd_ctx* ctx, const float* M, int Rc, int m, long ldm, const float* GM, long ldgm,
                                float* Et_out, long lde, int* rprime_host, void* ws, size_t ws_bytes);
-/* Cholesky variant of the same step: Et = U_c^{-T} with M^T G M = U_c^T U_c.  P = M Et^T differs from the
+/* Cholesky variant of the same step (csrc/chol.hip): Et = U_c^{-T} with M^T G M = U_c^T U_c.  P = M Et^T differs from the
  * eigenvector form by an orthogonal factor that the projected SVD absorbs, so R, s, Vt are unchanged.
  * *ok_host = 0 if the matrix is not numerically positive definite (use pmd_orthogonalize_factored then). */
 int pmd_orthogonalize_chol(pmd_ctx* ctx, const float* M, int Rc, int m, long ldm, const float* GM, long ldgm,
@@ -427,7 +428,7 @@ int pmd_projected_svd_factored(pmd_ctx* ctx, const float* M, int Rc, int m, long
  * caller, who can then form R in row blocks with pmd_gemm and overlap their download with the next block.
  * W1_in: optional m x T, ld T: M^T Z formed by the caller, e.g. the all-reduced sum of per-rank row-range partials.
  * et_lower != 0: Et is square lower triangular (pmd_orthogonalize_chol / pmd_chol_inverse), strmm replaces two GEMMs.) */
-/* The two halves of pmd_orthogonalize_chol, for callers that shard the rows of M over ranks: the partial
+/* The two halves of pmd_orthogonalize_chol (csrc/chol.hip), for callers that shard the rows of M over ranks: the partial
  * C = M[rows]^T GM[rows] (row-major lower block triangle; all-reduce it), then C -> Et in place. */
 size_t pmd_gram_mtgm_workspace_bytes(int rows, int m);
 /* leading dimension of the transposed copy M^T (m x rows) that pmd_gram_mtgm leaves at the start of its workspace (a multiple
@@ -442,7 +443,7 @@ size_t pmd_chol_inverse_workspace_bytes(int m);
 int pmd_chol_inverse(pmd_ctx* ctx, float* C, int m, long ldc, int abs_last_pivot, int* ok_host, void* ws, size_t ws_bytes);
 /* dst (cols x rows, ld_dst) = src (rows x cols, ld_src)^T, row-major */
 int pmd_transpose(pmd_ctx* ctx, const float* src, long ld_src, int rows, int cols, float* dst, long ld_dst);
-/* A13/A14: CSR arrays of the sparse spatial matrix built on the device (decomposition.py:812-853, :929-930);
+/* A13/A14: CSR arrays of the sparse spatial matrix built on the device (decomposition.py:812-853, :929-930; csrc/gram.hip);
  * cover1[d1][4] / cover2[d2][4]: indices of the tile-row / tile-column origins covering each FOV row / column. */
 int pmd_csr_count(pmd_ctx* ctx, int d1, int d2, int order_f, const int* cover1, const int* cover2, int n2,
                   const int* ranks, int K, long* row_nnz);

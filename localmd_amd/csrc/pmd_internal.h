@@ -66,9 +66,18 @@ int pmd_launch_tile_xbt_rp(pmd_ctx* ctx, const float* X, long ldx, const int* pi
                            const float* B, long b_tile_stride, long ldb, float* S, long s_tile_stride, long s_slice_stride, int s_ld,
                            int n_tiles, int T, int slices, int nrows);
 
-// global.hip
+// global.hip (also used by gram.hip and chol.hip)
+#define PMD_BLAS(ctx, call)                                                     \
+  do {                                                                          \
+    rocblas_status s__ = (call);                                                \
+    if (s__ != rocblas_status_success) return pmd_fail(ctx, PMD_ERR_BLAS, #call, rocblas_status_to_string(s__)); \
+  } while (0)
 int pmd_gemm_rm(pmd_ctx* ctx, int transA, int transB, int m, int n, int k, float alpha, const float* A, long lda,
                 const float* B, long ldb, float beta, float* C, long ldc);
+int pmd_gemm_k_chunk(const pmd_ctx* ctx, int k);   // length of one fp32 accumulation chain in a product of inner dimension k
+int launch_gather_rows(pmd_ctx* ctx, const float* src, long lds_, const int* perm, const float* scale, int nrows,
+                       int ncols, float* dst, long ldd);   // dst[c][x] = src[perm[c]][x] * scale[c]
+int launch_transpose(pmd_ctx* ctx, const float* src, long lds_, int rows, int cols, float* dst, long ldd);
 
 // gemm_f16x2.hip: fp32 products from two fp16 pieces per operand (X 2^-e = h1 + 2^-11 h2)
 bool pmd_f16x2_wanted(const pmd_ctx* ctx, int m, int n, int k);

@@ -75,7 +75,7 @@ def _block_errors(Cg, C64, m, bs):
 
 
 def _mtgm_block_size(m):
-    # pmd_gram_mtgm's row blocks at the default of five (global.hip)
+    # pmd_gram_mtgm's row blocks at the default of five (chol.hip)
     return max(256, ((m + 4) // 5 + 255) // 256 * 256)
 
 
@@ -171,7 +171,7 @@ def _within_one_ulp(got, ref, absterms):
 def test_gram_u_and_blocks_match_float64(gpu_ctx, name, K):
     """pmd_gram_u (dense G) and pmd_gram_blocks (Gblk / Gbg / Gstrip) sum in fp64 and round once: every entry within one fp32
     ulp of the float64 U^T U, tile x tile, tile x background and background x background; block entries beyond the ranks
-    exactly zero."""
+    exactly zero; and the two forms agree bit for bit wherever they hold the same entry (they share the accumulation code)."""
     torch = _t()
     ctx = gpu_ctx
     L = _layout(name, K)
@@ -210,6 +210,20 @@ def test_gram_u_and_blocks_match_float64(gpu_ctx, name, K):
         ok = _within_one_ulp(gstrip[:K, :Rc], G64[Rt:, :], Ga[Rt:, :])
         assert ok.all(), ("Gstrip", np.argwhere(~ok)[:5])
         assert np.all(gstrip[:K, Rc:] == 0)   # (the strip is cleared over its leading dimension)
+    # the dense and the block form are two stores of the same fp64 sums (same terms, same order): bit for bit
+    for p, (a, b) in enumerate(L["pairs"][:, :2]):
+        ra, rb = int(ranks[a]), int(ranks[b])
+        assert np.array_equal(Gh[off[a]:off[a] + ra, off[b]:off[b] + rb], gblk[p][:ra, :rb]), ("G vs Gblk", p, a, b)
+    for k in range(K):
+        kb, kk = divmod(k, 64)
+        for t in range(n_tiles):
+            r = int(ranks[t])
+            col = gbg[kb * n_tiles + t][:r, kk]
+            assert np.array_equal(Gh[off[t]:off[t] + r, Rt + k], col), ("G vs Gbg", k, t)
+            assert np.array_equal(gstrip[k, off[t]:off[t] + r], col), ("Gstrip vs Gbg", k, t)
+    if K > 0:
+        assert np.array_equal(Gh[Rt:, :Rc], gstrip[:K, :Rc]), "G[Rt:, :] vs Gstrip"
+        assert np.array_equal(Gh[Rt:, Rt:Rc], gstrip[:K, Rt:Rc]), "G[Rt:, Rt:] vs the strip's background block"
 
 
 def _apply(ctx, L, gb, M, ldm, ncols, GM, ldgm, a0=0):
@@ -648,6 +662,91 @@ def test_orthogonalize_factored_indefinite(gpu_ctx):
         ctx.call("pmd_ctx_set_null_cutoff", -1.0)
 
 
+def _indefinite(rng, n):
+    """Symmetric indefinite fp32 matrix with the spectrum of test_orthogonalize_factored_indefinite (3.5 decades, 30 %
+    negative, a cluster of 12 at 1e-5 of the largest) and its float64 eigenvalues."""
+    V, _ = np.linalg.qr(rng.standard_normal((n, n)))
+    mag = np.logspace(0, -3.5, n)
+    mag[-12:] = 1e-5 * (1 + 0.01 * np.arange(12))
+    sign = np.where(rng.random(n) < 0.3, -1.0, 1.0)
+    sign[0] = 1.0
+    S = (V * (mag * sign)) @ V.T
+    G32 = ((S + S.T) / 2).astype(np.float32)
+    G32 = np.ascontiguousarray(np.triu(G32) + np.triu(G32, 1).T)     # symmetric after rounding
+    return G32, np.linalg.eigvalsh(G32.astype(np.float64))
+
+
+def _orthogonalize(ctx, G, R, M, m, ldm, ldp):
+    torch = _t()
+    Pm = torch.full((R, ldp), 7.0, device=ctx.device)
+    rp = C.c_int(-1)
+    ws = ctx.workspace(ctx.lib.pmd_orthogonalize_workspace_bytes(R, m, 1 if M is not None else 0))
+    ctx.call("pmd_orthogonalize", P(G.clone()), R, P(M), m, ldm, P(Pm), ldp, C.byref(rp), P(ws), ws.numel())
+    ctx.sync()
+    return Pm, rp.value
+
+
+def test_orthogonalize_with_right_matrix_equals_factored_pair(gpu_ctx):
+    """pmd_orthogonalize with a right matrix M is pmd_gemm (G M) + pmd_orthogonalize_factored (Et) + pmd_gemm (P = M Et^T):
+    the same products through the same entry with the same leading dimensions and one shared eigen-solve epilogue, so the
+    same R' and the same P bit for bit (checked on MI355X before the epilogue was shared: bit-identical there as well)."""
+    torch = _t()
+    ctx = gpu_ctx
+    R, m = 200, 60
+    rng = np.random.default_rng(31)
+    G32, _ = _indefinite(rng, R)
+    G = torch.from_numpy(G32).to(ctx.device)
+    ldm, ldp = m + 3, m + 2
+    M = torch.from_numpy(rng.standard_normal((R, ldm)).astype(np.float32)).to(ctx.device)
+    P0, rp0 = _orthogonalize(ctx, G, R, M, m, ldm, ldp)
+    GM = torch.empty((R, m), device=ctx.device)
+    ctx.call("pmd_gemm", 0, 0, R, m, R, 1.0, P(G), R, P(M), ldm, 0.0, P(GM), m)
+    Et = torch.zeros((m, m), device=ctx.device)
+    rp = C.c_int(-1)
+    ws = ctx.workspace(ctx.lib.pmd_orthogonalize_factored_workspace_bytes(m))
+    ctx.call("pmd_orthogonalize_factored", P(M), R, m, ldm, P(GM), m, P(Et), m, C.byref(rp), P(ws), ws.numel())
+    assert rp.value == rp0 and rp0 == m, (rp.value, rp0)
+    P1 = torch.full((R, ldp), 7.0, device=ctx.device)
+    ctx.call("pmd_gemm", 0, 1, R, rp0, m, 1.0, P(M), ldm, P(Et), m, 0.0, P(P1), ldp)
+    ctx.sync()
+    print("orthogonalize vs factored pair: max |dP| =", float((P0[:, :rp0] - P1[:, :rp0]).abs().max()),
+          "max |P| =", float(P0[:, :rp0].abs().max()))
+    assert torch.all(P0[:, rp0:] == 7.0), "padding of P_out written"
+    assert torch.equal(P0, P1)
+
+
+def test_orthogonalize_identity_right_matrix(gpu_ctx):
+    """pmd_orthogonalize with M == NULL (m = R, the dense R <= frames route) on an indefinite G: columns of P in
+    |lambda|-descending order with P^T G64 P = diag(sign lambda), the scaled measure and bound of
+    test_orthogonalize_factored_indefinite; with pmd_ctx_set_null_cutoff(1e-3) exactly the directions above the cutoff."""
+    torch = _t()
+    ctx = gpu_ctx
+    R = 150
+    G32, lam64 = _indefinite(np.random.default_rng(32), R)
+    G64 = G32.astype(np.float64)
+    G = torch.from_numpy(G32).to(ctx.device)
+    order = np.argsort(-np.abs(lam64), kind="stable")
+    lmax = np.abs(lam64).max()
+    try:
+        for cutoff in (-1.0, 1e-3):
+            ctx.call("pmd_ctx_set_null_cutoff", cutoff)
+            Pm, rp = _orthogonalize(ctx, G, R, None, R, 0, R + 1)
+            above = np.nonzero(lam64 > cutoff * lmax)[0]
+            expect = R if cutoff < 0 else len(above)
+            assert rp == expect, (cutoff, rp, expect)
+            assert torch.all(Pm[:, R:] == 7.0), "padding of P_out written"
+            kept = order[:expect] if cutoff < 0 else order[np.isin(order, above)]
+            Pc = Pm.cpu().numpy()[:, :expect].astype(np.float64)
+            dev_ = np.abs(Pc.T @ G64 @ Pc - np.diag(np.sign(lam64[kept])))
+            scale = np.sqrt(np.abs(lam64[kept])[:, None] * np.abs(lam64[kept])[None, :])
+            worst = float((dev_ * scale / lmax).max())
+            print("orthogonalize, identity right matrix: cutoff", cutoff, "R'", rp, "worst", worst)
+            # measured on MI355X: 9.2e-8 and 7.3e-8 (test_orthogonalize_factored_indefinite: 1.1-1.4e-7 at order 300)
+            assert worst < 1e-6, (cutoff, worst)
+    finally:
+        ctx.call("pmd_ctx_set_null_cutoff", -1.0)
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # projected SVD
 
@@ -763,3 +862,52 @@ def test_projected_svd_whole_and_split(gpu_ctx):
     ctx.call("pmd_gemm", 0, 0, Rc, rp, m, 1.0, P(M), m, P(X1o), rp, 0.0, P(Rx), rp)
     ctx.sync()
     assert torch.equal(sx, s0) and torch.equal(Rx, R0), "R_out = NULL + X1_out + pmd_gemm differs from R_out"
+
+
+def test_projected_svd_more_rows_than_columns_with_projection(gpu_ctx):
+    """pmd_projected_svd with n1 > n2 and a projection P (rows_p x n1): eigenvectors of V^T V give Vt, left = V W / s and
+    R_out = P left.  s and the separated rows of Vt against the float64 SVD of V, R_out against P64 left64 up to the same
+    signs; V is left as it was; padding of ldr / ldvt untouched; two calls bit-identical."""
+    torch = _t()
+    ctx = gpu_ctx
+    rows_p, n1, n2 = 50, 300, 120
+    nk = n2
+    ldp, ldv, ldr, ldvt = n1 + 2, n2 + 1, nk + 5, n2 + 3
+    g = torch.Generator(device=ctx.device).manual_seed(23)
+    Pm = torch.randn((rows_p, ldp), device=ctx.device, generator=g)
+    V = torch.randn((n1, ldv), device=ctx.device, generator=g) * torch.logspace(0, -2, ldv, device=ctx.device)[None, :]
+    V0 = V.clone()
+
+    def run():
+        R = torch.full((rows_p, ldr), 7.0, device=ctx.device)
+        s = torch.empty(nk, device=ctx.device)
+        Vt = torch.full((nk, ldvt), 7.0, device=ctx.device)
+        ws = ctx.workspace(ctx.lib.pmd_projected_svd_workspace_bytes(rows_p, n1, n2))
+        ctx.call("pmd_projected_svd", P(Pm), rows_p, ldp, P(V), n1, n2, ldv, P(R), ldr, P(s), P(Vt), ldvt, P(ws), ws.numel())
+        ctx.sync()
+        return R, s, Vt
+
+    R0, s0, Vt0 = run()
+    assert torch.equal(V, V0), "V was written"
+    assert torch.all(R0[:, nk:] == 7.0) and torch.all(Vt0[:, n2:] == 7.0), "padding written"
+    R1, s1, Vt1 = run()
+    assert torch.equal(s0, s1) and torch.equal(Vt0, Vt1) and torch.equal(R0, R1), "two calls differ"
+    R0, Vt0 = R0[:, :nk].double(), Vt0[:, :n2].double()
+    left64, s64, Vt64 = torch.linalg.svd(V[:, :n2].double(), full_matrices=False)
+    Rref = Pm[:, :n1].double() @ left64
+    lam = s64 ** 2
+    gaps = (lam[:-1] - lam[1:]) / lam[0]
+    sep = torch.ones(nk, dtype=torch.bool, device=ctx.device)
+    sep[:-1] &= gaps > 1e-3
+    sep[1:] &= gaps > 1e-3
+    srel = float(((s0.double() - s64).abs() / s64[0]).max())
+    sg = torch.sign((Vt0 * Vt64).sum(1))
+    vdev = float((Vt0 * sg[:, None] - Vt64)[sep].abs().max())
+    rdev = float((R0 * sg[None, :] - Rref)[:, sep].abs().max() / Rref.abs().max())
+    print("projected_svd n1 > n2: separated", int(sep.sum()), "srel", srel, "vdev", vdev, "rdev", rdev)
+    assert int(sep.sum()) >= 10
+    # measured on MI355X: s within 8.2e-8 of s_0, the 46 separated rows of Vt within 3.6e-6, their columns of R_out within
+    # 4.3e-6 of max |R|; bounds four times that
+    assert srel < 3.5e-7, srel
+    assert vdev < 1.5e-5, vdev
+    assert rdev < 2e-5, rdev
