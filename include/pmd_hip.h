@@ -275,6 +275,37 @@ int pmd_hals_pixels(pmd_ctx* ctx, long n_px, const int* px_row, const int64_t* c
                     const int64_t* u_indptr, const int* u_indices, const float* u_data, const float* scale,
                     const float* Mt, long ldm, const float* H, long ldh, const int* frozen);
 
+/* Superpixel seeds (localmd_amd/superpixels.py, csrc/superpixel.hip): the neighbour moments of the thresholded movie and
+ * the connected components of a per-edge pixel graph.  Images are d1 x d2 in natural orientation, pixel c = i d2 + j.
+ *
+ * pmd_threshold_moments_accumulate: Y is a frames-first batch of element type elem (converted to fp32 exactly), frame f
+ *   of the call at Y + f ldy elements, ldy >= D = d1 d2; any n >= 1 (no block discipline).  With v = (float) Y[f][c]:
+ *   y = v > thr[c] ? fl32(v - thr[c]) : 0, so a NaN value or a NaN threshold gives 0.  mom is double [6][D] and is added
+ *   to: mom[0] += sum_f y, mom[1] += sum_f y^2, mom[2 .. 5] += sum_f y_p y_q for the forward neighbours q of p in the
+ *   order E (0, +1), SW (+1, -1), S (+1, 0), SE (+1, +1); a neighbour outside the image contributes 0.  Every product is
+ *   formed in fp64 from the fp32 y and is exact; every sum is one fp64 chain per pixel over the frames in ascending
+ *   order, continued from the stored value.  The bits of pixel c therefore depend on the columns of c and of its forward
+ *   neighbours, their thresholds and the previous state only: not on how the frames are split over calls, on ldy, on the
+ *   element type holding the same values, nor on the pixel's position.  One owner per pixel: no atomics, no workspace,
+ *   no synchronisation, no allocation.
+ *   Errors (PMD_ERR_ARG, nothing is launched): n < 1, d1 < 1, d2 < 1, ldy < D, unknown elem, a NULL pointer, more than
+ *   65535 * 62 columns.
+ *
+ * pmd_grid_components: edges[c] is one byte, bit 0: c is joined to its E neighbour, bit 1: SW, bit 2: S, bit 3: SE; a
+ *   bit that points outside the image and the high four bits are ignored.  label[c] (int32) becomes the smallest pixel
+ *   index of the connected component of c; an isolated pixel is its own root.  The result is fully determined by the
+ *   input.  Three launches (tiles in LDS, the tile borders on label, flattening); every cross-workgroup access to label
+ *   is a relaxed agent-scope atomic, parents are only ever lowered, and no workgroup waits for another.  ws: at least
+ *   pmd_grid_components_workspace_bytes bytes of device memory (a give-up flag, cleared by every call).  The call
+ *   synchronises the stream once, to read that flag: should a union reach its round limit (2 D + 2, which the algorithm
+ *   cannot reach) it returns PMD_ERR_UNSUPPORTED and label is not valid.  No allocation.
+ *   Errors (nothing is launched): d1 < 1, d2 < 1, d1 d2 >= 2^31, a NULL pointer (PMD_ERR_ARG); ws_bytes too small
+ *   (PMD_ERR_WORKSPACE). */
+int pmd_threshold_moments_accumulate(pmd_ctx* ctx, const void* Y, int elem, long ldy, int n, int d1, int d2,
+                                     const float* thr, double* mom);
+size_t pmd_grid_components_workspace_bytes(int d1, int d2);
+int pmd_grid_components(pmd_ctx* ctx, int d1, int d2, const uint8_t* edges, int* label, void* ws, size_t ws_bytes);
+
 /* A2: background basis = rank-K rSVD of the standardised sample (pmd_loader.py:46-68, :300-314).
  * xs: pixel-major sample with round_up(D,1024) rows allocated (rows >= D zero). basis_out[c][k]. */
 size_t pmd_background_rsvd_workspace_bytes(long D, int n, int K);

@@ -15,6 +15,7 @@ from .summary import summary_images
 from .quantiles import quantile_images
 from .baseline import Baseline, rolling_baseline, dff_movie, trace_baseline
 from .demix import Demixed, demix
+from .superpixels import Superpixels, superpixels
 
 PMDDataset = lazy_data_loader  # the name the reference's README uses (README.md:67)
 
@@ -24,4 +25,5 @@ __all__ = [
     "project_movie", "make_pmd_diagnostic_images", "export_movie", "extract_traces",
     "regressor_maps", "event_regressors", "summary_images", "quantile_images",
     "Baseline", "rolling_baseline", "dff_movie", "trace_baseline", "Demixed", "demix",
+    "Superpixels", "superpixels",
 ]

@@ -54,6 +54,9 @@ SIGNATURES = {
     "pmd_baseline_apply": (c_i, [c_p, c_p, c_i, c_l, c_i, c_l, c_l, c_l, c_i, c_p, c_l, c_i, c_f, c_p, c_l]),
     "pmd_hals_sweep": (c_i, [c_p, c_p, c_l, c_p, c_l, c_i, c_l, c_p, c_p, c_p, c_p, c_p]),
     "pmd_hals_pixels": (c_i, [c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_p, c_l, c_p]),
+    "pmd_threshold_moments_accumulate": (c_i, [c_p, c_p, c_i, c_l, c_i, c_i, c_i, c_p, c_p]),
+    "pmd_grid_components_workspace_bytes": (c_sz, [c_i, c_i]),
+    "pmd_grid_components": (c_i, [c_p, c_i, c_i, c_p, c_p, c_p, c_sz]),
     "pmd_background_rsvd_workspace_bytes": (c_sz, [c_l, c_i, c_i]),
     "pmd_background_rsvd": (c_i, [c_p, c_p, c_l, c_i, c_l, c_i, c_u64, c_p, c_p, c_sz]),
     "pmd_bg_project_workspace_bytes": (c_sz, [c_l, c_i]),

@@ -193,6 +193,13 @@ class PMDArray:
 
         return demix(self, rois, **kw)
 
+    def superpixels(self, movie=None, **kw):
+        """ROI seeds from thresholded local correlations of the denoised / raw movie: a label image that extract_traces
+        and demix accept, computed on the GPU (superpixels.superpixels; same keywords)."""
+        from .superpixels import superpixels
+
+        return superpixels(self, movie, **kw)
+
     @property
     def _combined_temporal(self):
         """(R * s) V, built on first use and cached: __getitem__ is then one sparse-dense product
