@@ -306,6 +306,32 @@ int pmd_threshold_moments_accumulate(pmd_ctx* ctx, const void* Y, int elem, long
 size_t pmd_grid_components_workspace_bytes(int d1, int d2);
 int pmd_grid_components(pmd_ctx* ctx, int d1, int d2, const uint8_t* edges, int* label, void* ws, size_t ws_bytes);
 
+/* Spike inference (localmd_amd/deconvolve.py, csrc/oasis.hip): OASIS for an AR(1) model, n_prob independent problems in
+ * one launch.  Y is frames-first (frame t at Y + t ldy elements); problem p reads column col[p] (0 <= col[p] < ldy), its
+ * parameters par[4 p .. 4 p + 3] = g, lam, s_min, b, and the table row pw + pw_row[p] ldpw, whose entry l = 0 .. T is g^l
+ * rounded to fp32 (built by the caller; the kernel never forms a power, it only indexes the row).  It minimises
+ * 1/2 |c + b - y|^2 + lam sum_t s_t over s_t = c_t - g c_{t-1} >= 0 (s_min > 0: the hard-threshold variant) by
+ * pool-adjacent-violators.  Every fp32 operation below is rounded on its own (no contraction), divisions are IEEE,
+ * denormals are kept:
+ *   forward, t = 0 .. T - 1: mu = lam * (1 - g); y' = (y[t] - b) - (t < T - 1 ? mu : lam); push the pool (v, w, t0, l) =
+ *     (y', 1, t, 1); while there are >= 2 pools and v_i < v_{i-1} * pw[l_{i-1}] + s_min, with q = pw[l_{i-1}]:
+ *     num = w_{i-1} * v_{i-1} + (q * w_i) * v_i; den = w_{i-1} + (q * q) * w_i; v_{i-1} = num / den; w_{i-1} = den;
+ *     l_{i-1} += l_i; pop.  den >= 1.  A NaN never compares true and never merges.
+ *   fill, pool k: vp = v_k > 0 ? v_k : 0; c[t0_k + j] = vp * pw[j] for j < l_k; s = 0 except at the first frame of a
+ *     pool k >= 1, where with d = c[t0_k] - g * c[t0_k - 1], s[t0_k] = d > 0 ? d : 0.
+ *   residual: d_t = y[t] - (c[t] + b); rss = sum_t (double) d_t * (double) d_t, one fp64 chain in ascending t.
+ * C and S (T rows of n_prob columns, ldc, lds >= n_prob), rss[n_prob] and n_pools[n_prob] (the number of pools at the
+ * end) may each be NULL.  The bits of a problem depend on its column, its four parameters and its table row only: not
+ * on n_prob, its position, the leading dimensions, which outputs are requested, or how problems are split over calls.
+ * col and pw_row are trusted (the caller validates them).  ws: pmd_oasis_ar1_workspace_bytes(T, n_prob) =
+ * 12 T n_prob bytes (the pool stacks).  No synchronisation, no allocation.
+ * Errors (nothing is launched): T < 1, T >= 2^31 - 1, n_prob < 1, ldy < 1, ldpw < T + 1, ldc or lds < n_prob, a NULL
+ * Y / col / par / pw_row / pw, all four outputs NULL (PMD_ERR_ARG); ws NULL or too small (PMD_ERR_WORKSPACE). */
+size_t pmd_oasis_ar1_workspace_bytes(long T, long n_prob);
+int pmd_oasis_ar1(pmd_ctx* ctx, const float* Y, long ldy, long T, long n_prob, const int* col, const float* par,
+                  const int* pw_row, const float* pw, long ldpw, float* C, long ldc, float* S, long lds, double* rss,
+                  int* n_pools, void* ws, size_t ws_bytes);
+
 /* A2: background basis = rank-K rSVD of the standardised sample (pmd_loader.py:46-68, :300-314).
  * xs: pixel-major sample with round_up(D,1024) rows allocated (rows >= D zero). basis_out[c][k]. */
 size_t pmd_background_rsvd_workspace_bytes(long D, int n, int K);

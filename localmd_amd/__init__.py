@@ -16,6 +16,7 @@ from .quantiles import quantile_images
 from .baseline import Baseline, rolling_baseline, dff_movie, trace_baseline
 from .demix import Demixed, demix
 from .superpixels import Superpixels, superpixels
+from .deconvolve import Deconvolved, deconvolve, estimate_decay
 
 PMDDataset = lazy_data_loader  # the name the reference's README uses (README.md:67)
 
@@ -25,5 +26,5 @@ __all__ = [
     "project_movie", "make_pmd_diagnostic_images", "export_movie", "extract_traces",
     "regressor_maps", "event_regressors", "summary_images", "quantile_images",
     "Baseline", "rolling_baseline", "dff_movie", "trace_baseline", "Demixed", "demix",
-    "Superpixels", "superpixels",
+    "Superpixels", "superpixels", "Deconvolved", "deconvolve", "estimate_decay",
 ]

@@ -57,6 +57,8 @@ SIGNATURES = {
     "pmd_threshold_moments_accumulate": (c_i, [c_p, c_p, c_i, c_l, c_i, c_i, c_i, c_p, c_p]),
     "pmd_grid_components_workspace_bytes": (c_sz, [c_i, c_i]),
     "pmd_grid_components": (c_i, [c_p, c_i, c_i, c_p, c_p, c_p, c_sz]),
+    "pmd_oasis_ar1_workspace_bytes": (c_sz, [c_l, c_l]),
+    "pmd_oasis_ar1": (c_i, [c_p, c_p, c_l, c_l, c_l, c_p, c_p, c_p, c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_p, c_p, c_sz]),
     "pmd_background_rsvd_workspace_bytes": (c_sz, [c_l, c_i, c_i]),
     "pmd_background_rsvd": (c_i, [c_p, c_p, c_l, c_i, c_l, c_i, c_u64, c_p, c_p, c_sz]),
     "pmd_bg_project_workspace_bytes": (c_sz, [c_l, c_i]),

@@ -1,0 +1,334 @@
+"""
+Spike inference: the activity behind each ROI trace, by OASIS for an AR(1) model (Friedrich, Zhou & Paninski 2017,
+Alg. 1).
+
+``deconvolve(traces)`` takes (K, T) time courses (those of demix, extract_traces or trace_baseline) and returns, per
+trace, the denoised calcium ``c``, the non-negative spike train ``s_t = c_t - g c_{t-1}`` and the decay ``g``, noise
+level ``sigma`` and penalty ``lam`` it used.  For one trace it minimises ``1/2 |c + b - y|^2 + lam sum_t s_t`` over
+``s >= 0`` (``s_min > 0``: the hard-threshold variant of the paper).
+
+The solve is sequential along time but independent across traces and across candidate penalties, so the device runs one
+lane per (trace, penalty) problem (``pmd_oasis_ar1``, csrc/oasis.hip; the arithmetic is stated in include/pmd_hip.h and
+restated in tests/oasis_ref.py, which reproduces it bit for bit).  Every scalar decision is float64 host code around it:
+
+* ``noise=None``: the Welch upper-half-band sigma a pixel gets (``pmd_stats`` on the (T, K) matrix, 1024-frame chunks).
+* ``g=None``: ``estimate_decay``, from the first autocovariances with the noise taken off lag 0.
+* ``lam=None``: the largest penalty whose residual stays within the noise, ``rss(lam) <= sigma^2 T``, by an m-section
+  search (``search_lambda``).  Every round is one batch of (trace, candidate) problems over all traces still searching.
+
+The powers of g come from a host table (``power_table``), one row per trace, shared by all its candidates.
+
+Device memory (``deconvolve_device_bytes``): the traces, the two outputs and the tables stay resident, ``12 K T +
+4 K (T + 1)`` bytes; the solver's pool stacks are ``12 T`` bytes per problem in flight and are capped at
+``max_workspace_bytes``: a round is split into launches that fit (``launch_plan``), and no bit depends on the split.
+
+Out of scope: AR(2), joint optimisation of g or of the baseline, and a rise time.
+"""
+import numpy as np
+
+from ._stream import device_context
+
+LAGS = 5                    # autocovariance lags estimate_decay fits
+POOL_BYTES = 12             # (v, w, t0) of one pool on a problem's stack
+MIN_NOISE_FRAMES = 256      # the Welch window: pmd_stats makes no estimate below it
+G_MAX = 0.9999              # the ceiling of an estimated decay
+FLT_MIN = float(np.finfo(np.float32).tiny)
+
+
+class Deconvolved:
+    """Result of deconvolve: ``calcium`` and ``spikes`` ((K, T) float32), and per trace ``g``, ``noise``, ``lam``,
+    ``baseline`` (float32 as the solver read them; ``noise`` float64), ``rss`` (float64, |y - c - b|^2), ``n_pools`` and
+    ``evaluations`` (the number of solves the trace took)."""
+
+    def __init__(self, calcium, spikes, g, noise, lam, baseline, rss, n_pools, evaluations):
+        self.calcium, self.spikes = calcium, spikes
+        self.g, self.noise, self.lam, self.baseline = g, noise, lam, baseline
+        self.rss, self.n_pools, self.evaluations = rss, n_pools, evaluations
+
+    def __repr__(self):
+        return "Deconvolved({} traces, {} frames)".format(*self.calcium.shape)
+
+
+# ---- host side: tables, estimates, the search, the plan (no device work) ---------------------------------------------
+def power_table(g, T):
+    """pw[l] = g^l for l = 0 .. T as the solver reads it: the float64 power of the fp32 value of g, rounded once to
+    fp32, and exactly 0 below the smallest normal fp32 number.  ``g`` a scalar ((T + 1,)) or (K,) ((K, T + 1))."""
+    g64 = np.asarray(g, dtype=np.float32).astype(np.float64)
+    p = g64[..., None] ** np.arange(int(T) + 1, dtype=np.float64)
+    return np.where(p < FLT_MIN, 0.0, p).astype(np.float32)
+
+
+def estimate_decay(traces, noise, lags=LAGS):
+    """The AR(1) decay of every row of ``traces`` ((K, T)) given its noise level, float64: with the autocovariances
+    ``xc[0 .. lags]`` of the mean-removed trace (divided by T) and ``a_tau = xc[tau - 1] - noise^2 [tau = 1]``, the
+    least-squares g of ``xc[tau] = g a_tau``, ``sum a_tau xc[tau] / sum a_tau^2``, clipped to [0, 0.9999]."""
+    x = np.atleast_2d(np.asarray(traces, dtype=np.float64))
+    K, T = x.shape
+    lags = int(lags)
+    if lags < 1 or T <= lags:
+        raise ValueError("estimate_decay needs 1 <= lags < T, got lags {} on {} frames".format(lags, T))
+    s2 = np.broadcast_to(np.asarray(noise, dtype=np.float64), (K,)) ** 2
+    x = x - x.mean(axis=1, keepdims=True)
+    xc = np.stack([np.einsum("kt,kt->k", x[:, :T - l], x[:, l:]) / T for l in range(lags + 1)], axis=1)
+    a = xc[:, :lags].copy()
+    a[:, 0] -= s2
+    den = np.einsum("kl,kl->k", a, a)
+    num = np.einsum("kl,kl->k", a, xc[:, 1:])
+    g = np.where(den > 0, num / np.where(den > 0, den, 1.0), 0.0)
+    return np.clip(g, 0.0, G_MAX)
+
+
+def lambda_ceiling(y, g, b):
+    """The penalty from which on the solution is c = 0, per row of ``y`` ((K, T) float32; g, b (K,) float32):
+    ``max(0, max_{t < T - 1} (y_t - b) / (1 - g), y_{T - 1} - b)`` in float64, rounded to fp32."""
+    d = np.asarray(y, dtype=np.float64) - np.asarray(b, dtype=np.float64)[:, None]
+    hi = np.maximum(0.0, d[:, -1])
+    if d.shape[1] > 1:
+        hi = np.maximum(hi, d[:, :-1].max(axis=1) / (1.0 - np.asarray(g, dtype=np.float64)))
+    return hi.astype(np.float32)
+
+
+def _collapsed(lo, hi):
+    """No fp32 number lies strictly between lo and hi."""
+    return np.nextafter(lo.astype(np.float32), np.float32(np.inf)) >= hi.astype(np.float32)
+
+
+def search_lambda(solve, target, lam_hi, rounds=5, points=8):
+    """The noise-constrained penalty of every trace: the largest lam found with ``rss(lam) <= target``.
+
+    ``solve(idx, lam) -> rss`` solves the problems (trace idx[i], penalty lam[i]) (int64 and float32 arrays of one
+    length) and returns their residual sums of squares (float64); it is the only access to the traces, so the same
+    function runs on the device and on the emulation.  ``target`` ((K,) float64) is sigma^2 T, ``lam_hi`` ((K,) float32)
+    lambda_ceiling.  Round 0 solves lam = 0 and lam = lam_hi for every trace: ``rss(0) >= target`` ends at 0 (the
+    trace is already smoother than its noise allows), ``rss(lam_hi) <= target`` ends at lam_hi (the trace is noise).
+    Every further round solves the ``points`` candidates ``fl32(lo + (hi - lo) j / (points + 1))`` of every trace
+    still searching; on the grid [lo, candidates, hi] the largest entry with rss <= target (lo always qualifies)
+    becomes lo and its successor hi.  A trace whose bracket holds no fp32 number any more drops out.
+    Returns (lam (K,) float32, evaluations (K,) int64: the solves each trace took)."""
+    target = np.asarray(target, dtype=np.float64)
+    K, m = len(target), int(points)
+    every = np.arange(K, dtype=np.int64)
+    lo, hi = np.zeros(K, dtype=np.float32), np.asarray(lam_hi, dtype=np.float32).copy()
+    r = np.asarray(solve(np.concatenate([every, every]), np.concatenate([lo, hi])), dtype=np.float64)
+    evaluations = np.full(K, 2, dtype=np.int64)
+    at_zero = r[:K] >= target
+    at_ceiling = ~at_zero & (r[K:] <= target)
+    lo[at_ceiling] = hi[at_ceiling]
+    active = ~at_zero & ~at_ceiling & ~_collapsed(lo, hi)
+    j = np.arange(1, m + 1, dtype=np.float64)
+    for _ in range(int(rounds)):
+        idx = np.nonzero(active)[0]
+        if len(idx) == 0:
+            break
+        lo64, hi64 = lo[idx].astype(np.float64), hi[idx].astype(np.float64)
+        cand = (lo64[:, None] + (hi64 - lo64)[:, None] * j / (m + 1)).astype(np.float32)
+        r = np.asarray(solve(np.repeat(idx, m), cand.reshape(-1)), dtype=np.float64).reshape(len(idx), m)
+        evaluations[idx] += m
+        grid = np.concatenate([lo[idx, None], cand, hi[idx, None]], axis=1)
+        ok = r <= target[idx, None]
+        best = np.where(ok.any(axis=1), m - np.argmax(ok[:, ::-1], axis=1), 0)     # index on the grid; 0 is lo
+        rows = np.arange(len(idx))
+        lo[idx], hi[idx] = grid[rows, best], grid[rows, best + 1]
+        active[idx] = ~_collapsed(lo[idx], hi[idx])
+    return lo, evaluations
+
+
+def workspace_bytes(T, n_prob):
+    """pmd_oasis_ar1_workspace_bytes: the pool stacks of n_prob problems."""
+    return POOL_BYTES * int(T) * int(n_prob)
+
+
+def launch_plan(n_prob, T, max_workspace_bytes):
+    """[(p0, p1), ...]: the ranges of problems one launch takes each: as many as have their pool stacks within
+    ``max_workspace_bytes``, in whole waves of 64 when more than one wave fits.  ValueError when not one problem fits."""
+    n_prob, T = int(n_prob), int(T)
+    per = int(max_workspace_bytes) // (POOL_BYTES * T)
+    if per < 1:
+        raise ValueError("max_workspace_bytes = {} does not hold the pool stack of one problem on {} frames: {} bytes "
+                         "are the least".format(int(max_workspace_bytes), T, workspace_bytes(T, 1)))
+    if per > 64:
+        per = per // 64 * 64
+    return [(p0, min(n_prob, p0 + per)) for p0 in range(0, n_prob, per)]
+
+
+def deconvolve_device_bytes(*, K, T, problems, max_workspace_bytes, stats_bytes=0):
+    """Device bytes deconvolve holds for K traces of T frames when its largest round has ``problems`` problems.  The
+    traces, the calcium, the spikes (12 K T) and the power tables (4 K (T + 1)) stay resident; the pool stacks of the
+    largest launch of launch_plan and 36 bytes of tables per problem of it come on top, and ``stats_bytes``, the
+    workspace of pmd_stats with its two outputs, when the noise is estimated."""
+    K, T = int(K), int(T)
+    largest = max(p1 - p0 for p0, p1 in launch_plan(problems, T, max_workspace_bytes))
+    need = 12 * K * T + 4 * K * (T + 1)
+    need += workspace_bytes(T, largest) + 36 * largest
+    return need + int(stats_bytes) + (1 << 20)     # the allocator's rounding of the small arrays
+
+
+def check_fit(need, free):
+    if need > free:
+        raise ValueError("deconvolve needs about {:.2f} GB of device memory, {:.2f} GB are free: lower "
+                         "max_workspace_bytes, or pass fewer traces at a time".format(need / 1e9, free / 1e9))
+
+
+def _per_trace(value, K, name, ok, rule):
+    """``value`` (a scalar or (K,)) as a (K,) float64 array whose entries all satisfy ``ok``."""
+    try:
+        a = np.asarray(value, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("{} must be a number or an array of {} numbers, got {!r}".format(name, K, value)) from None
+    if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != K):
+        raise ValueError("{} must be a scalar or of shape ({},), got shape {}".format(name, K, a.shape))
+    a = np.broadcast_to(a, (K,)).copy()
+    if not np.all(ok(a)):
+        raise ValueError("{} must satisfy {}".format(name, rule))
+    return a
+
+
+def _check_count(value, name):
+    good = isinstance(value, (int, np.integer)) and not isinstance(value, (bool, np.bool_))
+    if not good or int(value) < 1:
+        raise ValueError("{} must be an integer >= 1, got {!r}".format(name, value))
+    return int(value)
+
+
+def check_arguments(traces, g, noise, lam, s_min, baseline, search_rounds, search_points, max_workspace_bytes):
+    """The checked arguments of deconvolve, before any device work: (y (K, T) float32, g, noise, lam (each (K,) float64
+    or None), s_min, baseline ((K,) float32), rounds, points, max_workspace_bytes)."""
+    a = np.asarray(traces)
+    if a.ndim != 2 or a.dtype.kind not in "iuf" or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError("traces must be a (K, T) array of numbers with K >= 1 and T >= 1")
+    with np.errstate(over="ignore"):
+        y = np.ascontiguousarray(a, dtype=np.float32)
+    if not np.all(np.isfinite(y)):
+        raise ValueError("traces hold values that are not finite in float32")
+    K, T = y.shape
+    if T >= 2 ** 31 - 1:
+        raise ValueError("{} frames are too many: the solver counts frames in 32 bits".format(T))
+    finite = np.isfinite
+    if g is not None:
+        g = _per_trace(g, K, "g", lambda v: (v >= 0) & (v < 1), "0 <= g < 1")
+        if np.any(g.astype(np.float32) >= 1):
+            raise ValueError("g must be below 1 in float32")
+    if noise is not None:
+        noise = _per_trace(noise, K, "noise", lambda v: (v > 0) & finite(v), "noise > 0")
+    if lam is not None:
+        lam = _per_trace(lam, K, "lam", lambda v: (v >= 0) & finite(v.astype(np.float32)), "lam >= 0")
+    s_min = _per_trace(s_min, K, "s_min", lambda v: (v >= 0) & finite(v.astype(np.float32)), "s_min >= 0")
+    baseline = _per_trace(baseline, K, "baseline", lambda v: finite(v.astype(np.float32)), "a finite baseline")
+    rounds = _check_count(search_rounds, "search_rounds")
+    points = _check_count(search_points, "search_points")
+    cap = _check_count(max_workspace_bytes, "max_workspace_bytes")
+    if noise is None and T < MIN_NOISE_FRAMES:
+        raise ValueError("the noise level cannot be estimated from {} frames (the Welch window is {}): pass "
+                         "noise=".format(T, MIN_NOISE_FRAMES))
+    if g is None and T <= LAGS:
+        raise ValueError("the decay cannot be estimated from {} frames: pass g=".format(T))
+    launch_plan(1, T, cap)
+    return y, g, noise, lam, s_min.astype(np.float32), baseline.astype(np.float32), rounds, points, cap
+
+
+# ---- device side ----------------------------------------------------------------------------------------------------
+class _Solver:
+    """The traces, their parameters and tables on the device, and ``solve``: batches of (trace, penalty) problems through
+    pmd_oasis_ar1 in the launches of launch_plan."""
+
+    def __init__(self, ctx, Y, g, s_min, b, cap, largest):
+        import torch
+
+        self.ctx, self.Y, self.cap = ctx, Y, cap
+        self.T, self.K = (int(x) for x in Y.shape)
+        self.g, self.s_min, self.b = g, s_min, b
+        self.pw = torch.from_numpy(power_table(g, self.T)).to(ctx.device)
+        n = max(p1 - p0 for p0, p1 in launch_plan(largest, self.T, cap))
+        self.ws = torch.empty(workspace_bytes(self.T, n), dtype=torch.uint8, device=ctx.device)
+
+    def solve(self, idx, lam, C=None, S=None, pools=False):
+        """rss (float64) of the problems (trace idx[i], penalty lam[i]); with ``C`` / ``S`` ((T, n) device tensors) the
+        calcium and spikes of problem i go to column i; with ``pools`` returns (rss, n_pools)."""
+        import ctypes
+        import torch
+        from ._lib import ptr
+
+        ctx, T = self.ctx, self.T
+        idx = np.asarray(idx, dtype=np.int64)
+        lam = np.asarray(lam, dtype=np.float32)
+        n = len(idx)
+        if n == 0 or idx.min() < 0 or idx.max() >= self.K:
+            raise ValueError("problems must name traces 0 .. {}".format(self.K - 1))
+        par = np.stack([self.g[idx], lam, self.s_min[idx], self.b[idx]], axis=1).astype(np.float32)
+        rss, n_pools = np.empty(n, dtype=np.float64), np.empty(n, dtype=np.int32)
+        at = lambda t, p0: None if t is None else ctypes.c_void_p(t.data_ptr() + 4 * p0)   # noqa: E731
+        for p0, p1 in launch_plan(n, T, self.cap):
+            col = torch.from_numpy(idx[p0:p1].astype(np.int32)).to(ctx.device)
+            pr = torch.from_numpy(np.ascontiguousarray(par[p0:p1])).to(ctx.device)
+            r = torch.empty(p1 - p0, dtype=torch.float64, device=ctx.device)
+            npl = torch.empty(p1 - p0, dtype=torch.int32, device=ctx.device) if pools else None
+            ctx.call("pmd_oasis_ar1", ptr(self.Y), self.K, T, p1 - p0, ptr(col), ptr(pr), ptr(col), ptr(self.pw), T + 1,
+                     at(C, p0), n, at(S, p0), n, ptr(r), ptr(npl), ptr(self.ws), self.ws.numel())
+            rss[p0:p1] = r.cpu().numpy()
+            if pools:
+                n_pools[p0:p1] = npl.cpu().numpy()
+        return (rss, n_pools) if pools else rss
+
+
+def _device_noise(ctx, Y):
+    """The Welch noise level of every column of the (T, K) device matrix (pmd_stats, 1024-frame chunks), float64."""
+    import torch
+    from ._lib import ptr
+
+    T, K = (int(x) for x in Y.shape)
+    mean = torch.empty(K, dtype=torch.float32, device=ctx.device)
+    std = torch.empty(K, dtype=torch.float32, device=ctx.device)
+    ws = torch.empty(ctx.lib.pmd_stats_workspace_bytes(T, K, 1024), dtype=torch.uint8, device=ctx.device)
+    ctx.call("pmd_stats", ptr(Y), T, K, 1024, 1, ptr(mean), ptr(std), ptr(ws), ws.numel())
+    ctx.sync()
+    return std.cpu().numpy().astype(np.float64)
+
+
+# ---- public entry point --------------------------------------------------------------------------------------------
+def deconvolve(traces, g=None, noise=None, lam=None, s_min=0.0, baseline=0.0, search_rounds=5, search_points=8,
+               max_workspace_bytes=1 << 30, device=None, ctx=None):
+    """Spike inference of the rows of ``traces`` ((K, T) numbers, all finite): a Deconvolved with the denoised
+    ``calcium`` c and the ``spikes`` s >= 0 ((K, T) float32) of the AR(1) model ``c_t = g c_{t-1} + s_t``,
+    ``y = c + baseline + noise``, solved by OASIS on the device.
+
+    ``g`` (0 <= g < 1), ``noise`` (> 0), ``lam`` (>= 0), ``s_min`` (>= 0) and ``baseline`` are scalars or (K,) arrays.
+    ``noise=None`` estimates the noise level of every trace as the decomposition does for a pixel (Welch, the upper half
+    of the band; needs T >= 256, and reads high when fast transients put power there).  ``g=None`` estimates the decay
+    from the autocovariances (estimate_decay).  ``lam=None`` searches the largest penalty whose residual sum of squares
+    stays within ``noise^2 T``: round 0 and ``search_rounds`` rounds of ``search_points`` candidates per trace
+    (search_lambda), then one solve per trace at the penalty found.  ``s_min > 0`` also merges every spike below it into
+    its predecessor's pool.  The result reports what was used (``g``, ``noise``, ``lam``, ``baseline``), ``rss``,
+    ``n_pools`` and the solves each trace took (``evaluations``).
+
+    Device memory is 12 K T + 4 K (T + 1) bytes resident plus pool stacks of 12 T bytes per problem in flight, capped at
+    ``max_workspace_bytes`` (deconvolve_device_bytes); a plan that does not fit raises ValueError.  No output bit
+    depends on the cap.  Argument errors are raised before any device work."""
+    import torch
+    from .decomposition import _device_free_bytes
+
+    y, g, noise, lam, s_min, b, rounds, points, cap = check_arguments(
+        traces, g, noise, lam, s_min, baseline, search_rounds, search_points, max_workspace_bytes)
+    K, T = y.shape
+    largest = K if lam is not None else K * max(2, points)
+    with device_context(None, device, ctx) as (ctx, _):
+        stats_bytes = 0 if noise is not None else int(ctx.lib.pmd_stats_workspace_bytes(T, K, 1024)) + 8 * K
+        need = deconvolve_device_bytes(K=K, T=T, problems=largest, max_workspace_bytes=cap, stats_bytes=stats_bytes)
+        check_fit(need, _device_free_bytes(ctx.device))
+        Y = torch.from_numpy(y.T.copy()).to(ctx.device)      # frames-first, as every trace consumer here
+        if noise is None:
+            noise = _device_noise(ctx, Y)
+        if g is None:
+            g = estimate_decay(y, noise)
+        g32 = g.astype(np.float32)
+        solver = _Solver(ctx, Y, g32, s_min, b, cap, largest)
+        every = np.arange(K, dtype=np.int64)
+        if lam is None:
+            lam32, evaluations = search_lambda(solver.solve, noise ** 2 * T, lambda_ceiling(y, g32, b), rounds, points)
+        else:
+            lam32, evaluations = lam.astype(np.float32), np.zeros(K, dtype=np.int64)
+        C = torch.empty((T, K), dtype=torch.float32, device=ctx.device)
+        S = torch.empty((T, K), dtype=torch.float32, device=ctx.device)
+        rss, n_pools = solver.solve(every, lam32, C, S, pools=True)
+        ctx.sync()
+        calcium, spikes = np.ascontiguousarray(C.cpu().numpy().T), np.ascontiguousarray(S.cpu().numpy().T)
+    return Deconvolved(calcium, spikes, g32, noise, lam32, b, rss, n_pools, evaluations + 1)
