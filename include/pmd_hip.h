@@ -332,6 +332,47 @@ int pmd_oasis_ar1(pmd_ctx* ctx, const float* Y, long ldy, long T, long n_prob, c
                   const int* pw_row, const float* pw, long ldpw, float* C, long ldc, float* S, long lds, double* rss,
                   int* n_pools, void* ws, size_t ws_bytes);
 
+/* Rigid motion correction by template matching (localmd_amd/register.py, csrc/register.hip).  A frame is d1 x d2; the
+ * window is rows [my, d1 - my) x columns [mx, d2 - mx) of the template, h x w pixels, h, w >= PMD_SHIFT_MIN_WINDOW.
+ * tp is the fp32 template on the window minus its mean, row-major h x w.  With sy = dy + my, sx = dx + mx the surface of
+ * frame f is C[sy][sx] = sum_{i < h, j < w} tp[i][j] f[i + sy][j + sx] for 0 <= sy <= 2 my, 0 <= sx <= 2 mx: the
+ * un-normalised zero-mean cross-correlation; every term lies inside the frame and every shift sums h w terms.
+ *
+ * The correlation: n frames of element type elem (widened in registers), frame k at X + k frame_stride elements, the
+ *   image's pixel (y, x) at (y0 + y) row_stride + x0 + x inside it.  surf receives n (2 my + 1)(2 mx + 1) floats.
+ *   The window is cut into tiles of 32 rows x 64 columns; a tile's sum is an fmaf chain over its rows (in S = 4, 2 or 1
+ *   row ranges for (2 my + 1) ceil((2 mx + 1) / 8) <= 64, <= 128, above; the ranges are added in ascending order) and
+ *   columns in ascending order, and the tiles are added in ascending (row-major) order.  No atomics: the bits of a frame
+ *   depend on the frame, tp and the geometry only.  ws holds the tile partials of a launch group; the workspace function
+ *   sizes it for min(n, 64 MB worth of) frames, and any size of at least one frame's partials
+ *   (4 tiles (2 my + 1)(2 mx + 1) bytes) is taken.  Errors: n < 0, my or mx outside 1 .. PMD_SHIFT_MAX, d1 or d2 above
+ *   PMD_SHIFT_MAX_DIM, a window below 8 x 8, an unknown elem, y0 or x0 < 0, row_stride < x0 + d2, frame_stride <
+ *   (y0 + d1 - 1) row_stride + x0 + d2, a NULL X / tp / surf (PMD_ERR_ARG); ws NULL or too small (PMD_ERR_WORKSPACE).
+ * The peak: per frame arg = (dy, dx) of the first maximum of the surface in row-major order, NaN entries skipped;
+ *   peak its value; neigh the 3 x 3 entries around it (row-major, NaN outside the surface).  A surface without a finite
+ *   entry gives (0, 0), NaN and nine NaN.
+ * The shifted movie: out[k][y][x] from frame k shifted by ishift[2 k], ishift[2 k + 1] (the floors of the shift) and the
+ *   bilinear weights wts[4 k .. 4 k + 3] = w00, w01, w10, w11 of the samples a = f[y + iy][x + ix], b = f[y + iy][x + ix + 1],
+ *   c = f[y + iy + 1][x + ix], d = f[y + iy + 1][x + ix + 1].  Samples outside the frame are those of the nearest edge
+ *   pixel (border PMD_SHIFT_BORDER_NEAREST) or fill (PMD_SHIFT_BORDER_CONSTANT).  A frame with weights exactly
+ *   (1, 0, 0, 0) is copied: bit for bit when elem == out_elem, else converted (exactly, or quantised as below).  Every
+ *   other frame is fl(fl(fl(w00 a) + fl(w01 b)) + fl(fl(w10 c) + fl(w11 d))), no contraction; 16-bit outputs round half
+ *   to even, saturate, NaN -> 0.  Errors: n < 0, sides outside 1 .. PMD_SHIFT_MAX_DIM, unknown elem / out_elem / border,
+ *   a stride shorter than a row or a frame, a NULL pointer, X and out overlapping (PMD_ERR_ARG).
+ * None of the three synchronises or allocates; n == 0 launches nothing and returns PMD_OK. */
+#define PMD_SHIFT_MAX 31
+#define PMD_SHIFT_MIN_WINDOW 8
+#define PMD_SHIFT_MAX_DIM 16384
+#define PMD_SHIFT_BORDER_NEAREST 0
+#define PMD_SHIFT_BORDER_CONSTANT 1
+size_t pmd_shift_correlate_workspace_bytes(int n, int d1, int d2, int my, int mx);
+int pmd_shift_correlate(pmd_ctx* ctx, const void* X, int elem, long frame_stride, long row_stride, int y0, int x0, int n,
+                        int d1, int d2, int my, int mx, const float* tp, float* surf, void* ws, size_t ws_bytes);
+int pmd_shift_peak(pmd_ctx* ctx, const float* surf, int n, int my, int mx, int* arg, float* peak, float* neigh);
+int pmd_shift_apply(pmd_ctx* ctx, const void* X, int elem, long frame_stride, long row_stride, int n, int d1, int d2,
+                    const int* ishift, const float* wts, int border, float fill, void* out, int out_elem,
+                    long out_frame_stride, long out_row_stride);
+
 /* A2: background basis = rank-K rSVD of the standardised sample (pmd_loader.py:46-68, :300-314).
  * xs: pixel-major sample with round_up(D,1024) rows allocated (rows >= D zero). basis_out[c][k]. */
 size_t pmd_background_rsvd_workspace_bytes(long D, int n, int K);

@@ -17,6 +17,7 @@ from .baseline import Baseline, rolling_baseline, dff_movie, trace_baseline
 from .demix import Demixed, demix
 from .superpixels import Superpixels, superpixels
 from .deconvolve import Deconvolved, deconvolve, estimate_decay
+from .register import Registration, RegisteredMovie, register_movie, apply_shifts, subpixel_peak
 
 PMDDataset = lazy_data_loader  # the name the reference's README uses (README.md:67)
 
@@ -27,4 +28,5 @@ __all__ = [
     "regressor_maps", "event_regressors", "summary_images", "quantile_images",
     "Baseline", "rolling_baseline", "dff_movie", "trace_baseline", "Demixed", "demix",
     "Superpixels", "superpixels", "Deconvolved", "deconvolve", "estimate_decay",
+    "Registration", "RegisteredMovie", "register_movie", "apply_shifts", "subpixel_peak",
 ]
