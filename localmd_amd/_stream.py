@@ -6,11 +6,14 @@ PMDArray, how a source is read (host sources through the pinned staging ring of 
 tensors sliced in place), the 1024-frame reconstruction blocks, the walk over the blocks of a batch and the Vt columns
 of one, the uploaded statistics and R s, the host ring that results leave the device through, and the argument and
 device-memory checks the callers have in common.  Rebuilding a block of the denoised or residual movie from these is
-_expand's.  No helper knows its caller.
+_expand's.  The movie sources, the frame-batch plan and the element types are _movie.py's, the layer below this one and
+below the decomposition driver.  No helper knows its caller.
 """
 import contextlib
 
 import numpy as np
+
+from ._movie import _StreamedMovie, _device_elem, _stream_batches, _stream_dtype
 
 BLOCK = 1024            # frames per reconstruction block; blocks start on multiples of it
 
@@ -51,8 +54,6 @@ def block_plan(T, frame_batch_size, block=BLOCK):
     """[(b0, b1, [(c0, c1), ...])]: the frame batches the movie is read in (those of the streamed decomposition, whole
     1024-frame chunks) and the reconstruction blocks of each: ``block`` frames from the batch's start on, the last one
     shorter.  With block = BLOCK the blocks start on multiples of it and are the same for every frame_batch_size."""
-    from .decomposition import _stream_batches
-
     return [(b0, b1, [(c0, min(b1, c0 + block)) for c0 in range(b0, b1, block)])
             for b0, b1 in _stream_batches(T, frame_batch_size)]
 
@@ -81,19 +82,9 @@ def block_walk(plan, D):
     return walk
 
 
-def _device_elem(t):
-    import torch
-
-    m = {torch.float32: 0, torch.int16: 2}
-    if hasattr(torch, "uint16"):
-        m[torch.uint16] = 1
-    return m.get(t.dtype)
-
-
 def source_info(movie, shape):
     """(on_device, element size the movie is uploaded / read in) of a movie that must have ``shape``."""
     import torch
-    from .decomposition import _stream_dtype
 
     got = tuple(int(x) for x in movie.shape)
     if got != tuple(shape):
@@ -148,7 +139,6 @@ def read_batches(ctx, movie, batches, frame_batch_size, num_workers, consume):
     types the kernels do not read are converted to fp32); any other source goes through the pinned staging ring of the
     streamed decomposition in its own batches of frame_batch_size; without a movie every batch is None."""
     import torch
-    from .decomposition import _StreamedMovie
 
     if movie is None:
         for b0, b1 in batches:

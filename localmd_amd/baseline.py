@@ -26,6 +26,7 @@ import itertools
 import numpy as np
 
 from ._expand import Expander, expander_bytes, panel_code
+from ._movie import _device_free_bytes
 from ._stream import BLOCK, batch_buffer_bytes, block_plan, block_walk, device_context, read_batches, source_info
 
 KINDS = ("denoised", "raw")
@@ -324,8 +325,6 @@ def rolling_baseline(pmd, movie=None, *, kind="denoised", window, temporal_bin=1
     frame_batch_size, source and residency.  Device memory grows with the movie's length: 8 D ceil(T / temporal_bin)
     bytes of knots and filter output plus a workspace of up to 256 MB (baseline_device_bytes); a plan that does not fit
     raises ValueError and says to raise temporal_bin.  Argument errors are raised before any device work."""
-    from .decomposition import _device_free_bytes
-
     window = _check_window(window)
     b, on_device, esize = _check_common(pmd, movie, kind, temporal_bin, method)
     half = half_window(window, b)
@@ -356,7 +355,6 @@ def dff_movie(pmd, out, movie=None, *, kind="denoised", output="dff", baseline=N
     Every output bit is the same for every frame_batch_size, source, destination and residency.  Argument errors are
     raised before any device work and before a file is created; a file this call created is removed when it fails
     midway.  Device memory grows with the movie's length as in rolling_baseline."""
-    from .decomposition import _device_free_bytes
     from .export import _destination, _DeviceSink, _HostSink
 
     _check_name(output, OUTPUTS, "output")

@@ -26,6 +26,7 @@ Out of scope: AR(2), joint optimisation of g or of the baseline, and a rise time
 """
 import numpy as np
 
+from ._movie import _device_free_bytes
 from ._stream import device_context
 
 LAGS = 5                    # autocovariance lags estimate_decay fits
@@ -304,8 +305,6 @@ def deconvolve(traces, g=None, noise=None, lam=None, s_min=0.0, baseline=0.0, se
     ``max_workspace_bytes`` (deconvolve_device_bytes); a plan that does not fit raises ValueError.  No output bit
     depends on the cap.  Argument errors are raised before any device work."""
     import torch
-    from .decomposition import _device_free_bytes
-
     y, g, noise, lam, s_min, b, rounds, points, cap = check_arguments(
         traces, g, noise, lam, s_min, baseline, search_rounds, search_points, max_workspace_bytes)
     K, T = y.shape

@@ -37,6 +37,7 @@ C and P stay on the device for the whole call: ``8 K T`` bytes, the only term th
 import numpy as np
 import scipy.sparse
 
+from ._movie import _device_free_bytes
 from ._stream import BLOCK, VtBlocks, check_fit, device_context, factor_bytes, scaled_r, upload_f32
 from .traces import denoised_factors, roi_weights
 
@@ -159,7 +160,6 @@ def demix(pmd, rois, *, outer_iters=3, sweeps=5, update_footprints=True, nonneg_
     After ``pmd.to_device()`` its context and uploaded factors are reused; every output bit is the same either way.
     Device memory grows with the movie's length as 8 K T bytes (demix_device_bytes); a plan that does not fit raises
     ValueError.  Argument errors are raised before any device work."""
-    from .decomposition import _device_free_bytes
     from .pmdarray import PMDArray
 
     if not isinstance(pmd, PMDArray):

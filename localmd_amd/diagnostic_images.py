@@ -17,6 +17,7 @@ from typing import NamedTuple
 import numpy as np
 
 from ._lib import Context, ptr
+from ._movie import _device_free_bytes, _stream_batch_frames
 from ._stream import (batch_buffer_bytes, block_plan, check_fit, device_context, mean_std, read_batches, scaled_r,
                       source_info, upload_f32)
 
@@ -165,8 +166,6 @@ def diag_plan(T, frame_batch_size):
     """[(b0, b1, [(c0, c1), ...])]: the frame batches the movie is read in (those of the streamed decomposition, whole
     1024-frame chunks) and the reconstruction blocks of each, at most DIAG_RECON_FRAMES frames, starting on multiples of
     DIAG_FRAME_BLOCK."""
-    from .decomposition import _stream_batch_frames
-
     return block_plan(T, frame_batch_size, min(_stream_batch_frames(frame_batch_size), DIAG_RECON_FRAMES))
 
 
@@ -235,8 +234,6 @@ def make_pmd_diagnostic_images(original_movie, pmd, *, mode="max", lag=1, frame_
     ((R s) Vt[:, batch] with pmd_gemm, then U and the noise image with the expansion kernels) and one fused kernel forms
     the moments of the movie, the reconstruction and the residual; device memory does not grow with the movie's length
     except for the T doubles of frame_residual_rms."""
-    from .decomposition import _device_free_bytes
-
     (T, d1, d2), lag, on_device, esize = _check_args(original_movie, pmd, mode, lag)
     D = d1 * d2
     plan = diag_plan(T, frame_batch_size)

@@ -27,6 +27,7 @@ import threading
 import numpy as np
 
 from ._expand import ENTRY_FIELDS, EXPORT_PATCH, _PANEL_CODE, Expander, expander_bytes, panel_code  # noqa: F401
+from ._movie import _ELEM, _device_free_bytes
 from ._stream import BLOCK as EXPORT_BLOCK, block_plan as export_plan
 from ._stream import (batch_buffer_bytes, block_walk, check_fit, device_context, name_tuple, read_batches,
                       source_info)
@@ -36,7 +37,6 @@ HOST_SLOTS = 2          # device + page-locked output buffers of a host destinat
 COPY_THREADS = 8        # threads that copy a block into a NumPy destination
 PANELS = ("raw", "denoised", "residual")
 _OUT_DTYPES = {"float32": np.float32, "uint16": np.uint16, "int16": np.int16}
-_ELEM = {np.dtype(np.float32): 0, np.dtype(np.uint16): 1, np.dtype(np.int16): 2}   # PMD_ELEM_F32 / _U16 / _I16
 
 
 def quantize(v, dtype):
@@ -281,7 +281,6 @@ def export_movie(pmd, out, movie=None, *, panels="denoised", dtype="float32", fr
     "uint16" or "int16" (round half to even, saturating, NaN -> 0: quantize).  After ``pmd.to_device()`` its context
     and uploaded factors are reused.  Argument errors are raised before any device work and before a file is created;
     a file this call created is removed when it fails midway."""
-    from .decomposition import _device_free_bytes
     from .pmdarray import PMDArray
 
     if not isinstance(pmd, PMDArray):

@@ -22,6 +22,7 @@ source.  The movie is read once through the scaffold of _stream; device memory d
 import numpy as np
 
 from ._expand import Expander, expander_bytes, interleave, panel_code, split_panels
+from ._movie import _device_free_bytes
 from ._stream import (BLOCK, batch_buffer_bytes, block_plan, block_walk, check_fit, device_context, name_tuple,
                       read_batches, source_info, upload_f32)
 
@@ -156,7 +157,6 @@ def regressor_maps(pmd, regressors, movie=None, *, kinds="denoised", stat="sum",
     device tensors (sliced in place).  After ``pmd.to_device()`` its context and uploaded factors are reused.  Every
     map has the same bits for every frame_batch_size and source.  Argument errors are raised before any device work
     and before the movie is read."""
-    from .decomposition import _device_free_bytes
     from .export import expand_tables_for
     from .pmdarray import PMDArray
 

@@ -23,8 +23,9 @@ call reduces in chunk order.
 import numpy as np
 import scipy.sparse
 
+from ._movie import _device_free_bytes
 from ._stream import ToHost, device_context, mean_std, read_batches, upload_f32
-from .decomposition import _device_free_bytes, _projected_svd_dev, display
+from .decomposition import _projected_svd_dev, display
 from .pmdarray import PMDArray
 
 # Largest group support: the largest tile the decomposition accepts (40 x 40 pixels, pmd_pick_dvariant), so a tile is

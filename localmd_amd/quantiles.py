@@ -23,6 +23,7 @@ The device only counts integers, so every output bit is the same for every batch
 import numpy as np
 
 from ._expand import Expander, expander_bytes, interleave, panel_code, split_panels
+from ._movie import _device_free_bytes
 from ._stream import (batch_buffer_bytes, block_plan, block_walk, check_fit, device_context, name_tuple,
                       read_batches, source_info, upload_f32)
 from .maps import KINDS
@@ -161,7 +162,6 @@ def quantile_images(pmd, movie=None, *, kinds="denoised", q=0.5, mad=False, inte
     for every order and subset of kinds and q.  Argument errors are raised before any device work and before the movie
     is read; a decomposition of no frames has no order statistics and raises ValueError.  A plan that does not fit the
     free device memory raises ValueError (1 KB per pixel, kind and distinct rank)."""
-    from .decomposition import _device_free_bytes
     from .export import expand_tables_for
     from .pmdarray import PMDArray
 

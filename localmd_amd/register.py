@@ -26,6 +26,7 @@ destination.  Device memory does not grow with the movie's length.
 """
 import numpy as np
 
+from ._movie import _ELEM, _device_elem, _device_free_bytes, _stream_dtype
 from ._stream import BLOCK, batch_buffer_bytes, block_plan, block_walk, check_fit, device_context, read_batches
 from .dataset import lazy_data_loader
 
@@ -35,7 +36,6 @@ MAX_DIM = 16384              # PMD_SHIFT_MAX_DIM
 MAX_ABS_SHIFT = 1 << 30      # shifts given to apply_shifts: their floors are int32 with room for the + 1
 WS_TARGET = 64 << 20         # RG_WS_TARGET of csrc/register.hip: the tile partials of one launch group, about
 TILE_ROWS, TILE_COLS = 32, 64
-_ELEM = {np.dtype(np.float32): 0, np.dtype(np.uint16): 1, np.dtype(np.int16): 2}
 _OUT_DTYPES = ("float32", "uint16", "int16")
 
 
@@ -243,8 +243,6 @@ class RegisteredMovie(lazy_data_loader):
     register_movie (None: the movie's own when every shift is an integer, else float32)."""
 
     def __init__(self, movie, registration, border=None, dtype=None):
-        from .decomposition import _stream_dtype
-
         T, d1, d2 = (int(x) for x in movie.shape)
         shifts = registration.shifts if isinstance(registration, Registration) else registration
         self._shifts = check_shifts(shifts, T)
@@ -283,8 +281,6 @@ def _resolve_dtype(dtype, src_dtype, whole):
 def _movie_info(movie):
     """(T, d1, d2, on_device, staged dtype) of a source."""
     import torch
-    from ._stream import _device_elem
-    from .decomposition import _stream_dtype
 
     try:
         shape = tuple(int(x) for x in movie.shape)
@@ -294,8 +290,7 @@ def _movie_info(movie):
         raise ValueError("movie must have shape (T, d1, d2), got {}".format(shape))
     if isinstance(movie, torch.Tensor) and movie.device.type != "cpu":
         e = _device_elem(movie[:0])
-        dt = {0: np.float32, 1: np.uint16, 2: np.int16}.get(e, np.float32)
-        return shape + (True, np.dtype(dt))
+        return shape + (True, next((dt for dt, code in _ELEM.items() if code == e), np.dtype(np.float32)))
     src = movie.detach().numpy() if isinstance(movie, torch.Tensor) else movie
     return shape + (False, _stream_dtype(src))
 
@@ -433,7 +428,6 @@ def _run(movie, info, out_dest, out_dtype, border, est_args, given_shifts, frame
     import ctypes as C
     import itertools
     from ._stream import ToHost
-    from .decomposition import _device_free_bytes
     from .export import _DeviceSink, _HostSink
 
     T, d1, d2, on_device, np_dtype = info

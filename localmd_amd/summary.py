@@ -20,6 +20,7 @@ source.  The movie is read once through the scaffold of _stream; device memory d
 import numpy as np
 
 from ._expand import Expander, expander_bytes, interleave, panel_code, split_panels
+from ._movie import _device_free_bytes
 from ._stream import (batch_buffer_bytes, block_plan, block_walk, check_fit, device_context, name_tuple,
                       read_batches, source_info, upload_f32)
 from .maps import GAMMA, KINDS, centring_vector
@@ -128,7 +129,6 @@ def summary_images(pmd, movie=None, *, kinds="denoised", stats=("mean", "std", "
     ``pmd.to_device()`` its context and uploaded factors are reused.  Every image has the same bits for every
     frame_batch_size and source, for every order and subset of kinds and stats.  Argument errors are raised before any
     device work and before the movie is read; a decomposition of no frames has no extrema and raises ValueError."""
-    from .decomposition import _device_free_bytes
     from .export import expand_tables_for
     from .pmdarray import PMDArray
 

@@ -21,6 +21,7 @@ Device memory does not grow with the movie's length (superpixel_device_bytes).
 import numpy as np
 
 from ._expand import Expander, expander_bytes, panel_code
+from ._movie import _device_free_bytes
 from ._stream import (batch_buffer_bytes, block_plan, block_walk, check_fit, device_context, read_batches, source_info,
                       upload_f32)
 from .quantiles import movie_passes, quantile_device_bytes, quantile_images
@@ -221,7 +222,6 @@ def superpixels(pmd, movie=None, *, kind="denoised", th=2.0, cut_off=0.9, min_si
     has the same bits for every frame_batch_size, source and residency, and for order "C" and "F" of the same movie.
     Argument errors are raised before any device work and before the movie is read; a decomposition of no frames raises
     ValueError, and so does a plan that does not fit the free device memory."""
-    from .decomposition import _device_free_bytes
     from .export import expand_tables_for
     from .pmdarray import PMDArray
 

@@ -71,6 +71,7 @@ def main():
     a = ap.parse_args()
     import torch
     from localmd_amd import decomposition as Dm
+    from localmd_amd._movie import _stream_batch_frames
     from localmd_amd._lib import Context
     from localmd_amd.dataset import ArrayDataset
 
@@ -81,7 +82,7 @@ def main():
         T = max(4096, int(0.8 * avail / (7.0 * D)) // 1024 * 1024)
         print("host memory: T reduced to {}".format(T), file=sys.stderr)
     ctx = Context(0)
-    res = {"shape": [T, d, d], "frame_range": a.frame_range, "batch_frames": Dm._stream_batch_frames(10000),
+    res = {"shape": [T, d, d], "frame_range": a.frame_range, "batch_frames": _stream_batch_frames(10000),
            "h2d_pinned_gbs": {"float32": h2d_rate(np.float32, D), "uint16": h2d_rate(np.uint16, D)}}
     t0 = time.perf_counter()
     mov = make(T, d)

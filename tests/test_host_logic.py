@@ -392,7 +392,7 @@ def test_lazy_loader_is_never_reentered_by_default():
     import types
     import torch
     from localmd_amd.dataset import lazy_data_loader
-    from localmd_amd.decomposition import _Movie
+    from localmd_amd._movie import _Movie
 
     rng = np.random.default_rng(1)
     data = rng.random((64, 9, 7)).astype(np.float32)
@@ -534,7 +534,7 @@ def test_movie_upload_handles_one_frame_batches():
     import types
     import torch
     from localmd_amd.dataset import ArrayDataset
-    from localmd_amd.decomposition import _Movie
+    from localmd_amd._movie import _Movie
 
     rng = np.random.default_rng(0)
     data = rng.random((11, 12, 13)).astype(np.float32)
