@@ -401,7 +401,8 @@ int pmd_threshold_sim(pmd_ctx* ctx, int b1, int b2, int t, int iters, uint64_t s
  * pool_q[P][pool_max]: local pixels of pooling window p (-1 pads); pool_idx[q]: window of pixel q;
  * pool_w[q] = 1/|window|.  n_rows = pixel rows of xf.  Outputs, with rp = pmd_tile_rpad(r): Ut_out[n][rp][dpad],
  * V_out[n][rp][ldv] (= sigma*V rows), stats_out[n][rp][2], good_out/keep_out[n][rp], ranks_out[n], lam_out[n][rp]
- * (sigma^2, may be NULL).  r is unbounded as in the reference (decomposition.py:643-665); r + 10 > 64 runs the
+ * (sigma^2, may be NULL).  min(r, t_crop / a, P) components exist; the rows from there on are written as zeros in every
+ * output (frames < t_crop of V_out).  r is unbounded as in the reference (decomposition.py:643-665); r + 10 > 64 runs the
  * generic-width kernels of wide.hip. */
 size_t pmd_tiles_workspace_bytes(int n_tiles, int b1, int b2, int P, int r, int a, int t_crop, long ldv, long n_rows);
 int pmd_tiles_decompose(pmd_ctx* ctx, const float* xf, long ldx, long n_rows, int t_crop, const int* tile_pix, int n_tiles, int b1,
@@ -624,6 +625,20 @@ int pmdk_small_qr(pmd_ctx* ctx, const float* Yt, long y_tile_stride, int y_ld, i
                   long q_tile_stride, int q_ld, int n_tiles);
 int pmdk_small_eig(pmd_ctx* ctx, const double* G, int slices, int n, int mode, double tol, double* Nout,
                    double* lam_out, int n_tiles);
+/* Cholesky whitening of the 64-row path: G[tile][slices][64][64], Nout[tile][64][64] = inverse of the upper factor of the
+ * symmetrised slice sum's leading n x n block; a pivot <= tol * max diagonal gives a zero column; zero outside n x n. */
+int pmdk_small_chol(pmd_ctx* ctx, const double* G, int slices, int n, double tol, double* Nout, int n_tiles);
+/* generic width (rp a multiple of 64): G[tile][slices][rp][rp] = In In2^T over `slices` position ranges (In2 NULL: In) */
+int pmdk_wide_gram(pmd_ctx* ctx, const float* In, long tile_stride, long ld, int len, int n_tiles, int slices, int rp,
+                   double* G, const float* In2);
+/* workspace of pmdk_wide_eig for n_tiles problems of order n */
+size_t pmdk_wide_eig_workspace_bytes(int n, int n_tiles);
+/* pmdk_small_eig at any rp: G[tile][slices][rp][rp], Nout[tile][rp][rp], lam_out[tile][rp], order n <= rp (rocSOLVER) */
+int pmdk_wide_eig(pmd_ctx* ctx, const double* G, int slices, int rp, int n, int mode, double tol, double* Nout,
+                  double* lam_out, int n_tiles, void* ws, size_t ws_bytes);
+/* pmdk_tile_rowmix at any rp: N[tile][rp][rp] (n_tile_stride 0: shared); rows [n_out, rp) of Out are zeroed up to len */
+int pmdk_wide_rowmix(pmd_ctx* ctx, const float* In, long in_tile_stride, long ld_in, const double* N, long n_tile_stride,
+                     int rp, int n_in, int n_out, float* Out, long out_tile_stride, long ld_out, int len, int n_tiles);
 int pmdk_tile_pool_bin(pmd_ctx* ctx, const float* X, long ldx, long n_rows, const int* pix, int n_tiles, int d,
                        const int* pool_q, int pool_max, int P, int a, int nbins, float* xbar, float* abar, long ld_ab,
                        long tile_stride);

@@ -135,6 +135,11 @@ SIGNATURES = {
     "pmdk_tile_rowmix": (c_i, [c_p, c_p, c_l, c_l, c_p, c_l, c_i, c_i, c_p, c_l, c_l, c_i, c_i]),
     "pmdk_small_qr": (c_i, [c_p, c_p, c_l, c_i, c_i, c_i, c_p, c_l, c_i, c_i]),
     "pmdk_small_eig": (c_i, [c_p, c_p, c_i, c_i, c_i, c_d, c_p, c_p, c_i]),
+    "pmdk_small_chol": (c_i, [c_p, c_p, c_i, c_i, c_d, c_p, c_i]),
+    "pmdk_wide_gram": (c_i, [c_p, c_p, c_l, c_l, c_i, c_i, c_i, c_i, c_p, c_p]),
+    "pmdk_wide_eig_workspace_bytes": (c_sz, [c_i, c_i]),
+    "pmdk_wide_eig": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_d, c_p, c_p, c_i, c_p, c_sz]),
+    "pmdk_wide_rowmix": (c_i, [c_p, c_p, c_l, c_l, c_p, c_l, c_i, c_i, c_i, c_p, c_l, c_l, c_i, c_i]),
     "pmdk_tile_pool_bin": (c_i, [c_p, c_p, c_l, c_l, c_p, c_i, c_i, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_l, c_l]),
     "pmdk_roughness": (c_i, [c_p, c_p, c_l, c_i, c_i, c_i, c_p, c_l, c_l, c_i, c_i, c_p, c_i]),
     "pmdk_syevd": (c_i, [c_p, c_i, c_p, c_l, c_p, c_p, c_p]),

@@ -47,7 +47,7 @@ int pmd_launch_expand_pooled(pmd_ctx* ctx, const float* In, long in_tile_stride,
 int pmd_launch_stats_roughness(pmd_ctx* ctx, const float* Ut, long u_tile_stride, int u_ld, int b1, int b2,
                                const float* V, long v_tile_stride, long v_ld, int T, int r, float* stats, int n_tiles,
                                int rp);
-int pmd_launch_decide(pmd_ctx* ctx, const float* stats, int r, float thr_s, float thr_t, int max_fail, int cap,
+int pmd_launch_decide(pmd_ctx* ctx, float* stats, int r, float thr_s, float thr_t, int max_fail, int cap,
                       int n_tiles, int* good, int* keep, int* ranks, int rp);
 
 // wide.hip: generic-width forms of the small dense algebra (per-tile arrays [tile][rp][x], rp = pmd_tile_rpad(r) > 64),

@@ -440,6 +440,11 @@ int pmd_launch_small_chol(pmd_ctx* ctx, const double* G, int slices, int n, doub
   return PMD_OK;
 }
 
+extern "C" int pmdk_small_chol(pmd_ctx* ctx, const double* G, int slices, int n, double tol, double* Nout, int n_tiles) {
+  CTX_CHECK(ctx);
+  return pmd_launch_small_chol(ctx, G, slices, n, tol, Nout, n_tiles);
+}
+
 // ---------------------------------------------------------------- pooled basis expansion ---
 // Out[tile][c][q] = In[tile][c][pool_idx[q]] * pool_w[q]   (U_ds^T composed with the pooling map)
 __global__ void expand_pooled_kernel(const float* __restrict__ In, long in_tile_stride, int in_ld,
@@ -546,8 +551,9 @@ extern "C" int pmdk_roughness(pmd_ctx* ctx, const float* Ut, long u_tile_stride,
   return pmd_launch_stats_roughness(ctx, Ut, u_tile_stride, u_ld, b1, b2, V, v_tile_stride, v_ld, T, r, stats, n_tiles, PMD_RPAD);
 }
 
-// evaluation.py:133-164 + :195-222.  keep[tile][c] in {0,1}; ranks[tile] = number kept (capped).
-__global__ void decide_kernel(const float* __restrict__ stats, int r, float thr_s, float thr_t, int max_fail, int cap,
+// evaluation.py:133-164 + :195-222.  keep[tile][c] in {0,1}; ranks[tile] = number kept (capped).  The statistics of the rows
+// from r on, which no component fills, are cleared: every row of every output is then written by the call.
+__global__ void decide_kernel(float* __restrict__ stats, int r, float thr_s, float thr_t, int max_fail, int cap,
                               int n_tiles, int* __restrict__ good, int* __restrict__ keep, int* __restrict__ ranks, int rp) {
   const int tile = blockIdx.x * blockDim.x + threadIdx.x;
   if (tile >= n_tiles) return;
@@ -570,6 +576,9 @@ __global__ void decide_kernel(const float* __restrict__ stats, int r, float thr_
       }
       if (k && count >= cap) k = 0;
       count += k;
+    } else {
+      stats[((long)tile * rp + c) * 2 + 0] = 0.f;
+      stats[((long)tile * rp + c) * 2 + 1] = 0.f;
     }
     good[(long)tile * rp + c] = g;
     keep[(long)tile * rp + c] = k;
@@ -577,7 +586,7 @@ __global__ void decide_kernel(const float* __restrict__ stats, int r, float thr_
   ranks[tile] = count;
 }
 
-int pmd_launch_decide(pmd_ctx* ctx, const float* stats, int r, float thr_s, float thr_t, int max_fail, int cap,
+int pmd_launch_decide(pmd_ctx* ctx, float* stats, int r, float thr_s, float thr_t, int max_fail, int cap,
                       int n_tiles, int* good, int* keep, int* ranks, int rp) {
   pmd_prof_scope prof__(ctx, "decide");
   hipLaunchKernelGGL(decide_kernel, dim3((n_tiles + 63) / 64), dim3(64), 0, ctx->stream, stats, r, thr_s, thr_t,

@@ -227,6 +227,28 @@ int pmd_launch_wide_rowmix(pmd_ctx* ctx, const float* In, long in_tile_stride, l
   return PMD_OK;
 }
 
+// ---------------------------------------------------------------- kernel-level entry points (parity tests) -----
+extern "C" int pmdk_wide_gram(pmd_ctx* ctx, const float* In, long tile_stride, long ld, int len, int n_tiles, int slices, int rp,
+                              double* G, const float* In2) {
+  CTX_CHECK(ctx);
+  return pmd_launch_wide_gram(ctx, In, tile_stride, ld, len, n_tiles, slices, rp, G, In2);
+}
+
+extern "C" size_t pmdk_wide_eig_workspace_bytes(int n, int n_tiles) { return pmd_wide_eig_workspace_bytes(n, n_tiles); }
+
+extern "C" int pmdk_wide_eig(pmd_ctx* ctx, const double* G, int slices, int rp, int n, int mode, double tol, double* Nout,
+                             double* lam_out, int n_tiles, void* ws, size_t ws_bytes) {
+  CTX_CHECK(ctx);
+  return pmd_launch_wide_eig(ctx, G, slices, rp, n, mode, tol, Nout, lam_out, n_tiles, ws, ws_bytes);
+}
+
+extern "C" int pmdk_wide_rowmix(pmd_ctx* ctx, const float* In, long in_tile_stride, long ld_in, const double* N, long n_tile_stride,
+                                int rp, int n_in, int n_out, float* Out, long out_tile_stride, long ld_out, int len, int n_tiles) {
+  CTX_CHECK(ctx);
+  return pmd_launch_wide_rowmix(ctx, In, in_tile_stride, ld_in, N, n_tile_stride, rp, n_in, n_out, Out, out_tile_stride, ld_out, len,
+                                n_tiles);
+}
+
 // ---------------------------------------------------------------- streaming contractions in row blocks of 64 ----
 // A: [tile][rp][a_ld], Out: [tile][rp][ldo]; rows [0, nrows) are computed (whole blocks of 64), the tile strides are the
 // caller's (rp * ld)
