@@ -373,6 +373,67 @@ int pmd_shift_apply(pmd_ctx* ctx, const void* X, int elem, long frame_stride, lo
                     const int* ishift, const float* wts, int border, float fill, void* out, int out_elem,
                     long out_frame_stride, long out_row_stride);
 
+/* Piecewise-rigid motion correction (localmd_amd/piecewise.py, csrc/piecewise.hip): patch surfaces around every frame's
+ * rigid peak, and the warp by the smooth field the patch shifts span.  max_shift = (my, mx) as above; max_deviation =
+ * (ey, ex), each in 1 .. PMD_PATCH_MAX_DEV.  oy = my + ey, ox = mx + ex.
+ *
+ * Patch area: rows [oy, d1 - oy) x columns [ox, d2 - ox) of the template, Hh x Ww pixels, so that every term of every
+ *   patch surface lies inside the frame and every entry sums the same number of terms.
+ * Patches: ph x pw pixels, 8 <= ph <= Hh, 8 <= pw <= Ww, at strides 1 <= sy <= ph, 1 <= sx <= pw (no gaps).  Row starts
+ *   a_i = min(i sy, Hh - ph) for i < gy = 1 + ceil((Hh - ph) / sy), columns the same; P = gy gx <= PMD_PATCH_MAX.
+ *   t'_p is the fp32 template on patch p minus that patch's own mean (float64 on the host, rounded once), packed
+ *   (P, ph, pw), p = i gx + j.
+ * Patch surfaces: with (cy_k, cx_k) = centre[2 k], centre[2 k + 1] the integer rigid peak of frame k, for 0 <= v <= 2 ey,
+ *   0 <= u <= 2 ex
+ *     C_{k,p}[v][u] = sum_{i < ph, j < pw} t'_p[i][j] f_k[oy + a_p + i + cy_k + v - ey][ox + b_p + j + cx_k + u - ex],
+ *   the un-normalised zero-mean correlation of the patch searched around the frame's own rigid peak.  surf receives
+ *   n P (2 ey + 1)(2 ex + 1) floats, frame-major, then patch, then row-major (v, u).  Element types as for
+ *   pmd_shift_correlate, widened in registers.  Summation order: a patch is cut into tiles of 32 rows x 64 columns;
+ *   inside a tile the rows fall into K = min(32, 256 / (2 ey + 1)) residue classes (row i belongs to class i mod K); an
+ *   accumulator is one fmaf chain over the rows of its class ascending, then the columns ascending; the K classes are
+ *   added in ascending order, then the tiles in ascending (row-major) order.  No atomics: the bits of a (frame, patch)
+ *   surface depend on that frame, t'_p, the centre and the geometry only, not on n, the launch group or the other
+ *   patches.  A centre with |cy| > my or |cx| > mx is clamped in the kernel.  ystart (gy ints), xstart (gx ints) and
+ *   centre are device tables, so the host cannot see them without synchronising: a start outside 0 .. Hh - ph
+ *   (0 .. Ww - pw) is clamped in the kernel as well, it is not an error; no table can cause a read outside the frame.
+ *   ws holds the tile partials of a launch group (4 P tiles (2 ey + 1)(2 ex + 1) bytes per frame); the workspace
+ *   function sizes it for min(n, 64 MB worth of) frames and any size of at least one frame's partials is taken.
+ *   Errors: n < 0, my or mx outside 1 .. PMD_SHIFT_MAX, ey or ex outside 1 .. PMD_PATCH_MAX_DEV, d1 or d2 above
+ *   PMD_SHIFT_MAX_DIM, ph or pw below 8 or above the patch area, gy or gx < 1 or gy gx > PMD_PATCH_MAX, an unknown elem,
+ *   row_stride < d2, frame_stride < (d1 - 1) row_stride + d2, a NULL X / ystart / xstart / centre / tp / surf
+ *   (PMD_ERR_ARG); ws NULL or too small (PMD_ERR_WORKSPACE).
+ * Patch peaks: pmd_shift_peak on the n P surfaces with (my, mx) = (ey, ex).  The patch shift is (cy_k + dy_p, cx_k + dx_p)
+ *   plus the parabola's offset (host, float64); a patch whose surface has no finite entry, or whose t'_p is all zero,
+ *   takes the frame's rigid shift.
+ * Field: patch centres yc_i = oy + a_i + (ph - 1) / 2.  Per row y the host gives row_idx[y] = i0 in 0 .. max(gy - 2, 0)
+ *   and row_w[y] = ay = clip((y - yc_i0) / (yc_{i0 + 1} - yc_i0), 0, 1) (float64, rounded once; 0 when gy = 1): the field
+ *   is constant beyond the outermost centres.  Columns the same.  grid holds per frame the (gy, gx, 2) patch shifts
+ *   (dy, dx) in fp32.  The shift of a pixel, per component, every operation rounded on its own:
+ *     top = fl(g00 + fl(ax fl(g01 - g00))), bot the same on grid row i0 + 1, s = fl(top + fl(ay fl(bot - top))),
+ *   so a grid whose entries are all equal gives exactly that value.  Table indices are clamped to 0 .. g - 2 in the
+ *   kernel (and the second index to g - 1).
+ * Warp: Y = fl(float(y) + s_y) clamped to [-1, d1], a NaN acting as -1; iy = floor(Y), fy = Y - iy (exact); columns the
+ *   same; w00 = fl(fl(1 - fy) fl(1 - fx)), w01 = fl(fl(1 - fy) fx), w10 = fl(fy fl(1 - fx)), w11 = fl(fy fx);
+ *   out[y][x] = quant(fl(fl(fl(w00 a) + fl(w01 b)) + fl(fl(w10 c) + fl(w11 d)))) with the samples a, b, c, d at
+ *   (iy, ix), (iy, ix + 1), (iy + 1, ix), (iy + 1, ix + 1), their border handling and quant those of pmd_shift_apply; no
+ *   contraction, no copy path.  On a frame of finite pixels (none of them -0.0) a grid whose entries are all the same
+ *   integer pair gives the bits of pmd_shift_apply for that shift.  Errors: n < 0, sides outside 1 .. PMD_SHIFT_MAX_DIM,
+ *   gy or gx outside 1 .. PMD_WARP_MAX_GRID, unknown elem / out_elem / border, a stride shorter than a row or a frame, a
+ *   NULL pointer, X and out overlapping (PMD_ERR_ARG).
+ * Neither synchronises or allocates; n == 0 launches nothing and returns PMD_OK. */
+#define PMD_PATCH_MAX_DEV 7
+#define PMD_PATCH_MAX 4096
+#define PMD_WARP_MAX_GRID 64
+size_t pmd_patch_correlate_workspace_bytes(int n, int d1, int d2, int my, int mx, int ey, int ex, int ph, int pw, int gy,
+                                           int gx);
+int pmd_patch_correlate(pmd_ctx* ctx, const void* X, int elem, long frame_stride, long row_stride, int n, int d1, int d2,
+                        int my, int mx, int ey, int ex, int ph, int pw, int gy, int gx, const int* ystart,
+                        const int* xstart, const int* centre, const float* tp, float* surf, void* ws, size_t ws_bytes);
+int pmd_warp_apply(pmd_ctx* ctx, const void* X, int elem, long frame_stride, long row_stride, int n, int d1, int d2,
+                   const float* grid, int gy, int gx, const int* row_idx, const float* row_w, const int* col_idx,
+                   const float* col_w, int border, float fill, void* out, int out_elem, long out_frame_stride,
+                   long out_row_stride);
+
 /* A2: background basis = rank-K rSVD of the standardised sample (pmd_loader.py:46-68, :300-314).
  * xs: pixel-major sample with round_up(D,1024) rows allocated (rows >= D zero). basis_out[c][k]. */
 size_t pmd_background_rsvd_workspace_bytes(long D, int n, int K);

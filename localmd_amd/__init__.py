@@ -18,6 +18,7 @@ from .demix import Demixed, demix
 from .superpixels import Superpixels, superpixels
 from .deconvolve import Deconvolved, deconvolve, estimate_decay
 from .register import Registration, RegisteredMovie, register_movie, apply_shifts, subpixel_peak
+from .piecewise import PiecewiseRegistration, WarpedMovie, register_piecewise, apply_field, warp_frames
 
 PMDDataset = lazy_data_loader  # the name the reference's README uses (README.md:67)
 
@@ -29,4 +30,5 @@ __all__ = [
     "Baseline", "rolling_baseline", "dff_movie", "trace_baseline", "Demixed", "demix",
     "Superpixels", "superpixels", "Deconvolved", "deconvolve", "estimate_decay",
     "Registration", "RegisteredMovie", "register_movie", "apply_shifts", "subpixel_peak",
+    "PiecewiseRegistration", "WarpedMovie", "register_piecewise", "apply_field", "warp_frames",
 ]

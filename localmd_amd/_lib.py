@@ -63,6 +63,11 @@ SIGNATURES = {
     "pmd_shift_correlate": (c_i, [c_p, c_p, c_i, c_l, c_l, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_sz]),
     "pmd_shift_peak": (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p]),
     "pmd_shift_apply": (c_i, [c_p, c_p, c_i, c_l, c_l, c_i, c_i, c_i, c_p, c_p, c_i, c_f, c_p, c_i, c_l, c_l]),
+    "pmd_patch_correlate_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i]),
+    "pmd_patch_correlate": (c_i, [c_p, c_p, c_i, c_l, c_l, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p,
+                                  c_p, c_p, c_p, c_p, c_sz]),
+    "pmd_warp_apply": (c_i, [c_p, c_p, c_i, c_l, c_l, c_i, c_i, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_f, c_p, c_i,
+                             c_l, c_l]),
     "pmd_background_rsvd_workspace_bytes": (c_sz, [c_l, c_i, c_i]),
     "pmd_background_rsvd": (c_i, [c_p, c_p, c_l, c_i, c_l, c_i, c_u64, c_p, c_p, c_sz]),
     "pmd_bg_project_workspace_bytes": (c_sz, [c_l, c_i]),
