@@ -207,11 +207,12 @@ int pmd_pixel_hist_accumulate(pmd_ctx* ctx, const void* Y, int elem, long ldy, l
 int pmd_pixel_hist_select(pmd_ctx* ctx, long D, uint32_t* hist, int* rank, uint32_t* prefix);
 
 /* Rolling baseline and dF/F along time (localmd_amd/baseline.py, csrc/baseline.hip): the series of a pixel is reduced to
- * knots (bin means), the knots are filtered by a sliding minimum and / or maximum, and the baseline of a frame is
+ * knots (bin means), the knots are filtered by a sliding minimum and / or maximum or by a sliding order statistic, and the
+ * baseline of a frame is
  * interpolated between the knots.  All matrices are frames-first with a leading dimension in elements; every fp32
  * operation below is rounded on its own (no contraction).  The bits written for pixel c depend on column c of the inputs
  * and the scalar arguments only: not on N, the leading dimensions, alignment, the element type holding the same values
- * or the pixel's position.  None of the three synchronises or allocates; an argument error returns PMD_ERR_ARG with
+ * or the pixel's position.  None of them synchronises or allocates; an argument error returns PMD_ERR_ARG with
  * nothing launched.
  *
  * pmd_bin_means: Y holds the n frames f0 .. f0 + n of a series (1 <= n <= PMD_STATS_BLOCK, element type elem, ldy >= N);
@@ -231,6 +232,25 @@ int pmd_pixel_hist_select(pmd_ctx* ctx, long D, uint32_t* hist, int* rank, uint3
  *   Errors: n < 1, N < 1, N > 65535 * 256, ldx < N, ldo < N, half < 0, is_max not 0 / 1, a NULL pointer, work_floats too
  *   small, X and out overlapping.
  *
+ * pmd_sliding_quantile: the sliding order statistic.  X is n x N fp32, frames-first, ldx >= N; out is n x N, ldo >= N, and
+ *   does not overlap X.  W = 2 half + 1.  The window of output (j, c) is the multiset X[clamp(j + i, 0, n - 1)][c] for
+ *   i = -half .. half: the edges are replicated (scipy.ndimage's mode "nearest"), not cut, so every window has W members
+ *   and one rank serves every output.  out[j][c] is the member at 0-based position rank when the window is ordered by the
+ *   keys of pmd_pixel_hist_accumulate (quantiles.float_keys: -0 before +0, every NaN last); the value written is
+ *   quantiles.key_floats of that key, so a NaN comes out as the NaN with the bits 0x7FFFFFFF.  rank = 0 is the sliding
+ *   minimum that drops NaN unless the whole window is NaN, rank = 2 half the maximum with NaN winning.  half >= 0 may
+ *   exceed n.
+ *   The bits of column c depend on column c, n, half and rank only: not on N, the leading dimensions, alignment, the
+ *   column's position or a split into column ranges (X + c0, out + c0).  No global atomics.  A wave takes
+ *   PMD_SLIDING_QUANTILE_SLICE consecutive outputs: a 32-step bisection on the key for the first, then per output one
+ *   member leaves and one enters and the answer moves by at most one distinct value, found by one scan of the window.
+ *   The element visits per output and column are O(min(W, n)): a scan reads the rows the window really holds once, and
+ *   counts the replicated first and last row with a multiplicity.
+ *   work: at least pmd_sliding_quantile_work_floats(n, N, half) floats of device memory; the query returns 0 (the state
+ *   lives in registers) and work may then be NULL.
+ *   Errors: n < 1 or n >= 2^31, N < 1, N > 65535 * 256, ldx < N, ldo < N, half < 0 or half >= 2^30, rank outside
+ *   0 .. 2 half, NULL X or out, X and out overlapping, work_floats below the query (or NULL work with a query above 0).
+ *
  * pmd_baseline_apply: frames f0 .. f0 + n (1 <= n <= PMD_STATS_BLOCK, f0 >= 0, f0 + n <= T) of a series of T frames,
  *   1 <= T < PMD_BASELINE_MAX_FRAMES, whose ceil(T / bin) knots are the rows of K (ldk >= N).  Bin j has n_j = min(bin,
  *   T - j bin) frames and the centre c_j = j bin + (n_j - 1) / 2 (exact in fp32).  The baseline F0 of frame t: K_0 for
@@ -245,6 +265,10 @@ int pmd_pixel_hist_select(pmd_ctx* ctx, long D, uint32_t* hist, int* rank, uint3
 int pmd_bin_means(pmd_ctx* ctx, const void* Y, int elem, long ldy, int n, long N, long f0, int bin, float* K, long ldk);
 long pmd_sliding_extremum_work_floats(long n, long Nc);
 int pmd_sliding_extremum(pmd_ctx* ctx, const float* X, long ldx, long n, long N, long half, int is_max, float* out,
+                         long ldo, float* work, long work_floats);
+#define PMD_SLIDING_QUANTILE_SLICE 128
+long pmd_sliding_quantile_work_floats(long n, long Nc, long half);
+int pmd_sliding_quantile(pmd_ctx* ctx, const float* X, long ldx, long n, long N, long half, long rank, float* out,
                          long ldo, float* work, long work_floats);
 int pmd_baseline_apply(pmd_ctx* ctx, const void* X, int elem, long ldx, int n, long N, long f0, long T, int bin,
                        const float* K, long ldk, int mode, float min_baseline, float* out, long ldo);

@@ -51,6 +51,8 @@ SIGNATURES = {
     "pmd_bin_means": (c_i, [c_p, c_p, c_i, c_l, c_i, c_l, c_l, c_i, c_p, c_l]),
     "pmd_sliding_extremum_work_floats": (c_l, [c_l, c_l]),
     "pmd_sliding_extremum": (c_i, [c_p, c_p, c_l, c_l, c_l, c_l, c_i, c_p, c_l, c_p, c_l]),
+    "pmd_sliding_quantile_work_floats": (c_l, [c_l, c_l, c_l]),
+    "pmd_sliding_quantile": (c_i, [c_p, c_p, c_l, c_l, c_l, c_l, c_l, c_p, c_l, c_p, c_l]),
     "pmd_baseline_apply": (c_i, [c_p, c_p, c_i, c_l, c_i, c_l, c_l, c_l, c_i, c_p, c_l, c_i, c_f, c_p, c_l]),
     "pmd_hals_sweep": (c_i, [c_p, c_p, c_l, c_p, c_l, c_i, c_l, c_p, c_p, c_p, c_p, c_p]),
     "pmd_hals_pixels": (c_i, [c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_p, c_l, c_p]),

@@ -12,7 +12,9 @@ filter is neither a running reduction nor linear in the movie, so every pixel of
    the batch in place, in their own dtype.
 2. the sliding minimum over ``2 h + 1`` knots, and for "maximin" (the morphological opening, as in Suite2p) the sliding
    maximum of the result (``pmd_sliding_extremum``, work per knot independent of h), in ranges of pixel columns so that
-   the workspace stays within WORK_BYTES.
+   the workspace stays within WORK_BYTES.  ``method="percentile"`` takes instead the running low percentile of CaImAN's
+   detrend_df_f: the member of rank min(W - 1, floor(q W)) of the W = 2 h + 1 knots around each knot, the series'
+   ends replicated (``pmd_sliding_quantile``, exact on integer keys; work per knot grows as min(W, n_bins)).
 3. dff_movie only: a second pass rebuilds every block and writes it through ``pmd_baseline_apply``, which interpolates
    the baseline between the knots, into the sink.  The knots stay on the device between the passes.
 
@@ -30,11 +32,16 @@ from ._movie import _device_free_bytes
 from ._stream import BLOCK, batch_buffer_bytes, block_plan, block_walk, device_context, read_batches, source_info
 
 KINDS = ("denoised", "raw")
-METHODS = ("maximin", "minimum")
+METHODS = ("maximin", "minimum")      # the sliding extrema
+PERCENTILE = "percentile"             # the sliding order statistic
+ALL_METHODS = METHODS + (PERCENTILE,)
+DEFAULT_Q = 0.08             # CaImAN's detrend_df_f: the 8th percentile
 OUTPUTS = ("baseline", "detrended", "dff")
 MAX_BIN = 256                # PMD_BASELINE_MAX_BIN: a bin lies inside one reconstruction block
 MAX_FRAMES = 1 << 23         # PMD_BASELINE_MAX_FRAMES: frame numbers and bin centres (multiples of 1/2) are exact in fp32
 WORK_BYTES = 256 << 20       # the most workspace one pmd_sliding_extremum call gets
+QUANTILE_SLICE = 128         # PMD_SLIDING_QUANTILE_SLICE: the outputs one wave of pmd_sliding_quantile walks
+MAX_HALF = 1 << 30           # pmd_sliding_quantile: the counts of a window of 2 half + 1 members fit 32 bits
 
 
 # ---- host side: the knot grid, the filter plan, the interpolation (no device work) ----------------------------------
@@ -72,6 +79,18 @@ def interpolate(knots, centres, t):
     return np.where(exact.reshape(shape), ka, f).astype(np.float32)
 
 
+def percentile_rank(half, q):
+    """The 0-based rank min(W - 1, floor(q W)) of the q-quantile among the W = 2 half + 1 members of a window, in
+    float64: scipy.ndimage.percentile_filter's rule for the percentile 100 q."""
+    W = 2 * int(half) + 1
+    return min(W - 1, int(np.floor(np.float64(q) * np.float64(W))))
+
+
+def quantile_work_floats(n_bins, cols, half):
+    """pmd_sliding_quantile_work_floats: the state of a column lives in registers, there is no workspace."""
+    return 0
+
+
 def filter_plan(n_bins, N):
     """([(c0, c1), ...], work_floats): the ranges of pixel columns one pmd_sliding_extremum call takes each, multiples
     of 256 columns (of 4 when the series is very long) whose workspace of n_bins * round_up(columns, 4) floats stays
@@ -83,22 +102,27 @@ def filter_plan(n_bins, N):
     return [(c0, min(N, c0 + cols)) for c0 in range(0, N, cols)], n_bins * cols
 
 
-def knot_bytes(T, D, temporal_bin):
-    """Device bytes that grow with the movie's length: the knots, the filter's output and its workspace."""
+def knot_bytes(T, D, temporal_bin, method="maximin", half=0):
+    """Device bytes that grow with the movie's length: the knots, the filter's output and its workspace (that of the
+    sliding extrema, or for "percentile" that of pmd_sliding_quantile over the same column ranges: none)."""
     n_bins = -(-int(T) // int(temporal_bin))
-    return 2 * 4 * n_bins * int(D) + 4 * filter_plan(n_bins, D)[1]
+    ranges, work_floats = filter_plan(n_bins, D)
+    if method == PERCENTILE:
+        work_floats = max(quantile_work_floats(n_bins, c1 - c0, half) for c0, c1 in ranges)
+    return 2 * 4 * n_bins * int(D) + 4 * work_floats
 
 
 def baseline_device_bytes(*, T, D, temporal_bin, nb, esize, kind, n_cols, rank, n_entries, n_a, n_patches, host_source,
-                          n_batches, factors_on_device, host_dest=False):
+                          n_batches, factors_on_device, host_dest=False, method="maximin", half=0):
     """Device bytes rolling_baseline (and dff_movie: ``host_dest`` adds the output ring of a host destination) holds on
     a movie of T frames of D pixels read in batches of nb frames.  Unlike every other consumer of a decomposition this
     one grows with the movie's length, as T / temporal_bin: the knots are 4 D ceil(T / temporal_bin) bytes, the filter's
-    output as much again, and the filter's workspace up to the same, bounded by WORK_BYTES (knot_bytes).  On top of
-    them the batch buffers of a raw pass, or for the denoised movie the expander with one expanded block."""
+    output as much again, and the extremum filters' workspace up to the same, bounded by WORK_BYTES; the percentile
+    filter (``method``, ``half``) has none (knot_bytes).  On top of them the batch buffers of a raw pass, or for the
+    denoised movie the expander with one expanded block."""
     from .export import HOST_SLOTS
 
-    need = knot_bytes(T, D, temporal_bin)
+    need = knot_bytes(T, D, temporal_bin, method, half)
     if kind == "raw":
         need += batch_buffer_bytes(nb, D, esize, host_source, n_batches)
     else:
@@ -136,6 +160,28 @@ def _check_name(value, allowed, word):
     return value
 
 
+def _check_method(method, q):
+    """(method, q): the method's name against ALL_METHODS; q is a float in [0, 1] for "percentile" (None: DEFAULT_Q) and
+    None for the others."""
+    _check_name(method, ALL_METHODS, "method")
+    if method != PERCENTILE:
+        if q is not None:
+            raise ValueError("q belongs to method 'percentile', the method is {!r}".format(method))
+        return method, None
+    if q is None:
+        return method, DEFAULT_Q
+    ok = isinstance(q, (int, float, np.integer, np.floating)) and not isinstance(q, (bool, np.bool_))
+    if not ok or not 0.0 <= float(q) <= 1.0:         # a NaN fails both comparisons
+        raise ValueError("q must be a number in [0, 1], got {!r}".format(q))
+    return method, float(q)
+
+
+def _check_half(half, method):
+    if method == PERCENTILE and half >= MAX_HALF:
+        raise ValueError("a window of {} knots is too long for method 'percentile'".format(2 * half + 1))
+    return half
+
+
 def _check_frames(T, what):
     if T == 0:
         raise ValueError("{} has no frames: there is no baseline".format(what))
@@ -146,12 +192,13 @@ def _check_frames(T, what):
 class Baseline:
     """Result of rolling_baseline: ``knots`` ((n_bins, d1, d2) float32, the baseline at the bin centres), ``centres``
     ((n_bins,) float64 frame positions), ``temporal_bin``, ``window_frames`` = (2 h + 1) temporal_bin, ``method``,
-    ``kind`` and ``n_frames``."""
+    ``kind``, ``n_frames`` and ``q`` (the quantile of method "percentile"; None for the extremum methods)."""
 
-    def __init__(self, knots, temporal_bin, window_frames, method, kind, n_frames):
+    def __init__(self, knots, temporal_bin, window_frames, method, kind, n_frames, *, q=None):
         self.knots = knots
         self.temporal_bin, self.window_frames = int(temporal_bin), int(window_frames)
         self.method, self.kind, self.n_frames = method, kind, int(n_frames)
+        self.q = q
         self.centres = bin_centres(self.n_frames, self.temporal_bin)
 
     def frames(self, t0=0, t1=None):
@@ -164,8 +211,9 @@ class Baseline:
         return interpolate(self.knots, self.centres, np.arange(t0, t1))
 
     def __repr__(self):
+        method = self.method if self.q is None else "{} q={:g}".format(self.method, self.q)
         return "Baseline({}; {} knots of {} frames; {} over {} frames)".format(
-            self.kind, len(self.centres), self.temporal_bin, self.method, self.window_frames)
+            self.kind, len(self.centres), self.temporal_bin, method, self.window_frames)
 
 
 def _check_baseline(b, shape, kind):
@@ -175,7 +223,9 @@ def _check_baseline(b, shape, kind):
     if b.kind != kind:
         raise ValueError("the baseline is that of the {} movie, kind is {!r}".format(b.kind, kind))
     _check_bin(b.temporal_bin)
-    _check_name(b.method, METHODS, "method")
+    if b.method == PERCENTILE and b.q is None:
+        raise ValueError("a percentile baseline must say its q")
+    _check_method(b.method, b.q)
     if b.n_frames != T:
         raise ValueError("the baseline covers {} frames, the decomposition {}".format(b.n_frames, T))
     want = (-(-T // b.temporal_bin), d1, d2)
@@ -191,15 +241,26 @@ def _offset(t, c0):
     return C.c_void_p(t.data_ptr() + 4 * int(c0))
 
 
-def _filter(ctx, K, half, method):
+def _filter(ctx, K, half, method, q=None):
     """The sliding minimum (and for "maximin" then the maximum) over ``2 half + 1`` rows of the (n_bins, N) device
-    tensor K, column range by column range; returns the tensor that holds the result (K or the second buffer)."""
+    tensor K, or for "percentile" the sliding member of rank percentile_rank(half, q) in one pass, column range by
+    column range; returns the tensor that holds the result (K or the second buffer)."""
     import torch
     from ._lib import ptr
 
     n_bins, N = (int(x) for x in K.shape)
     ranges, work_floats = filter_plan(n_bins, N)
     src, dst = K, torch.empty_like(K)
+    if method == PERCENTILE:
+        rank = percentile_rank(half, q)
+        query = ctx.lib.pmd_sliding_quantile_work_floats
+        work_floats = max(int(query(n_bins, c1 - c0, int(half))) for c0, c1 in ranges)
+        assert work_floats == max(quantile_work_floats(n_bins, c1 - c0, half) for c0, c1 in ranges)   # as check_fit saw
+        work = torch.empty(work_floats, dtype=torch.float32, device=K.device) if work_floats else None
+        for c0, c1 in ranges:
+            ctx.call("pmd_sliding_quantile", _offset(src, c0), N, n_bins, c1 - c0, int(half), rank, _offset(dst, c0), N,
+                     ptr(work), work_floats)
+        return dst
     work = torch.empty(work_floats, dtype=torch.float32, device=K.device)
     for is_max in ((0, 1) if method == "maximin" else (0,)):
         for c0, c1 in ranges:
@@ -245,7 +306,7 @@ class _Passes:
         read_batches(self.ctx, self.movie if self.ex is None else None, [(b0, b1) for b0, b1, _ in self.plan], self.fbs,
                      self.nw, consume)
 
-    def knots(self, half, method):
+    def knots(self, half, method, q=None):
         """Pass 1 and the filters: the (n_bins, D) device tensor of the filtered knots."""
         import torch
         from ._lib import ptr
@@ -253,7 +314,7 @@ class _Passes:
         ctx, D = self.ctx, self.D
         K = torch.empty((-(-self.T // self.bin), D), dtype=torch.float32, device=ctx.device)
         self.run(lambda X, elem, c0, m: ctx.call("pmd_bin_means", X, int(elem), D, int(m), D, int(c0), self.bin, ptr(K), D))
-        return _filter(ctx, K, half, method)
+        return _filter(ctx, K, half, method, q)
 
     def apply(self, K, mode, min_baseline, sink):
         """Pass 2: every block through pmd_baseline_apply into the sink."""
@@ -271,7 +332,7 @@ class _Passes:
         self.run(each)
 
 
-def _check_common(pmd, movie, kind, temporal_bin, method):
+def _check_common(pmd, movie, kind, temporal_bin, method, q):
     from .pmdarray import PMDArray
 
     if not isinstance(pmd, PMDArray):
@@ -279,16 +340,16 @@ def _check_common(pmd, movie, kind, temporal_bin, method):
     if kind == "residual":
         raise ValueError("the residual's baseline is about 0 and dF/F of it means nothing; choose from {}".format(KINDS))
     _check_name(kind, KINDS, "kind")
-    _check_name(method, METHODS, "method")
+    _, q = _check_method(method, q)
     b = _check_bin(temporal_bin)
     if kind == "raw" and movie is None:
         raise ValueError("kind 'raw' needs the movie: pass movie=")
     on_device, esize = source_info(movie, pmd.shape) if kind == "raw" else (False, 4)
     _check_frames(int(pmd.shape[0]), "the decomposition")
-    return b, on_device, esize
+    return b, on_device, esize, q
 
 
-def _fit(what, pmd, kind, b, esize, on_device, frame_batch_size, dv_active, host_dest, free):
+def _fit(what, pmd, kind, b, esize, on_device, frame_batch_size, dv_active, host_dest, free, method, half):
     """check_fit before anything is allocated on the device."""
     T, d1, d2 = (int(x) for x in pmd.shape)
     n_cols, rank = (int(x) for x in pmd.r.shape)
@@ -302,12 +363,12 @@ def _fit(what, pmd, kind, b, esize, on_device, frame_batch_size, dv_active, host
     need = baseline_device_bytes(T=T, D=d1 * d2, temporal_bin=b, nb=plan[0][1] - plan[0][0], esize=esize, kind=kind,
                                  n_cols=n_cols, rank=rank, n_entries=n_ent, n_a=n_a, n_patches=n_patches,
                                  host_source=not on_device, n_batches=len(plan), factors_on_device=dv_active,
-                                 host_dest=host_dest)
+                                 host_dest=host_dest, method=method, half=half)
     check_fit(what, need, free)
 
 
 # ---- public entry points -------------------------------------------------------------------------------------------
-def rolling_baseline(pmd, movie=None, *, kind="denoised", window, temporal_bin=16, method="maximin",
+def rolling_baseline(pmd, movie=None, *, kind="denoised", window, temporal_bin=16, method="maximin", q=None,
                      frame_batch_size=10000, num_workers=0, device=None, ctx=None):
     """The rolling baseline of every pixel of the ``kind`` movie ("denoised": ``mean_img + var_img * (U R diag(s) Vt)``,
     which reads no movie; "raw": ``movie``, read once; the residual has no baseline to speak of and is refused), as a
@@ -321,27 +382,37 @@ def rolling_baseline(pmd, movie=None, *, kind="denoised", window, temporal_bin=1
     in frames; h is the smallest integer with (2 h + 1) temporal_bin >= window, and the result says what was used in
     ``window_frames``.  NaN bin means are ignored unless a whole window is NaN.
 
+    ``method`` "percentile" is the running low percentile of CaImAN's detrend_df_f instead: of the W = 2 h + 1 bin means
+    around each bin, ordered, the one at the 0-based rank min(W - 1, floor(q W)) (scipy.ndimage.percentile_filter's
+    rule for the percentile 100 q), with ``q`` a float in [0, 1], None meaning 0.08; ``q`` with another method is an
+    error.  Here the series' ends are replicated, not cut (scipy's mode "nearest"), so every window has W members;
+    the order is that of quantile_images, -0 before +0 and every NaN last, so a NaN comes out only where NaNs reach
+    down to the rank.  It is exact and bit-reproducible, and unlike an extremum not biased by the knots' noise; its work
+    per pixel grows as n_bins min(W, n_bins) where the extrema take n_bins, so temporal_bin=1 with a long window (that
+    is CaImAN's filter on the frames themselves) is expensive.  The result carries ``q``.
+
     Sources, batching and residency are those of summary_images; the knots have the same bits for every
     frame_batch_size, source and residency.  Device memory grows with the movie's length: 8 D ceil(T / temporal_bin)
-    bytes of knots and filter output plus a workspace of up to 256 MB (baseline_device_bytes); a plan that does not fit
-    raises ValueError and says to raise temporal_bin.  Argument errors are raised before any device work."""
+    bytes of knots and filter output plus, for the extrema, a workspace of up to 256 MB (baseline_device_bytes); a plan
+    that does not fit raises ValueError and says to raise temporal_bin.  Argument errors are raised before any device
+    work."""
     window = _check_window(window)
-    b, on_device, esize = _check_common(pmd, movie, kind, temporal_bin, method)
-    half = half_window(window, b)
+    b, on_device, esize, q = _check_common(pmd, movie, kind, temporal_bin, method, q)
+    half = _check_half(half_window(window, b), method)
     T, d1, d2 = (int(x) for x in pmd.shape)
     with device_context(pmd, device, ctx) as (ctx, dv):
         _fit("rolling_baseline", pmd, kind, b, esize, on_device, frame_batch_size, dv is not None, False,
-             _device_free_bytes(ctx.device))
+             _device_free_bytes(ctx.device), method, half)
         ps = _Passes(ctx, pmd, dv, movie, kind, b, frame_batch_size, num_workers)
-        K = ps.knots(half, method)
+        K = ps.knots(half, method, q)
         ctx.sync()
         knots = K.cpu().numpy().reshape(-1, d1, d2)
-    return Baseline(knots, b, (2 * half + 1) * b, method, kind, T)
+    return Baseline(knots, b, (2 * half + 1) * b, method, kind, T, q=q)
 
 
 def dff_movie(pmd, out, movie=None, *, kind="denoised", output="dff", baseline=None, window=None, temporal_bin=16,
-              method="maximin", min_baseline=0.0, frame_batch_size=10000, num_workers=0, bigtiff=None, device=None,
-              ctx=None):
+              method="maximin", q=None, min_baseline=0.0, frame_batch_size=10000, num_workers=0, bigtiff=None,
+              device=None, ctx=None):
     """Write the ``kind`` movie ("denoised" or "raw") relative to its rolling baseline F0 to ``out`` (the destinations of
     export_movie: a .tif / .tiff or .npy path, a host array, a contiguous device tensor), (T, d1, d2) float32:
     ``output`` "dff" is (x - F0) / F0, 0 where F0 > ``min_baseline`` does not hold (a NaN F0 included); "detrended" is
@@ -349,8 +420,9 @@ def dff_movie(pmd, out, movie=None, *, kind="denoised", output="dff", baseline=N
 
     F0 at a frame is interpolated linearly (fp32, every operation rounded on its own) between the knots of
     rolling_baseline at the bin centres, and constant before the first and after the last centre.  The knots are built
-    with ``window``, ``temporal_bin`` and ``method`` as in rolling_baseline, or taken from ``baseline``, a Baseline of
-    this decomposition and kind (then ``window`` must be None; its bin and method apply).  They stay on the device
+    with ``window``, ``temporal_bin``, ``method`` and ``q`` as in rolling_baseline, or taken from ``baseline``, a Baseline
+    of this decomposition and kind, of any method (then ``window`` and ``q`` must be None; its bin and method apply and
+    no filter runs).  They stay on the device
     while a second pass rebuilds every block and writes it out: the raw movie is read twice, the denoised movie never.
     Every output bit is the same for every frame_batch_size, source, destination and residency.  Argument errors are
     raised before any device work and before a file is created; a file this call created is removed when it fails
@@ -373,11 +445,16 @@ def dff_movie(pmd, out, movie=None, *, kind="denoised", output="dff", baseline=N
     if baseline is not None and not isinstance(baseline, Baseline):
         raise TypeError("baseline must be a localmd_amd.Baseline, got {}".format(type(baseline).__name__))
     if baseline is not None:
-        temporal_bin, method = baseline.temporal_bin, baseline.method
-    b, on_device, esize = _check_common(pmd, movie, kind, temporal_bin, method)
+        if q is not None:
+            raise ValueError("pass q= with window=, not with baseline=: the baseline has its own")
+        temporal_bin, method, q = baseline.temporal_bin, baseline.method, baseline.q
+    b, on_device, esize, q = _check_common(pmd, movie, kind, temporal_bin, method, q)
     T, d1, d2 = (int(x) for x in pmd.shape)
     if baseline is not None:
         _check_baseline(baseline, (T, d1, d2), kind)
+        half = 0                             # no filter runs
+    else:
+        half = _check_half(half_window(window, b), method)
     dv = getattr(pmd, "_dev", None)
     dev_index = dv["ctx"].device_index if dv is not None else (ctx.device_index if ctx is not None else
                                                                (0 if device is None else int(device)))
@@ -386,12 +463,12 @@ def dff_movie(pmd, out, movie=None, *, kind="denoised", output="dff", baseline=N
 
     with device_context(pmd, dev_index, ctx) as (ctx, dv):
         _fit("dff_movie", pmd, kind, b, esize, on_device, frame_batch_size, dv is not None, dest.kind != "device",
-             _device_free_bytes(ctx.device))
+             _device_free_bytes(ctx.device), method, half)
         dest.open()
         try:
             ps = _Passes(ctx, pmd, dv, movie, kind, b, frame_batch_size, num_workers)
             if baseline is None:
-                K = ps.knots(half_window(window, b), method)
+                K = ps.knots(half, method, q)
             else:
                 import torch
 
@@ -415,18 +492,19 @@ def dff_movie(pmd, out, movie=None, *, kind="denoised", output="dff", baseline=N
         return dest.close()
 
 
-def trace_baseline(traces, *, window, temporal_bin=16, method="maximin", output="dff", min_baseline=0.0, device=None,
-                   ctx=None):
+def trace_baseline(traces, *, window, temporal_bin=16, method="maximin", q=None, output="dff", min_baseline=0.0,
+                   device=None, ctx=None):
     """The rows of ``traces`` ((K, T), for instance those of extract_traces) relative to their rolling baseline:
     (K, T) float32, ``output`` "dff", "detrended" or "baseline" as in dff_movie, the baseline built with ``window``,
-    ``temporal_bin`` and ``method`` as in rolling_baseline.  The three kernels of dff_movie run on the transposed
+    ``temporal_bin``, ``method`` and ``q`` as in rolling_baseline (``temporal_bin=1, method="percentile"`` is CaImAN's
+    percentile filter on the frames themselves).  The three kernels of dff_movie run on the transposed
     (T, K) matrix in 1024-frame blocks, so a trace gets the bits the same series gets as a pixel of a movie."""
     import torch
     from ._lib import ptr
 
     window = _check_window(window)
     b = _check_bin(temporal_bin)
-    _check_name(method, METHODS, "method")
+    _, q = _check_method(method, q)
     mode = OUTPUTS.index(_check_name(output, OUTPUTS, "output"))
     min_baseline = float(min_baseline)
     a = np.asarray(traces)
@@ -434,14 +512,14 @@ def trace_baseline(traces, *, window, temporal_bin=16, method="maximin", output=
         raise ValueError("traces must be a (K, T) array of numbers with K >= 1")
     Kn, T = (int(x) for x in a.shape)
     _check_frames(T, "a trace")
-    half = half_window(window, b)
+    half = _check_half(half_window(window, b), method)
     with device_context(None, device, ctx) as (ctx, _):
         X = torch.from_numpy(np.ascontiguousarray(a.T, dtype=np.float32)).to(ctx.device)
         knots = torch.empty((-(-T // b), Kn), dtype=torch.float32, device=ctx.device)
         blocks = [(c0, min(T, c0 + BLOCK) - c0) for c0 in range(0, T, BLOCK)]
         for c0, m in blocks:
             ctx.call("pmd_bin_means", ptr(X[c0]), 0, Kn, m, Kn, c0, b, ptr(knots), Kn)
-        knots = _filter(ctx, knots, half, method)
+        knots = _filter(ctx, knots, half, method, q)
         out = torch.empty((T, Kn), dtype=torch.float32, device=ctx.device)
         for c0, m in blocks:
             ctx.call("pmd_baseline_apply", ptr(X[c0]), 0, Kn, m, Kn, c0, T, b, ptr(knots), Kn, mode, min_baseline,

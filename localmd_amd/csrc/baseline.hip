@@ -1,6 +1,6 @@
 // Rolling-baseline dF/F (localmd_amd/baseline.py): the time series of every pixel is reduced to knots (the means of bins
 // of `bin` frames, pmd_bin_means), the knots go through a sliding minimum and / or maximum along time
-// (pmd_sliding_extremum), and every frame is compared with the baseline interpolated between the knots
+// (pmd_sliding_extremum) or a sliding order statistic (pmd_sliding_quantile), and every frame is compared with the baseline interpolated between the knots
 // (pmd_baseline_apply).  All three stream frames-first matrices: lane l of a wave owns V consecutive pixels, V = 4 (fp32)
 // or 8 (16-bit), one 16-byte load per frame (a row that is not 16-byte aligned, or a lane whose run crosses N, moves them
 // one by one on clamped indices; the arithmetic is the same, so are the bits), and walks time inside the thread, BL_U
@@ -19,6 +19,16 @@
 //                     padding that never wins: the scans start from NaN, which fminf / fmaxf drop against any value (as
 //                     they drop +inf / -inf padding against any value but NaN), so a window is NaN only when every frame
 //                     it really holds is.
+// quantile_kernel     the sliding order statistic, on the integer keys of quantile.hip.  A wave takes a slice of BL_QSLICE
+//                     consecutive outputs.  The first is selected by bisection on the 32 key bits, one counting scan
+//                     of the window per bit.  From then on each column keeps its answer key a with cl = #{key < a} and
+//                     ce = #{key == a}; the next window loses one member and gains one, two compares each update cl
+//                     and ce, and the answer stays while cl <= rank < cl + ce.  Otherwise it moves to the neighbouring
+//                     distinct key, which one scan of the window finds together with its count.  The scan runs when
+//                     any lane of the wave needs it, which with 256 columns per wave is nearly every step: the work
+//                     is one scan per output plus 33 per slice.  A scan reads the rows the window really holds once
+//                     and counts the replicated first and last row with a multiplicity, so it is min(W, n) rows
+//                     whatever half is.  Integer work only: no workspace, and nothing to round.
 // apply_kernel        a wave takes a slice of 32 frames.  Per frame the bin j whose centre is the last at or before the
 //                     frame and the weight w are the same in every lane; the knot rows j and j + 1 stay in registers
 //                     until j moves on.
@@ -31,6 +41,7 @@ constexpr int BL_WAVES = 4;
 constexpr int BL_U = 8;               // frames whose loads are in flight per lane
 constexpr int BL_APPLY_SLICE = 32;    // frames per wave of apply_kernel
 constexpr int BL_MIN_SLICE = 64;      // frames per wave of bin_means_kernel, at least
+constexpr int BL_QSLICE = PMD_SLIDING_QUANTILE_SLICE;   // outputs per wave of quantile_kernel
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -177,6 +188,141 @@ __global__ __launch_bounds__(64 * BL_WAVES) void extremum_kernel(const float* __
 #pragma unroll
     for (int t = 0; t < V; ++t) b[t] = bl_ext<MAX>(b[t], acc[t]);
     bl_store<V>(out + (j0 + r) * ldo, c, N, ov, b);
+  }
+}
+
+// the order-preserving key of pmd_pixel_hist_accumulate: -0 before +0, every NaN last
+__device__ __forceinline__ unsigned bl_key(float v) {
+  const unsigned b = __float_as_uint(v);
+  return v != v ? 0xFFFFFFFFu : b ^ ((unsigned)((int)b >> 31) | 0x80000000u);
+}
+
+__device__ __forceinline__ float bl_unkey(unsigned k) {
+  return __uint_as_float(k & 0x80000000u ? k ^ 0x80000000u : ~k);
+}
+
+// The members of the window of output j, as keys: the rows max(0, j - half) .. min(n - 1, j + half) once each, then the
+// copies that replicate the edges, row 0 another max(0, half - j) times and row n - 1 another max(0, j + half - (n - 1))
+// times, as one visit with a multiplicity each.  visit(k, m): the V keys of a row, counted m times.
+template <int V, typename F>
+__device__ __forceinline__ void bl_window(const float* __restrict__ X, long ldx, long n, long half, long j, long c,
+                                          const long* cj, bool xv, F&& visit) {
+  const long lo = max(j - half, 0L), hi = min(j + half, n - 1);
+  float v[V];
+  unsigned k[V];
+#pragma unroll 4                       // 8 rows in flight measured slower: 78 ms against 53 ms on 625 x 262 144 knots
+  for (long r = lo; r <= hi; ++r) {
+    bl_load_f32<V>(X + r * ldx, c, cj, xv, v);
+#pragma unroll
+    for (int t = 0; t < V; ++t) k[t] = bl_key(v[t]);
+    visit(k, 1u);
+  }
+  const unsigned m0 = (unsigned)max(half - j, 0L), m1 = (unsigned)max(j + half - (n - 1), 0L);   // half < 2^30
+  if (m0) {
+    bl_load_f32<V>(X, c, cj, xv, v);
+#pragma unroll
+    for (int t = 0; t < V; ++t) k[t] = bl_key(v[t]);
+    visit(k, m0);
+  }
+  if (m1) {
+    bl_load_f32<V>(X + (n - 1) * ldx, c, cj, xv, v);
+#pragma unroll
+    for (int t = 0; t < V; ++t) k[t] = bl_key(v[t]);
+    visit(k, m1);
+  }
+}
+
+__global__ __launch_bounds__(64 * BL_WAVES) void quantile_kernel(const float* __restrict__ X, long ldx, long n, long N,
+                                                                  long half, unsigned rank, float* __restrict__ out,
+                                                                  long ldo, int vec_x, int vec_out) {
+  constexpr int V = 4;
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const long c = ((long)blockIdx.y * 64 + lane) * V;
+  const long j0 = ((long)blockIdx.x * BL_WAVES + w) * BL_QSLICE;   // first output of this wave's slice
+  if (j0 >= n || c >= N) return;
+  const long j1 = min(n, j0 + BL_QSLICE);
+  const bool full = c + V <= N;
+  const bool xv = vec_x && full, ov = vec_out && full;
+  long cj[V];
+#pragma unroll
+  for (int t = 0; t < V; ++t) cj[t] = c + t < N ? c + t : N - 1;
+  // per column: the answer key a of the current window, cl = #{key < a} and ce = #{key == a} of its members
+  unsigned a[V], cl[V], ce[V];
+  float v[V], o[V];
+
+  // the first output: the smallest a with #{key <= a} > rank, bit by bit from the top
+#pragma unroll
+  for (int t = 0; t < V; ++t) a[t] = 0u;
+  for (int b = 31; b >= 0; --b) {
+    unsigned probe[V], cnt[V];
+#pragma unroll
+    for (int t = 0; t < V; ++t) probe[t] = a[t] | ((1u << b) - 1u), cnt[t] = 0u;
+    bl_window<V>(X, ldx, n, half, j0, c, cj, xv, [&](const unsigned* k, unsigned m) {
+#pragma unroll
+      for (int t = 0; t < V; ++t) cnt[t] += k[t] <= probe[t] ? m : 0u;
+    });
+#pragma unroll
+    for (int t = 0; t < V; ++t)
+      if (cnt[t] <= rank) a[t] |= 1u << b;
+  }
+#pragma unroll
+  for (int t = 0; t < V; ++t) cl[t] = ce[t] = 0u;
+  bl_window<V>(X, ldx, n, half, j0, c, cj, xv, [&](const unsigned* k, unsigned m) {
+#pragma unroll
+    for (int t = 0; t < V; ++t) cl[t] += k[t] < a[t] ? m : 0u, ce[t] += k[t] == a[t] ? m : 0u;
+  });
+#pragma unroll
+  for (int t = 0; t < V; ++t) o[t] = bl_unkey(a[t]);
+  bl_store<V>(out + j0 * ldo, c, N, ov, o);
+
+  for (long j = j0 + 1; j < j1; ++j) {
+    // the window loses the member at j - 1 - half and gains the one at j + half, both clamped
+    unsigned ko[V], ki[V];
+    bl_load_f32<V>(X + min(max(j - 1 - half, 0L), n - 1) * ldx, c, cj, xv, v);
+#pragma unroll
+    for (int t = 0; t < V; ++t) ko[t] = bl_key(v[t]);
+    bl_load_f32<V>(X + min(j + half, n - 1) * ldx, c, cj, xv, v);
+#pragma unroll
+    for (int t = 0; t < V; ++t) ki[t] = bl_key(v[t]);
+    bool stale = false;
+#pragma unroll
+    for (int t = 0; t < V; ++t) {
+      cl[t] += (ki[t] < a[t] ? 1u : 0u) - (ko[t] < a[t] ? 1u : 0u);
+      ce[t] += (ki[t] == a[t] ? 1u : 0u) - (ko[t] == a[t] ? 1u : 0u);
+      stale |= rank < cl[t] || rank - cl[t] >= ce[t];
+    }
+    if (__any(stale)) {                // the same in every lane of the wave
+      // the neighbours of a among the members: the largest key below with its count, the smallest above with its count
+      unsigned lo[V], nlo[V], hi[V], nhi[V];
+#pragma unroll
+      for (int t = 0; t < V; ++t) lo[t] = 0u, hi[t] = 0xFFFFFFFFu, nlo[t] = nhi[t] = 0u;
+      bl_window<V>(X, ldx, n, half, j, c, cj, xv, [&](const unsigned* k, unsigned m) {
+#pragma unroll
+        for (int t = 0; t < V; ++t) {
+          if (k[t] < a[t]) {
+            nlo[t] = k[t] > lo[t] ? m : (k[t] == lo[t] ? nlo[t] + m : nlo[t]);
+            lo[t] = k[t] > lo[t] ? k[t] : lo[t];
+          } else if (k[t] > a[t]) {
+            nhi[t] = k[t] < hi[t] ? m : (k[t] == hi[t] ? nhi[t] + m : nhi[t]);
+            hi[t] = k[t] < hi[t] ? k[t] : hi[t];
+          }
+        }
+      });
+      // one member was replaced, so the answer moves by one distinct value: down with cl == rank + 1, or up with
+      // cl + ce == rank
+#pragma unroll
+      for (int t = 0; t < V; ++t) {
+        if (rank < cl[t]) {
+          a[t] = lo[t], ce[t] = nlo[t], cl[t] -= nlo[t];
+        } else if (rank - cl[t] >= ce[t]) {
+          cl[t] += ce[t], a[t] = hi[t], ce[t] = nhi[t];
+        }
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < V; ++t) o[t] = bl_unkey(a[t]);
+    bl_store<V>(out + j * ldo, c, N, ov, o);
   }
 }
 
@@ -379,6 +525,39 @@ int pmd_sliding_extremum(pmd_ctx* ctx, const float* X, long ldx, long n, long N,
     hipLaunchKernelGGL(extremum_kernel<false>, grid, block, 0, ctx->stream, X, ldx, n, N, h, out, ldo, work, ldw, vec_x,
                        vec_out, vec_work);
   PMD_LAUNCH_CHECK(ctx, "extremum_kernel");
+  return PMD_OK;
+}
+
+long pmd_sliding_quantile_work_floats(long n, long Nc, long half) {
+  (void)n, (void)Nc, (void)half;       // the state of a column lives in registers
+  return 0;
+}
+
+int pmd_sliding_quantile(pmd_ctx* ctx, const float* X, long ldx, long n, long N, long half, long rank, float* out, long ldo,
+                         float* work, long work_floats) {
+  CTX_CHECK(ctx);
+  const char* what = "pmd_sliding_quantile";
+  if (n < 1 || N < 1 || ldx < N || ldo < N)
+    return pmd_fail(ctx, PMD_ERR_ARG, what, "bad scalar argument (n >= 1, N >= 1, ldx >= N, ldo >= N)");
+  if (n > 0x7fffffffL) return pmd_fail(ctx, PMD_ERR_ARG, what, "n >= 2^31");
+  if (half < 0 || half >= (1L << 30)) return pmd_fail(ctx, PMD_ERR_ARG, what, "half outside 0 .. 2^30 - 1");
+  if (rank < 0 || rank > 2 * half) return pmd_fail(ctx, PMD_ERR_ARG, what, "rank outside 0 .. 2 half");
+  if (!X || !out) return pmd_fail(ctx, PMD_ERR_ARG, what, "null pointer");
+  const long need = pmd_sliding_quantile_work_floats(n, N, half);
+  if (work_floats < need || (need > 0 && !work))
+    return pmd_fail(ctx, PMD_ERR_ARG, what, "workspace smaller than pmd_sliding_quantile_work_floats(n, N, half)");
+  const float *xe = X + (n - 1) * ldx + N, *oe = out + (n - 1) * ldo + N;
+  if ((uintptr_t)X < (uintptr_t)oe && (uintptr_t)out < (uintptr_t)xe)
+    return pmd_fail(ctx, PMD_ERR_ARG, what, "X and out overlap");
+  if ((N + 255) / 256 > 65535) return pmd_fail(ctx, PMD_ERR_ARG, what, "too many pixels in one call");
+  pmd_prof_scope prof__(ctx, "sliding_quantile");
+  const long slices = (n + BL_QSLICE - 1) / BL_QSLICE;
+  const dim3 grid((unsigned)((slices + BL_WAVES - 1) / BL_WAVES), (unsigned)((N + 255) / 256)), block(64 * BL_WAVES);
+  const int vec_x = (ldx * 4) % 16 == 0 && (uintptr_t)X % 16 == 0;
+  const int vec_out = (ldo * 4) % 16 == 0 && (uintptr_t)out % 16 == 0;
+  hipLaunchKernelGGL(quantile_kernel, grid, block, 0, ctx->stream, X, ldx, n, N, half, (unsigned)rank, out, ldo, vec_x,
+                     vec_out);
+  PMD_LAUNCH_CHECK(ctx, "quantile_kernel");
   return PMD_OK;
 }
 

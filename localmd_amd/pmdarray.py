@@ -174,14 +174,15 @@ class PMDArray:
 
     def baseline(self, movie=None, **kw):
         """The rolling baseline of every pixel of the denoised / raw movie at knots temporal_bin frames apart: bin
-        means through a sliding minimum (and maximum), computed on the GPU (baseline.rolling_baseline; same keywords)."""
+        means through a sliding minimum (and maximum), or with method="percentile" and q through a sliding percentile,
+        computed on the GPU (baseline.rolling_baseline; same keywords)."""
         from .baseline import rolling_baseline
 
         return rolling_baseline(self, movie, **kw)
 
     def dff(self, out, movie=None, **kw):
-        """The denoised / raw movie relative to its rolling baseline, (x - F0) / F0, x - F0 or F0, streamed to ``out``
-        (baseline.dff_movie; same keywords)."""
+        """The denoised / raw movie relative to its rolling baseline (method "maximin", "minimum" or "percentile" with
+        q), (x - F0) / F0, x - F0 or F0, streamed to ``out`` (baseline.dff_movie; same keywords)."""
         from .baseline import dff_movie
 
         return dff_movie(self, out, movie, **kw)
