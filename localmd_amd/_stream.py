@@ -1,13 +1,14 @@
 """
 One pass over a movie against a stored decomposition: what project_frames / project_movie, make_pmd_diagnostic_images,
 export_movie, extract_traces, regressor_maps, summary_images, quantile_images and the rolling baseline (baseline.py)
-share.  The device context of a
-PMDArray, how a source is read (host sources through the pinned staging ring of the streamed decomposition, device
-tensors sliced in place), the 1024-frame reconstruction blocks, the walk over the blocks of a batch and the Vt columns
-of one, the uploaded statistics and R s, the host ring that results leave the device through, and the argument and
-device-memory checks the callers have in common.  Rebuilding a block of the denoised or residual movie from these is
-_expand's.  The movie sources, the frame-batch plan and the element types are _movie.py's, the layer below this one and
-below the decomposition driver.  No helper knows its caller.
+share.  The device context of a PMDArray, how a source is read (host sources through the pinned staging ring of the
+streamed decomposition, device tensors sliced in place), the 1024-frame reconstruction blocks, the walk over the
+blocks of a batch and the Vt columns of one, the uploaded statistics and R s, the host ring that results leave the
+device through, and the argument and device-memory checks the callers have in common.  Rebuilding a block of the
+denoised or residual movie from these is _expand's; where a pass that writes a movie puts its frames (destinations,
+sinks, and the scaffold that opens, finishes and aborts them, movie_pass) is _sink's, the module beside this one.  The
+movie sources, the frame-batch plan and the element types are _movie.py's, the layer below this one and below the
+decomposition driver.  No helper knows its caller.
 """
 import contextlib
 
@@ -153,6 +154,21 @@ def read_batches(ctx, movie, batches, frame_batch_size, num_workers, consume):
     else:
         src = _StreamedMovie(ctx, movie, frame_batch_size, num_workers=num_workers)
         src.run_pass(lambda batch, b0, n: consume(batch, src.elem, b0, n))
+
+
+def each_block(ctx, movie, plan, D, frame_batch_size, num_workers):
+    """blocks(each) for _sink.movie_pass: reads ``movie`` once along ``plan`` (read_batches; None: no movie is read) and
+    calls each(c0, m, yp, elem) for every reconstruction block (block_walk), in frame order."""
+    walk = block_walk(plan, D)
+
+    def blocks(each):
+        def consume(batch, elem, b0, n):
+            for c0, m, yp in walk(batch, b0):
+                each(c0, m, yp, elem)
+
+        read_batches(ctx, movie, [(b0, b1) for b0, b1, _ in plan], frame_batch_size, num_workers, consume)
+
+    return blocks
 
 
 class VtBlocks:

@@ -16,19 +16,20 @@ filter is neither a running reduction nor linear in the movie, so every pixel of
    detrend_df_f: the member of rank min(W - 1, floor(q W)) of the W = 2 h + 1 knots around each knot, the series'
    ends replicated (``pmd_sliding_quantile``, exact on integer keys; work per knot grows as min(W, n_bins)).
 3. dff_movie only: a second pass rebuilds every block and writes it through ``pmd_baseline_apply``, which interpolates
-   the baseline between the knots, into the sink.  The knots stay on the device between the passes.
+   the baseline between the knots, into the destination (_sink.movie_pass opens it, gives every block its address and
+   orders finish, abort and close; the file is created once the knots stand).  The knots stay on the device between the
+   passes.
 
 The bins divide the 1024-frame reconstruction block, so a bin never straddles a block and every output bit is the same
 for every frame_batch_size, source and residency.  This is the one consumer whose device memory grows with the movie's
 length T: the knots and the filter's output are ``4 D ceil(T / temporal_bin)`` bytes each.  Raise temporal_bin when they
 do not fit.
 """
-import itertools
-
 import numpy as np
 
 from ._expand import Expander, expander_bytes, panel_code
 from ._movie import _device_free_bytes
+from ._sink import HOST_SLOTS, _destination, check_bigtiff, device_index, movie_pass
 from ._stream import BLOCK, batch_buffer_bytes, block_plan, block_walk, device_context, read_batches, source_info
 
 KINDS = ("denoised", "raw")
@@ -120,8 +121,6 @@ def baseline_device_bytes(*, T, D, temporal_bin, nb, esize, kind, n_cols, rank, 
     output as much again, and the extremum filters' workspace up to the same, bounded by WORK_BYTES; the percentile
     filter (``method``, ``half``) has none (knot_bytes).  On top of them the batch buffers of a raw pass, or for the
     denoised movie the expander with one expanded block."""
-    from .export import HOST_SLOTS
-
     need = knot_bytes(T, D, temporal_bin, method, half)
     if kind == "raw":
         need += batch_buffer_bytes(nb, D, esize, host_source, n_batches)
@@ -316,20 +315,18 @@ class _Passes:
         self.run(lambda X, elem, c0, m: ctx.call("pmd_bin_means", X, int(elem), D, int(m), D, int(c0), self.bin, ptr(K), D))
         return _filter(ctx, K, half, method, q)
 
-    def apply(self, K, mode, min_baseline, sink):
-        """Pass 2: every block through pmd_baseline_apply into the sink."""
-        import ctypes as C
+    def apply(self, K, mode, min_baseline, dest, frame_shape):
+        """Pass 2: every block through pmd_baseline_apply into the destination (movie_pass); what dest.close() returns."""
         from ._lib import ptr
 
-        ctx, D, count = self.ctx, self.D, itertools.count()
+        ctx, D = self.ctx, self.D
 
-        def each(X, elem, c0, m):
-            k = next(count)
+        def write(c0, m, X, elem, out):
             ctx.call("pmd_baseline_apply", X, int(elem), D, int(m), D, int(c0), self.T, self.bin, ptr(K), D, mode,
-                     float(min_baseline), C.c_void_p(sink.dst(k, c0)), D)
-            sink.done(k, c0, m)
+                     float(min_baseline), out, D)
 
-        self.run(each)
+        return movie_pass(ctx, dest, frame_shape, np.dtype(np.float32), min(self.T, BLOCK),
+                          lambda each: self.run(lambda X, elem, c0, m: each(c0, m, X, elem)), write)
 
 
 def _check_common(pmd, movie, kind, temporal_bin, method, q):
@@ -427,8 +424,6 @@ def dff_movie(pmd, out, movie=None, *, kind="denoised", output="dff", baseline=N
     Every output bit is the same for every frame_batch_size, source, destination and residency.  Argument errors are
     raised before any device work and before a file is created; a file this call created is removed when it fails
     midway.  Device memory grows with the movie's length as in rolling_baseline."""
-    from .export import _destination, _DeviceSink, _HostSink
-
     _check_name(output, OUTPUTS, "output")
     if baseline is None:
         if window is None:
@@ -436,8 +431,7 @@ def dff_movie(pmd, out, movie=None, *, kind="denoised", output="dff", baseline=N
         window = _check_window(window)
     elif window is not None:
         raise ValueError("pass window= or baseline=, not both")
-    if bigtiff is not None and not isinstance(bigtiff, bool):
-        raise ValueError("bigtiff must be None, True or False")
+    check_bigtiff(bigtiff)
     try:
         min_baseline = float(min_baseline)
     except (TypeError, ValueError):
@@ -455,41 +449,21 @@ def dff_movie(pmd, out, movie=None, *, kind="denoised", output="dff", baseline=N
         half = 0                             # no filter runs
     else:
         half = _check_half(half_window(window, b), method)
-    dv = getattr(pmd, "_dev", None)
-    dev_index = dv["ctx"].device_index if dv is not None else (ctx.device_index if ctx is not None else
-                                                               (0 if device is None else int(device)))
+    dev_index = device_index(pmd, device, ctx)
     dest = _destination(out, (T, d1, d2), np.dtype(np.float32), bigtiff, dev_index)
     mode = OUTPUTS.index(output)
 
     with device_context(pmd, dev_index, ctx) as (ctx, dv):
         _fit("dff_movie", pmd, kind, b, esize, on_device, frame_batch_size, dv is not None, dest.kind != "device",
              _device_free_bytes(ctx.device), method, half)
-        dest.open()
-        try:
-            ps = _Passes(ctx, pmd, dv, movie, kind, b, frame_batch_size, num_workers)
-            if baseline is None:
-                K = ps.knots(half, method, q)
-            else:
-                import torch
+        ps = _Passes(ctx, pmd, dv, movie, kind, b, frame_batch_size, num_workers)
+        if baseline is None:
+            K = ps.knots(half, method, q)
+        else:
+            import torch
 
-                K = torch.from_numpy(np.ascontiguousarray(baseline.knots).reshape(-1, d1 * d2)).to(ctx.device)
-            if dest.kind == "device":
-                sink = _DeviceSink(dest.target, 4 * d1 * d2)
-            else:
-                sink = _HostSink(ctx, dest, 4 * d1 * d2, (d1, d2), np.dtype(np.float32), min(T, BLOCK))
-            try:
-                ps.apply(K, mode, min_baseline, sink)
-                sink.finish()
-                ctx.sync()
-            except BaseException:
-                sink.abort()
-                raise
-        except BaseException:
-            dest.abort()
-            raise
-        finally:
-            dest.shutdown()
-        return dest.close()
+            K = torch.from_numpy(np.ascontiguousarray(baseline.knots).reshape(-1, d1 * d2)).to(ctx.device)
+        return ps.apply(K, mode, min_baseline, dest, (d1, d2))
 
 
 def trace_baseline(traces, *, window, temporal_bin=16, method="maximin", q=None, output="dff", min_baseline=0.0,

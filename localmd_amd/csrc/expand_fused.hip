@@ -32,20 +32,6 @@ constexpr int EX_ET = 4;     // int64 fields per entry: {a_off, p64, r, c_row0}
 template <typename E>
 __device__ __forceinline__ float ex_load(const E* p) { return (float)*p; }
 
-// value -> output element: fp32 as is; integers round half to even, saturate, NaN -> 0
-template <typename O>
-__device__ __forceinline__ O ex_convert(float v) {
-  if constexpr (sizeof(O) == 4) {
-    return v;
-  } else {
-    const float mn = std::is_signed<O>::value ? -32768.f : 0.f;
-    const float mx = std::is_signed<O>::value ? 32767.f : 65535.f;
-    if (v != v) return (O)0;
-    const float r = fminf(fmaxf(rintf(v), mn), mx);
-    return (O)(int)r;
-  }
-}
-
 template <typename E, typename O>
 __global__ __launch_bounds__(256) void group_expand_kernel(const float* __restrict__ C, long ldc, int n, long D, int d2,
                                                            const float* __restrict__ mean, const float* __restrict__ stdv,
@@ -122,7 +108,7 @@ __global__ __launch_bounds__(256) void group_expand_kernel(const float* __restri
     for (int p = 0; p < n_panels; ++p) {
       const int kind = (panels >> (2 * p)) & 3;
       const float v = kind == 0 ? y : (kind == 1 ? x : __fsub_rn(y, x));
-      o[(long)p * d2] = ex_convert<O>(v);
+      o[(long)p * d2] = pmd_quant<O>(v);
     }
   }
 }

@@ -26,8 +26,6 @@
 //                     row) are staged in LDS once, the column index and weight of a thread's pixel are loaded once for
 //                     all its rows, the row index and weight are uniform: per pixel there is the frame's four samples,
 //                     four 8-byte LDS reads and one store.
-#include <type_traits>
-
 #include "pmd_common.h"
 #include "../../include/pmd_hip.h"
 
@@ -162,20 +160,6 @@ __global__ __launch_bounds__(PW_THREADS) void patch_reduce_kernel(const float* _
   surf[e] = s;
 }
 
-// the conversion of pmd_shift_apply (register.hip): fp32 as is; 16-bit round half to even, saturate, NaN -> 0
-template <typename O>
-__device__ __forceinline__ O pw_quant(float v) {
-  if constexpr (sizeof(O) == 4) {
-    return v;
-  } else {
-    const float mn = std::is_signed<O>::value ? -32768.f : 0.f;
-    const float mx = std::is_signed<O>::value ? 32767.f : 65535.f;
-    if (v != v) return (O)0;
-    const float r = fminf(fmaxf(rintf(v), mn), mx);
-    return (O)(int)r;
-  }
-}
-
 // a coordinate: clamped to [-1, d], NaN -> -1, so that its floor is an int in [-1, d] whatever the field holds
 __device__ __forceinline__ float pw_coord(float base, float s, int d) {
 #pragma clang fp contract(off)
@@ -244,7 +228,7 @@ __global__ __launch_bounds__(PW_THREADS) void warp_kernel(const E* __restrict__ 
     const float ofy = 1.f - fy, ofx = 1.f - fx;
     const float w00 = ofy * ofx, w01 = ofy * fx, w10 = fy * ofx, w11 = fy * fx;
     const float top = w00 * a + w01 * b, bot = w10 * c + w11 * d;
-    out[f * ofs + (long)y * ors + x] = pw_quant<O>(top + bot);
+    out[f * ofs + (long)y * ors + x] = pmd_quant<O>(top + bot);
   }
 }
 
@@ -280,15 +264,6 @@ void launch_warp(pmd_ctx* ctx, const warp_args& a, const void* X, void* out, int
                      a.constant, a.fill, (O*)out + (long)n0 * a.ofs, a.ofs, a.ors);
 }
 
-template <typename E>
-void launch_warp_out(pmd_ctx* ctx, int out_elem, const warp_args& a, const void* X, void* out, int n0, int g) {
-  if (out_elem == PMD_ELEM_F32) launch_warp<E, float>(ctx, a, X, out, n0, g);
-  else if (out_elem == PMD_ELEM_U16) launch_warp<E, uint16_t>(ctx, a, X, out, n0, g);
-  else launch_warp<E, int16_t>(ctx, a, X, out, n0, g);
-}
-
-bool pw_bad_elem(int e) { return e != PMD_ELEM_F32 && e != PMD_ELEM_U16 && e != PMD_ELEM_I16; }
-
 bool pw_bad_geometry(int d1, int d2, int my, int mx, int ey, int ex, int ph, int pw, int gy, int gx) {
   if (my < 1 || my > PMD_SHIFT_MAX || mx < 1 || mx > PMD_SHIFT_MAX || ey < 1 || ey > PMD_PATCH_MAX_DEV || ex < 1 ||
       ex > PMD_PATCH_MAX_DEV || d1 < 1 || d2 < 1 || d1 > PMD_SHIFT_MAX_DIM || d2 > PMD_SHIFT_MAX_DIM)
@@ -323,8 +298,8 @@ int pmd_patch_correlate(pmd_ctx* ctx, const void* X, int elem, long frame_stride
     return pmd_fail(ctx, PMD_ERR_ARG, what,
                     "max shifts outside 1 .. 31, deviations outside 1 .. 7, a side above 16384, a patch side below 8 or "
                     "above the patch area d - 2 (m + e), or a grid outside 1 .. 4096 patches");
-  if (pw_bad_elem(elem)) return pmd_fail(ctx, PMD_ERR_ARG, what, "unknown element type");
-  if (row_stride < d2 || frame_stride < (long)(d1 - 1) * row_stride + d2)
+  if (pmd_bad_elem(elem)) return pmd_fail(ctx, PMD_ERR_ARG, what, "unknown element type");
+  if (pmd_short_strides(frame_stride, row_stride, d1, d2))
     return pmd_fail(ctx, PMD_ERR_ARG, what, "a stride is shorter than a row / a frame");
   if (!X || !ystart || !xstart || !centre || !tp || !surf) return pmd_fail(ctx, PMD_ERR_ARG, what, "null pointer");
   if (n == 0) return PMD_OK;
@@ -334,26 +309,16 @@ int pmd_patch_correlate(pmd_ctx* ctx, const void* X, int elem, long frame_stride
   long group = (long)(ws_bytes / per);
   if (group > 32768) group = 32768;
   pmd_prof_scope prof__(ctx, "patch_correlate");
-  const size_t esize = elem == PMD_ELEM_F32 ? 4 : 2;
+  const size_t esize = pmd_elem_size(elem);
   const int ns = p.nv * p.nu;
   for (long f0 = 0; f0 < n; f0 += group) {
     const int g = (int)(n - f0 < group ? n - f0 : group);
     const char* x = (const char*)X + (size_t)f0 * frame_stride * esize;
     const int* cen = centre + 2 * f0;
-    switch (elem) {
-      case PMD_ELEM_F32:
-        launch_patch<float>(ctx, p, x, frame_stride, row_stride, g, my, mx, ey, ex, ph, pw, gx, ystart, xstart, cen, tp,
-                            (float*)ws);
-        break;
-      case PMD_ELEM_U16:
-        launch_patch<uint16_t>(ctx, p, x, frame_stride, row_stride, g, my, mx, ey, ex, ph, pw, gx, ystart, xstart, cen, tp,
-                               (float*)ws);
-        break;
-      default:
-        launch_patch<int16_t>(ctx, p, x, frame_stride, row_stride, g, my, mx, ey, ex, ph, pw, gx, ystart, xstart, cen, tp,
-                              (float*)ws);
-        break;
-    }
+    pmd_with_elem(elem, [&](auto e) {
+      launch_patch<typename decltype(e)::type>(ctx, p, x, frame_stride, row_stride, g, my, mx, ey, ex, ph, pw, gx, ystart,
+                                               xstart, cen, tp, (float*)ws);
+    });
     PMD_LAUNCH_CHECK(ctx, "patch_correlate_kernel");
     const long total = (long)g * p.P * ns;
     hipLaunchKernelGGL(patch_reduce_kernel, dim3((unsigned)((total + PW_THREADS - 1) / PW_THREADS)), dim3(PW_THREADS), 0,
@@ -374,32 +339,27 @@ int pmd_warp_apply(pmd_ctx* ctx, const void* X, int elem, long frame_stride, lon
     return pmd_fail(ctx, PMD_ERR_ARG, what, "frame sides outside 1 .. 16384");
   if (gy < 1 || gy > PMD_WARP_MAX_GRID || gx < 1 || gx > PMD_WARP_MAX_GRID)
     return pmd_fail(ctx, PMD_ERR_ARG, what, "grid sides outside 1 .. 64");
-  if (pw_bad_elem(elem) || pw_bad_elem(out_elem)) return pmd_fail(ctx, PMD_ERR_ARG, what, "unknown element type");
+  if (pmd_bad_elem(elem) || pmd_bad_elem(out_elem)) return pmd_fail(ctx, PMD_ERR_ARG, what, "unknown element type");
   if (border != PMD_SHIFT_BORDER_NEAREST && border != PMD_SHIFT_BORDER_CONSTANT)
     return pmd_fail(ctx, PMD_ERR_ARG, what, "border is neither nearest (0) nor constant (1)");
-  if (row_stride < d2 || out_row_stride < d2 || frame_stride < (long)(d1 - 1) * row_stride + d2 ||
-      out_frame_stride < (long)(d1 - 1) * out_row_stride + d2)
+  if (pmd_short_strides(frame_stride, row_stride, d1, d2) ||
+      pmd_short_strides(out_frame_stride, out_row_stride, d1, d2))
     return pmd_fail(ctx, PMD_ERR_ARG, what, "a stride is shorter than a row / a frame");
   if (!X || !grid || !row_idx || !row_w || !col_idx || !col_w || !out)
     return pmd_fail(ctx, PMD_ERR_ARG, what, "null pointer");
   if (n == 0) return PMD_OK;
-  {
-    const size_t es = elem == PMD_ELEM_F32 ? 4 : 2, os = out_elem == PMD_ELEM_F32 ? 4 : 2;
-    const uintptr_t xa = (uintptr_t)X, xe = xa + ((size_t)(n - 1) * frame_stride + (size_t)(d1 - 1) * row_stride + d2) * es;
-    const uintptr_t oa = (uintptr_t)out,
-                    oe = oa + ((size_t)(n - 1) * out_frame_stride + (size_t)(d1 - 1) * out_row_stride + d2) * os;
-    if (xa < oe && oa < xe) return pmd_fail(ctx, PMD_ERR_ARG, what, "X and out overlap");
-  }
+  if (pmd_images_overlap(X, elem, frame_stride, row_stride, out, out_elem, out_frame_stride, out_row_stride, n, d1, d2))
+    return pmd_fail(ctx, PMD_ERR_ARG, what, "X and out overlap");
   pmd_prof_scope prof__(ctx, "warp_apply");
   const warp_args a = {frame_stride, row_stride, out_frame_stride, out_row_stride, d1, d2, gy, gx,
                        border == PMD_SHIFT_BORDER_CONSTANT, fill, grid, row_idx, col_idx, row_w, col_w};
   for (int n0 = 0; n0 < n; n0 += 32768) {
     const int g = n - n0 < 32768 ? n - n0 : 32768;
-    switch (elem) {
-      case PMD_ELEM_F32: launch_warp_out<float>(ctx, out_elem, a, X, out, n0, g); break;
-      case PMD_ELEM_U16: launch_warp_out<uint16_t>(ctx, out_elem, a, X, out, n0, g); break;
-      default: launch_warp_out<int16_t>(ctx, out_elem, a, X, out, n0, g); break;
-    }
+    pmd_with_elem(elem, [&](auto e) {
+      pmd_with_elem(out_elem, [&](auto o) {
+        launch_warp<typename decltype(e)::type, typename decltype(o)::type>(ctx, a, X, out, n0, g);
+      });
+    });
     PMD_LAUNCH_CHECK(ctx, "warp_kernel");
   }
   return PMD_OK;

@@ -5,7 +5,10 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <type_traits>
 #include <vector>
+
+#include "../../include/pmd_hip.h"   // enum pmd_elem
 
 #define PMD_OK 0
 #define PMD_ERR_HIP -1
@@ -147,7 +150,57 @@ __device__ __forceinline__ int pmd_xcd_tile() {
   }
   return off + m;
 }
+
+// value -> output element: fp32 as is; 16-bit integers round half to even, saturate, NaN -> 0 (export.quantize on the
+// host).  The one conversion of pmd_group_expand, pmd_shift_apply and pmd_warp_apply.
+template <typename O>
+__device__ __forceinline__ O pmd_quant(float v) {
+  if constexpr (sizeof(O) == 4) {
+    return v;
+  } else {
+    const float mn = std::is_signed<O>::value ? -32768.f : 0.f;
+    const float mx = std::is_signed<O>::value ? 32767.f : 65535.f;
+    if (v != v) return (O)0;
+    const float r = fminf(fmaxf(rintf(v), mn), mx);
+    return (O)(int)r;
+  }
+}
 #endif
+
+// ---- element types and strided images (host side of the launchers) --------------------------------------------------
+static inline bool pmd_bad_elem(int e) { return e != PMD_ELEM_F32 && e != PMD_ELEM_U16 && e != PMD_ELEM_I16; }
+static inline size_t pmd_elem_size(int e) { return e == PMD_ELEM_F32 ? 4 : 2; }
+
+// f(pmd_elem_tag<T>{}) with T the C type of ``elem`` (checked with pmd_bad_elem before); in f, ``typename
+// decltype(tag)::type`` is T
+template <typename T>
+struct pmd_elem_tag {
+  using type = T;
+};
+template <typename F>
+static inline void pmd_with_elem(int elem, F&& f) {
+  switch (elem) {
+    case PMD_ELEM_F32: f(pmd_elem_tag<float>{}); break;
+    case PMD_ELEM_U16: f(pmd_elem_tag<uint16_t>{}); break;
+    default: f(pmd_elem_tag<int16_t>{}); break;
+  }
+}
+
+// n frames of d1 x d2 elements at the given strides (in elements): a row stride shorter than a row, or a frame stride
+// shorter than a frame
+static inline bool pmd_short_strides(long frame_stride, long row_stride, int d1, int d2) {
+  return row_stride < d2 || frame_stride < (long)(d1 - 1) * row_stride + d2;
+}
+
+// whether the byte ranges of two such images, first element to last, intersect (n >= 1)
+static inline bool pmd_images_overlap(const void* X, int elem, long frame_stride, long row_stride, const void* out,
+                                      int out_elem, long out_frame_stride, long out_row_stride, int n, int d1, int d2) {
+  const uintptr_t xa = (uintptr_t)X, oa = (uintptr_t)out;
+  const uintptr_t xe = xa + ((size_t)(n - 1) * frame_stride + (size_t)(d1 - 1) * row_stride + d2) * pmd_elem_size(elem);
+  const uintptr_t oe =
+      oa + ((size_t)(n - 1) * out_frame_stride + (size_t)(d1 - 1) * out_row_stride + d2) * pmd_elem_size(out_elem);
+  return xa < oe && oa < xe;
+}
 
 // carve a caller-provided workspace
 struct pmd_arena {

@@ -25,8 +25,6 @@
 // apply_kernel        one thread per output pixel.  A frame whose weights are (1, 0, 0, 0) is copied (converted exactly
 //                     or quantised when the element types differ, no arithmetic); every other frame is
 //                     (w00 a + w01 b) + (w10 c + w11 d), each operation rounded on its own (contraction is off).
-#include <type_traits>
-
 #include "pmd_common.h"
 #include "../../include/pmd_hip.h"
 
@@ -200,20 +198,6 @@ __global__ __launch_bounds__(64) void peak_kernel(const float* __restrict__ surf
     }
 }
 
-// the conversion of pmd_group_expand: fp32 as is; 16-bit round half to even, saturate, NaN -> 0
-template <typename O>
-__device__ __forceinline__ O rg_quant(float v) {
-  if constexpr (sizeof(O) == 4) {
-    return v;
-  } else {
-    const float mn = std::is_signed<O>::value ? -32768.f : 0.f;
-    const float mx = std::is_signed<O>::value ? 32767.f : 65535.f;
-    if (v != v) return (O)0;
-    const float r = fminf(fmaxf(rintf(v), mn), mx);
-    return (O)(int)r;
-  }
-}
-
 template <typename E, typename O>
 __global__ __launch_bounds__(RG_THREADS) void apply_kernel(const E* __restrict__ X, long fs, long rs, int d1, int d2,
                                                             const int* __restrict__ ishift, const float* __restrict__ wts,
@@ -233,11 +217,11 @@ __global__ __launch_bounds__(RG_THREADS) void apply_kernel(const E* __restrict__
   const long cxa = min(max(xa, 0L), (long)d2 - 1), cxb = min(max(xb, 0L), (long)d2 - 1);
   if (copy) {
     if (constant && !(ina && inc)) {
-      *o = rg_quant<O>(fill);
+      *o = pmd_quant<O>(fill);
     } else {
       const E v = F[cya * rs + cxa];
       if constexpr (std::is_same<E, O>::value) *o = v;
-      else *o = rg_quant<O>((float)v);
+      else *o = pmd_quant<O>((float)v);
     }
     return;
   }
@@ -250,7 +234,7 @@ __global__ __launch_bounds__(RG_THREADS) void apply_kernel(const E* __restrict__
     if (!(inb && ind)) d = fill;
   }
   const float top = w00 * a + w01 * b, bot = w10 * c + w11 * d;
-  *o = rg_quant<O>(top + bot);
+  *o = pmd_quant<O>(top + bot);
 }
 
 template <typename E>
@@ -268,19 +252,6 @@ void launch_apply(pmd_ctx* ctx, const void* X, long fs, long rs, int n0, int g, 
   hipLaunchKernelGGL((apply_kernel<E, O>), grid, dim3(RG_THREADS), 0, ctx->stream, (const E*)X + (long)n0 * fs, fs, rs, d1,
                      d2, ishift + 2 * (long)n0, wts + 4 * (long)n0, constant, fill, (O*)out + (long)n0 * ofs, ofs, ors);
 }
-
-template <typename E>
-void launch_apply_out(pmd_ctx* ctx, int out_elem, const void* X, long fs, long rs, int n0, int g, int d1, int d2,
-                      const int* ishift, const float* wts, int constant, float fill, void* out, long ofs, long ors) {
-  if (out_elem == PMD_ELEM_F32)
-    launch_apply<E, float>(ctx, X, fs, rs, n0, g, d1, d2, ishift, wts, constant, fill, out, ofs, ors);
-  else if (out_elem == PMD_ELEM_U16)
-    launch_apply<E, uint16_t>(ctx, X, fs, rs, n0, g, d1, d2, ishift, wts, constant, fill, out, ofs, ors);
-  else
-    launch_apply<E, int16_t>(ctx, X, fs, rs, n0, g, d1, d2, ishift, wts, constant, fill, out, ofs, ors);
-}
-
-bool rg_bad_elem(int e) { return e != PMD_ELEM_F32 && e != PMD_ELEM_U16 && e != PMD_ELEM_I16; }
 
 bool rg_bad_geometry(int d1, int d2, int my, int mx) {
   return my < 1 || my > PMD_SHIFT_MAX || mx < 1 || mx > PMD_SHIFT_MAX || d1 > PMD_SHIFT_MAX_DIM || d2 > PMD_SHIFT_MAX_DIM ||
@@ -309,7 +280,7 @@ int pmd_shift_correlate(pmd_ctx* ctx, const void* X, int elem, long frame_stride
   if (rg_bad_geometry(d1, d2, my, mx))
     return pmd_fail(ctx, PMD_ERR_ARG, what,
                     "max shifts outside 1 .. 31, a side above 16384, or a window d - 2 m below 8 pixels");
-  if (rg_bad_elem(elem)) return pmd_fail(ctx, PMD_ERR_ARG, what, "unknown element type");
+  if (pmd_bad_elem(elem)) return pmd_fail(ctx, PMD_ERR_ARG, what, "unknown element type");
   if (y0 < 0 || x0 < 0 || row_stride < (long)x0 + d2 || frame_stride < ((long)y0 + d1 - 1) * row_stride + x0 + d2)
     return pmd_fail(ctx, PMD_ERR_ARG, what, "the image at (y0, x0) does not lie inside a row / a frame of the strides");
   if (!X || !tp || !surf) return pmd_fail(ctx, PMD_ERR_ARG, what, "null pointer");
@@ -320,16 +291,14 @@ int pmd_shift_correlate(pmd_ctx* ctx, const void* X, int elem, long frame_stride
   long group = (long)(ws_bytes / per);
   if (group > 32768) group = 32768;
   pmd_prof_scope prof__(ctx, "shift_correlate");
-  const size_t esize = elem == PMD_ELEM_F32 ? 4 : 2;
+  const size_t esize = pmd_elem_size(elem);
   const int ns = p.nsy * p.nsx;
   for (long f0 = 0; f0 < n; f0 += group) {
     const int g = (int)(n - f0 < group ? n - f0 : group);
     const char* x = (const char*)X + ((size_t)f0 * frame_stride + (size_t)y0 * row_stride + x0) * esize;
-    switch (elem) {
-      case PMD_ELEM_F32: launch_correlate<float>(ctx, p, x, frame_stride, row_stride, g, my, mx, tp, (float*)ws); break;
-      case PMD_ELEM_U16: launch_correlate<uint16_t>(ctx, p, x, frame_stride, row_stride, g, my, mx, tp, (float*)ws); break;
-      default: launch_correlate<int16_t>(ctx, p, x, frame_stride, row_stride, g, my, mx, tp, (float*)ws); break;
-    }
+    pmd_with_elem(elem, [&](auto e) {
+      launch_correlate<typename decltype(e)::type>(ctx, p, x, frame_stride, row_stride, g, my, mx, tp, (float*)ws);
+    });
     PMD_LAUNCH_CHECK(ctx, "correlate_kernel");
     hipLaunchKernelGGL(reduce_kernel, dim3((unsigned)((ns + RG_THREADS - 1) / RG_THREADS), (unsigned)g), dim3(RG_THREADS), 0,
                        ctx->stream, (const float*)ws, p.ntiles, ns, surf + f0 * ns);
@@ -360,39 +329,27 @@ int pmd_shift_apply(pmd_ctx* ctx, const void* X, int elem, long frame_stride, lo
   if (n < 0) return pmd_fail(ctx, PMD_ERR_ARG, what, "n is negative");
   if (d1 < 1 || d2 < 1 || d1 > PMD_SHIFT_MAX_DIM || d2 > PMD_SHIFT_MAX_DIM)
     return pmd_fail(ctx, PMD_ERR_ARG, what, "frame sides outside 1 .. 16384");
-  if (rg_bad_elem(elem) || rg_bad_elem(out_elem)) return pmd_fail(ctx, PMD_ERR_ARG, what, "unknown element type");
+  if (pmd_bad_elem(elem) || pmd_bad_elem(out_elem)) return pmd_fail(ctx, PMD_ERR_ARG, what, "unknown element type");
   if (border != PMD_SHIFT_BORDER_NEAREST && border != PMD_SHIFT_BORDER_CONSTANT)
     return pmd_fail(ctx, PMD_ERR_ARG, what, "border is neither nearest (0) nor constant (1)");
-  if (row_stride < d2 || out_row_stride < d2 || frame_stride < (long)(d1 - 1) * row_stride + d2 ||
-      out_frame_stride < (long)(d1 - 1) * out_row_stride + d2)
+  if (pmd_short_strides(frame_stride, row_stride, d1, d2) ||
+      pmd_short_strides(out_frame_stride, out_row_stride, d1, d2))
     return pmd_fail(ctx, PMD_ERR_ARG, what, "a stride is shorter than a row / a frame");
   if (!X || !ishift || !wts || !out) return pmd_fail(ctx, PMD_ERR_ARG, what, "null pointer");
   if (n == 0) return PMD_OK;
-  {
-    const size_t es = elem == PMD_ELEM_F32 ? 4 : 2, os = out_elem == PMD_ELEM_F32 ? 4 : 2;
-    const uintptr_t xa = (uintptr_t)X, xe = xa + ((size_t)(n - 1) * frame_stride + (size_t)(d1 - 1) * row_stride + d2) * es;
-    const uintptr_t oa = (uintptr_t)out,
-                    oe = oa + ((size_t)(n - 1) * out_frame_stride + (size_t)(d1 - 1) * out_row_stride + d2) * os;
-    if (xa < oe && oa < xe) return pmd_fail(ctx, PMD_ERR_ARG, what, "X and out overlap");
-  }
+  if (pmd_images_overlap(X, elem, frame_stride, row_stride, out, out_elem, out_frame_stride, out_row_stride, n, d1, d2))
+    return pmd_fail(ctx, PMD_ERR_ARG, what, "X and out overlap");
   pmd_prof_scope prof__(ctx, "shift_apply");
   const int constant = border == PMD_SHIFT_BORDER_CONSTANT;
   for (int n0 = 0; n0 < n; n0 += 32768) {
     const int g = n - n0 < 32768 ? n - n0 : 32768;
-    switch (elem) {
-      case PMD_ELEM_F32:
-        launch_apply_out<float>(ctx, out_elem, X, frame_stride, row_stride, n0, g, d1, d2, ishift, wts, constant, fill, out,
-                                out_frame_stride, out_row_stride);
-        break;
-      case PMD_ELEM_U16:
-        launch_apply_out<uint16_t>(ctx, out_elem, X, frame_stride, row_stride, n0, g, d1, d2, ishift, wts, constant, fill,
-                                   out, out_frame_stride, out_row_stride);
-        break;
-      default:
-        launch_apply_out<int16_t>(ctx, out_elem, X, frame_stride, row_stride, n0, g, d1, d2, ishift, wts, constant, fill,
-                                  out, out_frame_stride, out_row_stride);
-        break;
-    }
+    pmd_with_elem(elem, [&](auto e) {
+      pmd_with_elem(out_elem, [&](auto o) {
+        launch_apply<typename decltype(e)::type, typename decltype(o)::type>(ctx, X, frame_stride, row_stride, n0, g, d1, d2,
+                                                                             ishift, wts, constant, fill, out,
+                                                                             out_frame_stride, out_row_stride);
+      });
+    });
     PMD_LAUNCH_CHECK(ctx, "apply_kernel");
   }
   return PMD_OK;

@@ -14,27 +14,21 @@ bit is the same for every batching and source) goes through ``pmd_gemm`` (C = (R
 ``pmd_group_expand`` (csrc/expand_fused.hip), from C to finished output frames.  The kernel walks, per 64-pixel patch,
 the groups of U's columns that touch it (projection.group_tables, cached on the PMDArray and shared with project_frames;
 the per-patch lists are built here).  Reading the movie and the block plan are those of _stream, the two calls of a
-block those of _expand.Expander, shared with regressor_maps, summary_images and quantile_images.  Host destinations get
-each block through a ring of two device and two page-locked buffers: the copy to the host runs on a side stream and a
-writer thread puts the frames into the file or array while the next block computes.  Device memory and host memory do
-not grow with the movie's length.
+block those of _expand.Expander, shared with regressor_maps, summary_images and quantile_images.  The destinations, the
+sinks (host destinations get each block through a ring of two device and two page-locked buffers while a writer thread
+puts the frames into the file or array) and the scaffold that opens, finishes and aborts them are _sink's, shared with
+dff_movie and the two registrations; what is left here is the tables, the argument checks and the block's two calls.
+Device memory and host memory do not grow with the movie's length.
 """
-import itertools
-import os
-import queue
-import threading
-
 import numpy as np
 
 from ._expand import ENTRY_FIELDS, EXPORT_PATCH, _PANEL_CODE, Expander, expander_bytes, panel_code  # noqa: F401
 from ._movie import _ELEM, _device_free_bytes
+from ._sink import HOST_SLOTS, _destination, check_bigtiff, device_index, movie_pass  # noqa: F401
 from ._stream import BLOCK as EXPORT_BLOCK, block_plan as export_plan
-from ._stream import (batch_buffer_bytes, block_walk, check_fit, device_context, name_tuple, read_batches,
-                      source_info)
+from ._stream import batch_buffer_bytes, check_fit, device_context, each_block, name_tuple, source_info
 from .projection import MAX_ROWS, P_MAX, ROW_PAD, _pad, tables_for
 
-HOST_SLOTS = 2          # device + page-locked output buffers of a host destination
-COPY_THREADS = 8        # threads that copy a block into a NumPy destination
 PANELS = ("raw", "denoised", "residual")
 _OUT_DTYPES = {"float32": np.float32, "uint16": np.uint16, "int16": np.int16}
 
@@ -125,132 +119,6 @@ def _out_dtype(dtype):
     return np.dtype(_OUT_DTYPES[key])
 
 
-def _torch_dtype(np_dtype):
-    import torch
-
-    return {np.dtype(np.float32): torch.float32, np.dtype(np.int16): torch.int16,
-            np.dtype(np.uint16): getattr(torch, "uint16", None)}[np.dtype(np_dtype)]
-
-
-class _Dest:
-    """Where the frames go: kind in {"tiff", "npy", "device", "array"}."""
-
-    def __init__(self, kind, target, shape, dtype, bigtiff=None):
-        self.kind, self.target, self.shape, self.dtype, self.bigtiff = kind, target, shape, dtype, bigtiff
-        self.writer = None      # TiffWriter / open_memmap once opened
-        self.pool = None        # copy threads of a NumPy destination
-
-    def open(self):
-        from ._minitiff import TiffWriter
-
-        if self.kind == "tiff":
-            self.writer = TiffWriter(self.target, self.shape, self.dtype, bigtiff=self.bigtiff)
-        elif self.kind == "npy":
-            self.writer = np.lib.format.open_memmap(self.target, mode="w+", dtype=self.dtype, shape=self.shape)
-
-    def put(self, t0, block):
-        """Frames t0 .. t0 + len(block) (a NumPy array), in frame order."""
-        if self.kind == "tiff":
-            self.writer.write(block)
-        elif self.kind == "npy" or isinstance(self.target, np.ndarray):
-            tgt = self.writer if self.kind == "npy" else self.target
-            self._copy(tgt[t0:t0 + len(block)], block)
-        else:
-            tgt = self.target
-            try:
-                import torch
-
-                if isinstance(tgt, torch.Tensor):
-                    tgt[t0:t0 + len(block)] = torch.from_numpy(block)
-                    return
-            except ImportError:     # pragma: no cover - torch is a dependency
-                pass
-            tgt[t0:t0 + len(block)] = block
-
-    def _copy(self, dst, src):
-        """dst[...] = src in frame ranges on COPY_THREADS threads (NumPy copies release the GIL; one thread moves well
-        under the device-to-host rate)."""
-        n = len(src)
-        parts = max(1, min(COPY_THREADS, n))
-        if parts == 1:
-            dst[...] = src
-            return
-        if self.pool is None:
-            from concurrent.futures import ThreadPoolExecutor
-
-            self.pool = ThreadPoolExecutor(max_workers=COPY_THREADS)
-        edges = [n * k // parts for k in range(parts + 1)]
-        for f in [self.pool.submit(dst[a:b].__setitem__, Ellipsis, src[a:b]) for a, b in zip(edges, edges[1:])]:
-            f.result()
-
-    def shutdown(self):
-        if self.pool is not None:
-            self.pool.shutdown()
-            self.pool = None
-
-    def close(self):
-        if self.kind == "tiff":
-            self.writer.close()
-        elif self.kind == "npy":
-            self.writer.flush()
-            self.writer = None
-        return self.target
-
-    def abort(self):
-        """Remove a file this export created (nothing to undo for a caller's array)."""
-        if self.kind == "tiff" and self.writer is not None:
-            self.writer.abort()
-        elif self.kind == "npy":
-            self.writer = None
-            try:
-                os.remove(self.target)
-            except FileNotFoundError:
-                pass
-
-
-def _destination(out, shape, dtype, bigtiff, device_index):
-    from ._minitiff import tiff_needs_bigtiff
-
-    if isinstance(out, (str, os.PathLike)):
-        path = os.fspath(out)
-        ext = os.path.splitext(path)[1].lower()
-        if ext in (".tif", ".tiff"):
-            if bigtiff is False and tiff_needs_bigtiff(shape[0], shape[1], shape[2], dtype.itemsize):
-                raise ValueError("{} frames of {} x {} {} do not fit in a classic TIFF (4 GiB); use bigtiff=True or "
-                                 "bigtiff=None".format(shape[0], shape[1], shape[2], dtype))
-            return _Dest("tiff", path, shape, dtype, bigtiff)
-        if ext == ".npy":
-            return _Dest("npy", path, shape, dtype)
-        raise ValueError("out {!r}: unknown suffix {!r}; use .tif, .tiff or .npy, or pass an array".format(path, ext))
-    if bigtiff is not None:
-        raise ValueError("bigtiff applies to a .tif / .tiff destination only")
-    try:
-        got_shape = tuple(int(x) for x in out.shape)
-    except (AttributeError, TypeError):
-        raise TypeError("out must be a path or an array-like with a shape and a dtype, got {}".format(
-            type(out).__name__)) from None
-    if got_shape != tuple(shape):
-        raise ValueError("out has shape {}, the export needs {}".format(got_shape, tuple(shape)))
-    import torch
-
-    if isinstance(out, torch.Tensor):
-        if out.dtype != _torch_dtype(dtype):
-            raise ValueError("out has dtype {}, the export writes {}".format(out.dtype, dtype))
-        if out.device.type != "cpu":
-            if not out.is_contiguous() or out.device != torch.device("cuda", device_index):
-                raise ValueError("a device tensor destination must be contiguous and on cuda:{} (got {}{})".format(
-                    device_index, out.device, "" if out.is_contiguous() else ", not contiguous"))
-            return _Dest("device", out, shape, dtype)
-        return _Dest("array", out, shape, dtype)
-    try:
-        got = np.dtype(out.dtype)
-    except (AttributeError, TypeError):
-        raise TypeError("out has no NumPy dtype ({})".format(type(out).__name__)) from None
-    if got != dtype:
-        raise ValueError("out has dtype {}, the export writes {}".format(got, dtype))
-    return _Dest("array", out, shape, dtype)
-
-
 def export_device_bytes(D, nb, esize, n_panels, out_esize, n_cols, rank, n_entries, n_a, n_patches, needs_movie,
                         host_source, n_batches, host_dest, factors_on_device):
     """Device bytes export_movie holds for a movie of D pixels read in batches of nb frames; no term grows with the
@@ -287,17 +155,14 @@ def export_movie(pmd, out, movie=None, *, panels="denoised", dtype="float32", fr
         raise TypeError("pmd must be a localmd_amd.PMDArray, got {}".format(type(pmd).__name__))
     panels = name_tuple(panels, PANELS, "panel", "panels")
     out_dtype = _out_dtype(dtype)
-    if bigtiff is not None and not isinstance(bigtiff, bool):
-        raise ValueError("bigtiff must be None, True or False")
+    check_bigtiff(bigtiff)
     T, d1, d2 = (int(x) for x in pmd.shape)
     D = d1 * d2
     needs_movie = any(p != "denoised" for p in panels)
     if needs_movie and movie is None:
         raise ValueError("panels {} need the movie: pass movie=".format(tuple(p for p in panels if p != "denoised")))
     on_device, esize = source_info(movie, pmd.shape) if movie is not None else (False, 4)
-    dv = getattr(pmd, "_dev", None)
-    dev_index = dv["ctx"].device_index if dv is not None else (ctx.device_index if ctx is not None else
-                                                               (0 if device is None else int(device)))
+    dev_index = device_index(pmd, device, ctx)
     dest = _destination(out, (T, d1, len(panels) * d2), out_dtype, bigtiff, dev_index)
     plan = export_plan(T, frame_batch_size)
     nb = plan[0][1] - plan[0][0] if plan else 0
@@ -309,144 +174,12 @@ def export_movie(pmd, out, movie=None, *, panels="denoised", dtype="float32", fr
                                    int(tabs["a"].size), int(xt["n_patches"]), needs_movie, not on_device, len(plan),
                                    dest.kind != "device", dv is not None)
         check_fit("export_movie", need, _device_free_bytes(ctx.device))
-        dest.open()
-        try:
-            _export(ctx, pmd, dv, tabs, xt, movie if needs_movie else None, plan, panels, out_dtype, dest,
-                    frame_batch_size, num_workers)
-        except BaseException:
-            dest.abort()
-            raise
-        finally:
-            dest.shutdown()
-        return dest.close()
+        ex = Expander(ctx, pmd, dv, tabs, xt)
+        P, code, out_elem = len(panels), panel_code(panels), _ELEM[out_dtype]
 
-
-class _HostSink:
-    """Output blocks to the host: HOST_SLOTS device buffers and as many page-locked ones; block k uses slot k mod
-    HOST_SLOTS.  Its copy to the host runs on a side stream, and a writer thread puts it into the destination while the
-    next blocks compute.  An error in the writer thread is raised in the caller."""
-
-    def __init__(self, ctx, dest, frame_bytes, frame_shape, np_dtype, block):
-        import torch
-
-        self.torch = torch
-        self.ctx, self.dest = ctx, dest
-        self.frame_bytes, self.frame_shape, self.np_dtype = frame_bytes, frame_shape, np_dtype
-        nbytes = block * frame_bytes
-        self.dev = [torch.empty(nbytes, dtype=torch.uint8, device=ctx.device) for _ in range(HOST_SLOTS)]
-        self.pin = [torch.empty(nbytes, dtype=torch.uint8, pin_memory=True) for _ in range(HOST_SLOTS)]
-        self.copied = [None] * HOST_SLOTS                   # event behind the last device-to-host copy out of a slot
-        self.consumed = [threading.Event() for _ in range(HOST_SLOTS)]
-        for e in self.consumed:
-            e.set()
-        self.side = torch.cuda.Stream(device=ctx.device)
-        self.q = queue.Queue()
-        self.error = None
-        self.thread = threading.Thread(target=self._writer, daemon=True)
-        self.thread.start()
-
-    def _writer(self):
-        while True:
-            item = self.q.get()
-            if item is None:
-                return
-            fin, j, t0, m = item
-            try:
-                if self.error is None:
-                    fin.synchronize()
-                    block = self.pin[j][:m * self.frame_bytes].numpy().view(self.np_dtype).reshape((m,) + self.frame_shape)
-                    self.dest.put(t0, block)
-            except BaseException as e:      # noqa: BLE001 - handed to the caller
-                self.error = e
-            finally:
-                self.consumed[j].set()
-
-    def dst(self, k, t0):
-        """Device pointer the kernel writes block k (frames from t0) to."""
-        j = k % HOST_SLOTS
-        if self.copied[j] is not None:
-            self.torch.cuda.current_stream(self.ctx.device).wait_event(self.copied[j])
-        return self.dev[j].data_ptr()
-
-    def done(self, k, t0, m):
-        torch = self.torch
-        j = k % HOST_SLOTS
-        self.consumed[j].wait()         # the writer has put the slot's previous block
-        self._raise()
-        self.consumed[j].clear()
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(self.ctx.device))
-        self.side.wait_event(ev)
-        with torch.cuda.stream(self.side):
-            self.pin[j][:m * self.frame_bytes].copy_(self.dev[j][:m * self.frame_bytes], non_blocking=True)
-            fin = torch.cuda.Event()
-            fin.record(self.side)
-        self.copied[j] = fin
-        self.q.put((fin, j, t0, m))
-
-    def _raise(self):
-        if self.error is not None:
-            raise self.error
-
-    def finish(self):
-        self.q.put(None)
-        self.thread.join()
-        self._raise()
-
-    def abort(self):
-        self.error = self.error or RuntimeError("export aborted")
-        self.q.put(None)
-        self.thread.join()
-        self.side.synchronize()
-
-
-class _DeviceSink:
-    """Output blocks straight into a contiguous device tensor."""
-
-    def __init__(self, out, frame_bytes):
-        self.base, self.frame_bytes = out.data_ptr(), frame_bytes
-
-    def dst(self, k, t0):
-        return self.base + t0 * self.frame_bytes
-
-    def done(self, k, t0, m):
-        pass
-
-    def finish(self):
-        pass
-
-    def abort(self):
-        pass
-
-
-def _export(ctx, pmd, dv, tabs, xt, movie, plan, panels, out_dtype, dest, frame_batch_size, num_workers):
-    import ctypes as C
-
-    T, d1, d2 = (int(x) for x in pmd.shape)
-    D = d1 * d2
-    P = len(panels)
-    code = panel_code(panels)
-    out_elem = _ELEM[out_dtype]
-    frame_bytes = D * P * out_dtype.itemsize
-    ex = Expander(ctx, pmd, dv, tabs, xt)
-
-    if dest.kind == "device":
-        sink = _DeviceSink(dest.target, frame_bytes)
-    else:
-        sink = _HostSink(ctx, dest, frame_bytes, (d1, P * d2), out_dtype, max(1, min(T, EXPORT_BLOCK)))
-    walk, count = block_walk(plan, D), itertools.count()
-
-    def consume(batch, elem, b0, n):
-        for c0, m, yp in walk(batch, b0):
+        def write(c0, m, yp, elem, to):
             ex.coefficients(c0, m)
-            k = next(count)
-            ex.expand(m, P, code, yp, elem, out=C.c_void_p(sink.dst(k, c0)), out_elem=out_elem)
-            sink.done(k, c0, m)
+            ex.expand(m, P, code, yp, elem, out=to, out_elem=out_elem)
 
-    try:
-        read_batches(ctx, movie, [(b0, b1) for b0, b1, _ in plan], frame_batch_size, num_workers, consume)
-        sink.finish()
-        ctx.sync()
-    except BaseException:
-        sink.abort()
-        raise
+        return movie_pass(ctx, dest, (d1, P * d2), out_dtype, max(1, min(T, EXPORT_BLOCK)),
+                          each_block(ctx, movie if needs_movie else None, plan, D, frame_batch_size, num_workers), write)

@@ -25,15 +25,20 @@ is the second half on its own (a second channel); ``WarpedMovie`` applies the fi
 The movie is read once in blocks of 1024 frames: rigid correlate and peak, the peak tables to the host, patch correlate
 (in sub-blocks of frames, so that the surfaces stay under SURFACE_CAP) and peak, the patch peak tables to the host, the
 parabola and the fallbacks, the grid back, the warp into the sink.  Device memory does not grow with the movie's length.
+
+The pass itself (register.motion_pass) and the front doors' checks (register.register_args, apply_args) are
+register.py's, the destinations and sinks _sink's; this module holds what differs: the patch grid, the field, the warp,
+the patch estimator and its finish on the host.
 """
+import functools
+
 import numpy as np
 
-from ._movie import _ELEM, _device_free_bytes, _stream_dtype
-from ._stream import BLOCK, block_plan, block_walk, check_fit, device_context, read_batches
+from ._movie import _ELEM, _stream_dtype
+from ._stream import BLOCK
 from .dataset import lazy_data_loader
-from .register import (MAX_DIM, Registration, _build_template, _check_counts, _check_no_alias, _check_stream_args,
-                       _dev_index, _Estimator, _is_int, _movie_info, _quantize, _resolve_dtype, check_border,
-                       check_max_shift, register_device_bytes, sample_frames, subpixel_peak, valid_rect)
+from .register import (Registration, _is_int, _quantize, _resolve_dtype, apply_args, check_border, check_max_shift,
+                       motion_pass, register_args, register_device_bytes, subpixel_peak, valid_rect)
 
 MAX_DEV = 7                  # PMD_PATCH_MAX_DEV
 MAX_PATCHES = 4096           # PMD_PATCH_MAX
@@ -378,6 +383,20 @@ class _PatchEstimator:
         tab = self.tab[:10 * m * P].cpu().numpy()
         return arg, tab[:m * P].reshape(m, pg.gy, pg.gx).copy(), tab[m * P:].reshape(m, pg.gy, pg.gx, 3, 3).copy()
 
+    def tables(self, T):
+        """What the pass finds per frame and patch (motion_pass keeps them next to the rigid tables)."""
+        g = (T, self.pg.gy, self.pg.gx)
+        return dict(patch_shifts=np.zeros(g + (2,), np.float64), ints=np.zeros(g + (2,), np.int32),
+                    ppeak=np.zeros(g, np.float32), fallback=np.zeros(g, bool))
+
+    def refine(self, X, elem, m, centre, arg, rigid, subpixel, found, sl):
+        """The patch shifts (m, gy, gx, 2) of a block from its rigid peaks (``centre`` on the device, ``arg`` on the
+        host) and rigid shifts: run, then the host finish; the block's rows ``sl`` of the tables are filled."""
+        parg, ppeak, pneigh = self.run(X, elem, m, centre)
+        sh, ints, fb = finish_patches(rigid, arg, parg, ppeak, pneigh, self.zero, subpixel)
+        found["patch_shifts"][sl], found["ints"][sl], found["ppeak"][sl], found["fallback"][sl] = sh, ints, ppeak, fb
+        return sh
+
 
 class _Warper:
     """The field tables and the grid of one block on the device, and the call."""
@@ -400,99 +419,6 @@ class _Warper:
         ri, rw, ci, cw = self.tables
         self.ctx.call("pmd_warp_apply", X, int(elem), D, self.d2, int(m), self.d1, self.d2, ptr(self.grid), self.gy, self.gx,
                       ptr(ri), ptr(rw), ptr(ci), ptr(cw), self.mode, self.fill, out, self.out_elem, D, self.d2)
-
-
-def _run(movie, info, dest, out_dtype, border, pg, est_args, given, frame_batch_size, num_workers, device, ctx, what):
-    """The one pass: per 1024-frame block estimate (est_args) or take (given = (shifts, centers)) the patch shifts, and
-    warp into the destination when there is one.  Returns what the estimate found."""
-    import ctypes as C
-    import itertools
-    from .export import _DeviceSink, _HostSink
-
-    T, d1, d2, on_device, np_dtype = info
-    D = d1 * d2
-    plan = block_plan(T, frame_batch_size)
-    nb = plan[0][1] - plan[0][0] if plan else 0
-    found = {}
-    with device_context(None, device, ctx) as (ctx, _):
-        n_sample = 0
-        if est_args is not None and est_args["template"] is None:
-            n_sample = len(sample_frames(T, est_args["template_frames"]))
-        gy, gx = (pg.gy, pg.gx) if est_args is not None else given[0].shape[1:3]
-        need = piecewise_device_bytes(d1=d1, d2=d2, nb=nb, esize=np_dtype.itemsize, host_source=not on_device,
-                                      n_batches=len(plan), gy=gy, gx=gx, pg=pg, n_sample=n_sample,
-                                      out_esize=out_dtype.itemsize if dest is not None else 0,
-                                      host_dest=dest is not None and dest.kind != "device")
-        check_fit(what, need, _device_free_bytes(ctx.device))
-        cap = max(1, min(BLOCK, nb))
-        est = pest = None
-        if est_args is not None:
-            my, mx = pg.max_shift
-            if est_args["template"] is None:
-                pre = _Estimator(ctx, d1, d2, my, mx, max(1, n_sample))
-                template = _build_template(ctx, pre, movie, T, d1, d2, np_dtype, on_device, est_args["template_frames"],
-                                           est_args["template_iters"])
-                del pre
-            else:
-                template = est_args["template"]
-            est, pest = _Estimator(ctx, d1, d2, my, mx, cap), _PatchEstimator(ctx, pg, cap)
-            est.set_template(template)
-            pest.set_template(template)
-            found.update(template=template, arg=np.zeros((T, 2), np.int32), peak=np.zeros(T, np.float32),
-                         rigid=np.zeros((T, 2), np.float64), shifts=np.zeros((T, pg.gy, pg.gx, 2), np.float64),
-                         ints=np.zeros((T, pg.gy, pg.gx, 2), np.int32), ppeak=np.zeros((T, pg.gy, pg.gx), np.float32),
-                         fallback=np.zeros((T, pg.gy, pg.gx), bool))
-            centers = pg.centers
-        else:
-            shifts, centers = given
-        if dest is not None:
-            dest.open()
-        try:
-            sink = wp = None
-            if dest is not None:
-                wp = _Warper(ctx, d1, d2, gy, gx, centers, cap, border, _ELEM[out_dtype])
-                fb = D * out_dtype.itemsize
-                sink = (_DeviceSink(dest.target, fb) if dest.kind == "device" else
-                        _HostSink(ctx, dest, fb, (d1, d2), out_dtype, cap))
-            walk, count = block_walk(plan, D), itertools.count()
-
-            def consume(batch, elem, b0, n):
-                for c0, m, yp in walk(batch, b0):
-                    if est is not None:
-                        arg, peak, neigh = est.run(yp, elem, c0, m)
-                        rigid = arg.astype(np.float64)
-                        if est_args["subpixel"]:
-                            rigid = rigid + subpixel_peak(neigh)
-                        # est.arg still holds the integer peaks of this block on the device: they are the centres
-                        parg, ppeak, pneigh = pest.run(yp, elem, m, est.arg)
-                        sh, ints, fb_ = finish_patches(rigid, arg, parg, ppeak, pneigh, pest.zero, est_args["subpixel"])
-                        sl = slice(c0, c0 + m)
-                        found["arg"][sl], found["peak"][sl], found["rigid"][sl] = arg, peak, rigid
-                        found["shifts"][sl], found["ints"][sl], found["ppeak"][sl], found["fallback"][sl] = sh, ints, ppeak, fb_
-                    else:
-                        sh = shifts[c0:c0 + m]
-                    if sink is not None:
-                        k = next(count)
-                        wp.run(yp, elem, m, sh, C.c_void_p(sink.dst(k, c0)))
-                        sink.done(k, c0, m)
-
-            try:
-                read_batches(ctx, movie, [(b0, b1) for b0, b1, _ in plan], frame_batch_size, num_workers, consume)
-                if sink is not None:
-                    sink.finish()
-                ctx.sync()
-            except BaseException:
-                if sink is not None:
-                    sink.abort()
-                raise
-        except BaseException:
-            if dest is not None:
-                dest.abort()
-            raise
-        finally:
-            if dest is not None:
-                dest.shutdown()
-        return found, (dest.close() if dest is not None else None)
 
 
 def _out_dtype(dtype):
@@ -525,35 +451,19 @@ def register_piecewise(movie, out=None, *, max_shift=15, patch=128, stride=96, m
     (piecewise_device_bytes is checked before anything is allocated).  Argument errors are raised before any device work
     and before a file is created; a file this call created is removed when it fails midway.  ``out`` must not share
     memory with the movie."""
-    from .export import _destination
-
-    info = _movie_info(movie)
-    T, d1, d2, on_device, np_dtype = info
-    if T < 1:
-        raise ValueError("the movie has no frames")
-    pg = PatchGrid(d1, d2, max_shift, max_deviation, patch, stride)
-    _check_counts(template_frames, template_iters)
-    _check_stream_args(frame_batch_size, bigtiff)
-    check_border(border)
-    if template is not None:
-        template = np.asarray(template)
-        if template.dtype.kind not in "iuf" or template.shape != (d1, d2):
-            raise ValueError("template must be a ({}, {}) image of numbers, got {} {}".format(d1, d2, template.dtype,
-                                                                                               template.shape))
-        template = np.ascontiguousarray(template, dtype=np.float32)
-    out_dtype = _out_dtype(dtype)
-    dest = None
-    if out is not None:
-        _check_no_alias(movie, out)
-        dest = _destination(out, (T, d1, d2), out_dtype, bigtiff, _dev_index(device, ctx))
-    elif bigtiff is not None:
-        raise ValueError("bigtiff applies to a .tif / .tiff destination only")
-    est_args = dict(template=template, template_frames=int(template_frames), template_iters=int(template_iters),
-                    subpixel=bool(subpixel))
-    found, _ = _run(movie, info, dest, out_dtype, border, pg, est_args, None, int(frame_batch_size), num_workers, device,
-                    ctx, "register_piecewise")
-    rigid = Registration(found["rigid"], found["arg"], found["peak"], found["template"], pg.max_shift, border)
-    return PiecewiseRegistration(rigid, found["shifts"], found["ints"], found["ppeak"], found["fallback"], pg,
+    info, pg, template, out_dtype, dest = register_args(
+        movie, out, lambda d1, d2: PatchGrid(d1, d2, max_shift, max_deviation, patch, stride), template, template_frames,
+        template_iters, frame_batch_size, bigtiff, border, lambda src: _out_dtype(dtype), device, ctx)
+    (my, mx), subpixel = pg.max_shift, bool(subpixel)
+    estimate = dict(my=my, mx=mx, template=template, template_frames=int(template_frames),
+                    template_iters=int(template_iters), subpixel=subpixel, surfaces=False)
+    found, _ = motion_pass(
+        "register_piecewise", movie, info, dest, out_dtype, int(frame_batch_size), num_workers, device, ctx,
+        functools.partial(piecewise_device_bytes, gy=pg.gy, gx=pg.gx, pg=pg), estimate=estimate,
+        patches=lambda ctx, cap: _PatchEstimator(ctx, pg, cap),
+        applier=lambda ctx, cap: _Warper(ctx, pg.d1, pg.d2, pg.gy, pg.gx, pg.centers, cap, border, _ELEM[out_dtype]))
+    rigid = Registration(found["shifts"], found["arg"], found["peak"], found["template"], pg.max_shift, border)
+    return PiecewiseRegistration(rigid, found["patch_shifts"], found["ints"], found["ppeak"], found["fallback"], pg,
                                  found["template"], border)
 
 
@@ -564,24 +474,15 @@ def apply_field(movie, out, registration, *, centers=None, border=None, dtype=No
     coordinates of the grid's rows and columns) to ``out``; for a second channel, or a field from elsewhere.  Sources,
     destinations, ``border`` (None: the registration's, else "nearest") and ``dtype`` are those of register_piecewise.
     The movie is read once.  Returns the path or the array."""
-    from .export import _destination
-
-    info = _movie_info(movie)
-    T, d1, d2, on_device, np_dtype = info
-    if T < 1:
-        raise ValueError("the movie has no frames")
-    if d1 > MAX_DIM or d2 > MAX_DIM:
-        raise ValueError("frames of {} x {} are larger than {} pixels a side".format(d1, d2, MAX_DIM))
-    given = _field_args(registration, centers, T, d1, d2)
     if border is None:
         border = registration.border if isinstance(registration, PiecewiseRegistration) else "nearest"
-    _check_stream_args(frame_batch_size, bigtiff)
-    check_border(border)
-    out_dtype = _out_dtype(dtype)
-    if out is None:
-        raise TypeError("apply_field needs a destination")
-    _check_no_alias(movie, out)
-    dest = _destination(out, (T, d1, d2), out_dtype, bigtiff, _dev_index(device, ctx))
-    _, res = _run(movie, info, dest, out_dtype, border, None, None, given, int(frame_batch_size), num_workers, device, ctx,
-                  "apply_field")
+    info, (shifts, cen), out_dtype, dest = apply_args(
+        "apply_field", movie, out, lambda T, d1, d2: _field_args(registration, centers, T, d1, d2), frame_batch_size,
+        bigtiff, border, lambda src, given: _out_dtype(dtype), device, ctx)
+    _, d1, d2 = info[:3]
+    gy, gx = shifts.shape[1:3]
+    _, res = motion_pass(
+        "apply_field", movie, info, dest, out_dtype, int(frame_batch_size), num_workers, device, ctx,
+        functools.partial(piecewise_device_bytes, gy=gy, gx=gx), given=shifts,
+        applier=lambda ctx, cap: _Warper(ctx, d1, d2, gy, gx, cen, cap, border, _ELEM[out_dtype]))
     return res

@@ -23,11 +23,18 @@ The movie is read in the frame batches of the streamed decomposition and handled
 peak, the 48 bytes per frame of the peak tables to the host, the parabola, the weight tables back, apply into the sink.
 The shifts of a block are final when its surfaces are (the template is fixed before the pass), so one read serves every
 destination.  Device memory does not grow with the movie's length.
+
+``motion_pass`` is that pass, written once for this module and for piecewise.py (which adds a patch estimator and
+swaps the applier for its warp); ``register_args`` and ``apply_args`` are the front doors' shared checks.  Destinations,
+sinks and the open / finish / abort scaffold under the pass are _sink's.
 """
+import functools
+
 import numpy as np
 
 from ._movie import _ELEM, _device_elem, _device_free_bytes, _stream_dtype
-from ._stream import BLOCK, batch_buffer_bytes, block_plan, block_walk, check_fit, device_context, read_batches
+from ._sink import HOST_SLOTS, _destination, _optional_destination, check_bigtiff, device_index, movie_pass
+from ._stream import BLOCK, batch_buffer_bytes, block_plan, check_fit, device_context, each_block
 from .dataset import lazy_data_loader
 
 MAX_SHIFT = 31               # PMD_SHIFT_MAX
@@ -196,8 +203,6 @@ def register_device_bytes(*, d1, d2, nb, esize, host_source, n_batches, my=None,
     given) t', the tile partials of one launch group, the surfaces of one 1024-frame block (twice when they leave
     through the host ring) and the peak tables; for the template the n_sample sample frames, raw and shifted; for a
     host destination the output ring of two blocks; the per-frame tables of a block."""
-    from .export import HOST_SLOTS
-
     D = d1 * d2
     blk = min(BLOCK, nb)
     need = batch_buffer_bytes(nb, D, esize, host_source, n_batches)
@@ -417,98 +422,78 @@ def _check_counts(template_frames, template_iters):
         raise ValueError("template_iters must be an int >= 0, got {!r}".format(template_iters))
 
 
-def _dev_index(device, ctx):
-    return ctx.device_index if ctx is not None else (0 if device is None else int(device))
+def motion_pass(what, movie, info, dest, out_dtype, frame_batch_size, num_workers, device, ctx, device_bytes, *,
+                estimate=None, patches=None, applier=None, given=None):
+    """The one pass of register_movie / apply_shifts and of register_piecewise / apply_field: per 1024-frame block
+    estimate the shifts or take them from ``given`` (indexed by frame), and apply them into ``dest`` when there is one
+    (_sink.movie_pass).  Returns (what the estimate found, what dest.close() returned).
 
-
-def _run(movie, info, out_dest, out_dtype, border, est_args, given_shifts, frame_batch_size, num_workers, device, ctx,
-         what):
-    """The one pass: per 1024-frame block estimate (est_args) or take (given_shifts) the shifts, and apply them into the
-    destination when there is one.  Returns what the estimate found."""
-    import ctypes as C
-    import itertools
+    ``estimate``: None, or the rigid step's dict(my, mx, template, template_frames, template_iters, subpixel, surfaces);
+    the pass builds the template when it is None, brings the surfaces to the host through a ring when asked, and keeps
+    the ``found`` tables template, arg, peak, shifts.  ``patches(ctx, cap)``: None, or what refines a block's rigid
+    shifts (piecewise._PatchEstimator: set_template, tables, refine).  ``applier(ctx, cap)``: an _Applier or a
+    piecewise._Warper, built when there is a destination.  ``device_bytes(**terms)``: the caller's device-memory bound
+    on the terms the pass knows, checked before anything is allocated."""
     from ._stream import ToHost
-    from .export import _DeviceSink, _HostSink
 
     T, d1, d2, on_device, np_dtype = info
-    D = d1 * d2
     plan = block_plan(T, frame_batch_size)
     nb = plan[0][1] - plan[0][0] if plan else 0
     found = {}
     with device_context(None, device, ctx) as (ctx, _):
         n_sample = 0
-        if est_args is not None and est_args["template"] is None:
-            n_sample = len(sample_frames(T, est_args["template_frames"]))
-        need = register_device_bytes(d1=d1, d2=d2, nb=nb, esize=np_dtype.itemsize, host_source=not on_device,
-                                     n_batches=len(plan), my=est_args and est_args["my"], mx=est_args and est_args["mx"],
-                                     n_sample=n_sample, out_esize=out_dtype.itemsize if out_dest is not None else 0,
-                                     host_dest=out_dest is not None and out_dest.kind != "device",
-                                     surfaces=bool(est_args and est_args["surfaces"]))
+        if estimate is not None and estimate["template"] is None:
+            n_sample = len(sample_frames(T, estimate["template_frames"]))
+        need = device_bytes(d1=d1, d2=d2, nb=nb, esize=np_dtype.itemsize, host_source=not on_device, n_batches=len(plan),
+                            n_sample=n_sample, out_esize=out_dtype.itemsize if dest is not None else 0,
+                            host_dest=dest is not None and dest.kind != "device")
         check_fit(what, need, _device_free_bytes(ctx.device))
         cap = max(1, min(BLOCK, nb))
-        est = ring = None
-        if est_args is not None:
-            my, mx = est_args["my"], est_args["mx"]
-            if est_args["template"] is None:
+        est = pest = ring = None
+        if estimate is not None:
+            my, mx, template = estimate["my"], estimate["mx"], estimate["template"]
+            if template is None:
                 pre = _Estimator(ctx, d1, d2, my, mx, max(1, n_sample))
-                template = _build_template(ctx, pre, movie, T, d1, d2, np_dtype, on_device, est_args["template_frames"],
-                                           est_args["template_iters"])
+                template = _build_template(ctx, pre, movie, T, d1, d2, np_dtype, on_device, estimate["template_frames"],
+                                           estimate["template_iters"])
                 del pre
-            else:
-                template = est_args["template"]
-            if est_args["surfaces"]:
+            if estimate["surfaces"]:
                 ring = ToHost(ctx, 1, T * (2 * my + 1) * (2 * mx + 1))
             est = _Estimator(ctx, d1, d2, my, mx, cap, ring)
             est.set_template(template)
             found.update(template=template, arg=np.zeros((T, 2), np.int32), peak=np.zeros(T, np.float32),
                          shifts=np.zeros((T, 2), np.float64))
-        if out_dest is not None:
-            out_dest.open()
-        try:
-            sink = ap = None
-            if out_dest is not None:
-                ap = _Applier(ctx, d1, d2, cap, border, _ELEM[out_dtype])
-                fb = D * out_dtype.itemsize
-                sink = (_DeviceSink(out_dest.target, fb) if out_dest.kind == "device" else
-                        _HostSink(ctx, out_dest, fb, (d1, d2), out_dtype, cap))
-            walk, count = block_walk(plan, D), itertools.count()
+            if patches is not None:
+                pest = patches(ctx, cap)
+                pest.set_template(template)
+                found.update(pest.tables(T))
+        ap = applier(ctx, cap) if dest is not None else None
 
-            def consume(batch, elem, b0, n):
-                for c0, m, yp in walk(batch, b0):
-                    if est is not None:
-                        arg, peak, neigh = est.run(yp, elem, c0, m)
-                        sh = arg.astype(np.float64)
-                        if est_args["subpixel"]:
-                            sh = sh + subpixel_peak(neigh)
-                        found["arg"][c0:c0 + m], found["peak"][c0:c0 + m], found["shifts"][c0:c0 + m] = arg, peak, sh
-                    else:
-                        sh = given_shifts[c0:c0 + m]
-                    if sink is not None:
-                        k = next(count)
-                        ap.run(yp, elem, m, sh, C.c_void_p(sink.dst(k, c0)))
-                        sink.done(k, c0, m)
+        def write(c0, m, yp, elem, out):
+            if est is not None:
+                arg, peak, neigh = est.run(yp, elem, c0, m)
+                sh = arg.astype(np.float64)
+                if estimate["subpixel"]:
+                    sh = sh + subpixel_peak(neigh)
+                sl = slice(c0, c0 + m)
+                found["arg"][sl], found["peak"][sl], found["shifts"][sl] = arg, peak, sh
+                if pest is not None:
+                    # est.arg still holds the integer peaks of this block on the device: they are the centres
+                    sh = pest.refine(yp, elem, m, est.arg, arg, sh, estimate["subpixel"], found, sl)
+            else:
+                sh = given[c0:c0 + m]
+            if out is not None:
+                ap.run(yp, elem, m, sh, out)
 
-            try:
-                read_batches(ctx, movie, [(b0, b1) for b0, b1, _ in plan], frame_batch_size, num_workers, consume)
-                if sink is not None:
-                    sink.finish()
-                if ring is not None:
-                    ring.finish()
-                ctx.sync()
-            except BaseException:
-                if sink is not None:
-                    sink.abort()
-                raise
-        except BaseException:
-            if out_dest is not None:
-                out_dest.abort()
-            raise
-        finally:
-            if out_dest is not None:
-                out_dest.shutdown()
+        def blocks(each):
+            each_block(ctx, movie, plan, d1 * d2, frame_batch_size, num_workers)(each)
+            if ring is not None:
+                ring.finish()
+
+        res = movie_pass(ctx, dest, (d1, d2), out_dtype, cap, blocks, write)
         if ring is not None:
             found["surfaces"] = ring.out.reshape(T, 2 * my + 1, 2 * mx + 1)
-        return found, (out_dest.close() if out_dest is not None else None)
+        return found, res
 
 
 def _check_no_alias(movie, out):
@@ -529,8 +514,52 @@ def _check_no_alias(movie, out):
 def _check_stream_args(frame_batch_size, bigtiff):
     if not _is_int(frame_batch_size) or frame_batch_size < 1:
         raise ValueError("frame_batch_size must be an int >= 1, got {!r}".format(frame_batch_size))
-    if bigtiff is not None and not isinstance(bigtiff, bool):
-        raise ValueError("bigtiff must be None, True or False")
+    check_bigtiff(bigtiff)
+
+
+def register_args(movie, out, geometry, template, template_frames, template_iters, frame_batch_size, bigtiff, border,
+                  out_dtype_of, device, ctx):
+    """The argument checks of register_movie and register_piecewise, in their order: (info, geometry(d1, d2), the fp32
+    template or None, the output dtype out_dtype_of(the movie's staged dtype), the destination or None)."""
+    info = _movie_info(movie)
+    T, d1, d2, _, np_dtype = info
+    if T < 1:
+        raise ValueError("the movie has no frames")
+    geo = geometry(d1, d2)
+    _check_counts(template_frames, template_iters)
+    _check_stream_args(frame_batch_size, bigtiff)
+    check_border(border)
+    if template is not None:
+        template = np.asarray(template)
+        if template.dtype.kind not in "iuf" or template.shape != (d1, d2):
+            raise ValueError("template must be a ({}, {}) image of numbers, got {} {}".format(d1, d2, template.dtype,
+                                                                                               template.shape))
+        template = np.ascontiguousarray(template, dtype=np.float32)
+    out_dtype = out_dtype_of(np_dtype)
+    if out is not None:
+        _check_no_alias(movie, out)
+    dest = _optional_destination(out, (T, d1, d2), out_dtype, bigtiff, device_index(None, device, ctx))
+    return info, geo, template, out_dtype, dest
+
+
+def apply_args(what, movie, out, given_of, frame_batch_size, bigtiff, border, out_dtype_of, device, ctx):
+    """The argument checks of apply_shifts and apply_field, in their order: (info, given_of(T, d1, d2), the output dtype
+    out_dtype_of(the movie's staged dtype, given), the destination)."""
+    info = _movie_info(movie)
+    T, d1, d2, _, np_dtype = info
+    if T < 1:
+        raise ValueError("the movie has no frames")
+    if d1 > MAX_DIM or d2 > MAX_DIM:
+        raise ValueError("frames of {} x {} are larger than {} pixels a side".format(d1, d2, MAX_DIM))
+    given = given_of(T, d1, d2)
+    _check_stream_args(frame_batch_size, bigtiff)
+    check_border(border)
+    out_dtype = out_dtype_of(np_dtype, given)
+    if out is None:
+        raise TypeError("{} needs a destination".format(what))
+    _check_no_alias(movie, out)
+    dest = _destination(out, (T, d1, d2), out_dtype, bigtiff, device_index(None, device, ctx))
+    return info, given, out_dtype, dest
 
 
 def register_movie(movie, out=None, *, max_shift=15, template=None, template_frames=200, template_iters=2,
@@ -562,33 +591,16 @@ def register_movie(movie, out=None, *, max_shift=15, template=None, template_fra
     movie's length (register_device_bytes is checked before anything is allocated); ``return_surfaces=True`` brings the
     (T, 2 my + 1, 2 mx + 1) surfaces to the host through a ring.  Argument errors are raised before any device work
     and before a file is created; a file this call created is removed when it fails midway.  ``out`` must not share memory with the movie."""
-    from .export import _destination
-
-    info = _movie_info(movie)
-    T, d1, d2, on_device, np_dtype = info
-    if T < 1:
-        raise ValueError("the movie has no frames")
-    my, mx = check_max_shift(max_shift, d1, d2)
-    _check_counts(template_frames, template_iters)
-    _check_stream_args(frame_batch_size, bigtiff)
-    check_border(border)
-    if template is not None:
-        template = np.asarray(template)
-        if template.dtype.kind not in "iuf" or template.shape != (d1, d2):
-            raise ValueError("template must be a ({}, {}) image of numbers, got {} {}".format(d1, d2, template.dtype,
-                                                                                               template.shape))
-        template = np.ascontiguousarray(template, dtype=np.float32)
-    out_dtype = _resolve_dtype(dtype, np_dtype, not subpixel)
-    dest = None
-    if out is not None:
-        _check_no_alias(movie, out)
-        dest = _destination(out, (T, d1, d2), out_dtype, bigtiff, _dev_index(device, ctx))
-    elif bigtiff is not None:
-        raise ValueError("bigtiff applies to a .tif / .tiff destination only")
-    est_args = dict(my=my, mx=mx, template=template, template_frames=int(template_frames),
+    info, (my, mx), template, out_dtype, dest = register_args(
+        movie, out, lambda d1, d2: check_max_shift(max_shift, d1, d2), template, template_frames, template_iters,
+        frame_batch_size, bigtiff, border, lambda src: _resolve_dtype(dtype, src, not subpixel), device, ctx)
+    _, d1, d2 = info[:3]
+    estimate = dict(my=my, mx=mx, template=template, template_frames=int(template_frames),
                     template_iters=int(template_iters), subpixel=bool(subpixel), surfaces=bool(return_surfaces))
-    found, _ = _run(movie, info, dest, out_dtype, border, est_args, None, int(frame_batch_size), num_workers, device, ctx,
-                    "register_movie")
+    found, _ = motion_pass("register_movie", movie, info, dest, out_dtype, int(frame_batch_size), num_workers, device, ctx,
+                           functools.partial(register_device_bytes, my=my, mx=mx, surfaces=bool(return_surfaces)),
+                           estimate=estimate,
+                           applier=lambda ctx, cap: _Applier(ctx, d1, d2, cap, border, _ELEM[out_dtype]))
     return Registration(found["shifts"], found["arg"], found["peak"], found["template"], (my, mx), border,
                         found.get("surfaces"))
 
@@ -600,24 +612,14 @@ def apply_shifts(movie, out, shifts, *, border="nearest", dtype=None, frame_batc
     elsewhere (of any size).  Sources, destinations, ``border`` and ``dtype`` are those of register_movie (None: the
     movie's own dtype when every shift is an integer, else float32).  The movie is read once.  Returns the path or the
     array."""
-    from .export import _destination
+    def given_of(T, d1, d2):
+        return check_shifts(shifts.shifts if isinstance(shifts, Registration) else shifts, T)
 
-    info = _movie_info(movie)
-    T, d1, d2, on_device, np_dtype = info
-    if T < 1:
-        raise ValueError("the movie has no frames")
-    if d1 > MAX_DIM or d2 > MAX_DIM:
-        raise ValueError("frames of {} x {} are larger than {} pixels a side".format(d1, d2, MAX_DIM))
-    if isinstance(shifts, Registration):
-        shifts = shifts.shifts
-    shifts = check_shifts(shifts, T)
-    _check_stream_args(frame_batch_size, bigtiff)
-    check_border(border)
-    out_dtype = _resolve_dtype(dtype, np_dtype, bool(np.all(shifts == np.floor(shifts))))
-    if out is None:
-        raise TypeError("apply_shifts needs a destination")
-    _check_no_alias(movie, out)
-    dest = _destination(out, (T, d1, d2), out_dtype, bigtiff, _dev_index(device, ctx))
-    _, res = _run(movie, info, dest, out_dtype, border, None, shifts, int(frame_batch_size), num_workers, device, ctx,
-                  "apply_shifts")
+    info, given, out_dtype, dest = apply_args(
+        "apply_shifts", movie, out, given_of, frame_batch_size, bigtiff, border,
+        lambda src, sh: _resolve_dtype(dtype, src, bool(np.all(sh == np.floor(sh)))), device, ctx)
+    _, d1, d2 = info[:3]
+    _, res = motion_pass("apply_shifts", movie, info, dest, out_dtype, int(frame_batch_size), num_workers, device, ctx,
+                         register_device_bytes, given=given,
+                         applier=lambda ctx, cap: _Applier(ctx, d1, d2, cap, border, _ELEM[out_dtype]))
     return res
