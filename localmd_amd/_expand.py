@@ -1,18 +1,26 @@
 """
 The second half of the movie-pass scaffold: one 1024-frame block of the denoised and / or residual movie, rebuilt on the
-device.  export_movie, regressor_maps (correlation), summary_images, quantile_images and the two passes of the rolling
-baseline (baseline.py) all do, per block,
+device.  export_movie, regressor_maps (correlation), summary_images, quantile_images, superpixels and the two passes of
+the rolling baseline (baseline.py) all do, per block,
 
     C = (R s) Vt[:, block]                       pmd_gemm, n_cols x 1024, leading dimension 1024
     frames = mean + std * (U C), y - that, y     pmd_group_expand (csrc/expand_fused.hip), panels side by side
 
 and differ only in where the frames go.  The Expander holds what that takes on the device; the panel code, the layout
-of a block of several panels and the device bytes are here with it.  Reading the movie, the block plan and the walk over
-a batch's blocks are the first half, _stream.  No helper knows its caller.
+of a block of several panels and the device bytes are here with it.
+
+The five consumers that turn the raw / denoised / residual movie into per-pixel state (summary_images, quantile_images,
+regressor_maps, superpixels, the knots of the rolling baseline) also share their prologue and their walk.  KindPlan is
+the host half: the shape, the block plan, the source's facts and the expand tables, built once per call before any
+device work, and ``facts(dv)``, the keywords every ``*_device_bytes`` of the five takes.  KindBlocks is the device
+half: the one Expander and the only walk, ``run(each, batch=...)``, which hands every block's raw frames in place and
+its expanded panels to the caller's kernel.  Reading the movie, the block plan and the walk over a batch's blocks are
+the first half, _stream.  No helper knows its caller.
 """
 import numpy as np
 
-from ._stream import BLOCK, VtBlocks, factor_bytes, mean_std, scaled_r, upload_f32
+from ._stream import (BLOCK, VtBlocks, block_plan, block_walk, factor_bytes, mean_std, read_batches, scaled_r,
+                      source_info, upload_f32)
 
 EXPORT_PATCH = 64       # pixels per patch of pmd_group_expand
 ENTRY_FIELDS = 4        # {a_off, p64, r, c_row0}
@@ -100,3 +108,78 @@ class Expander:
                       ptr(self.mean if mean is None else mean), ptr(self.std), self.n_patches, ptr(self.patch_ptr),
                       self.n_ent, ptr(self.entries), ptr(self.qmap), ptr(self.A), yp, int(elem), self.d1 * self.d2,
                       int(n_panels), int(code), ptr(self.block) if out is None else out, int(out_elem))
+
+
+# ---- the per-pixel consumers: one plan, one walk --------------------------------------------------------------------
+class KindPlan:
+    """The host half of a pass that turns the raw (``raw``) and / or expanded (``panels``: "denoised", "residual") movie
+    into per-pixel state; no device work.  ``T, d1, d2, D``; ``plan`` (block_plan) and ``nb``, the frames of its first
+    batch; ``on_device, esize`` (source_info of a ``movie`` that is given, else (False, 4)); ``n_cols, rank``;
+    ``reads_movie``, and ``movie``, None unless it is read; ``tabs, xt``, the tables of pmd_group_expand, built once and
+    only for panels or ``tables=True`` (None otherwise).  A decomposition of no frames has no blocks and builds no
+    tables: what that means is the caller's to say."""
+
+    def __init__(self, pmd, movie, *, raw, panels, frame_batch_size, tables=False):
+        self.T, self.d1, self.d2 = (int(x) for x in pmd.shape)
+        self.D = self.d1 * self.d2
+        self.raw, self.panels = bool(raw), tuple(panels)
+        self.reads_movie = self.raw or "residual" in self.panels
+        self.on_device, self.esize = source_info(movie, pmd.shape) if movie is not None else (False, 4)
+        self.movie = movie if self.reads_movie else None
+        self.frame_batch_size = frame_batch_size
+        self.plan = block_plan(self.T, frame_batch_size) if self.T else []
+        self.nb = self.plan[0][1] - self.plan[0][0] if self.plan else 0
+        self.n_cols, self.rank = (int(x) for x in pmd.r.shape)
+        self.tabs = self.xt = None
+        if self.T and (self.panels or tables):
+            from .export import expand_tables_for
+
+            self.tabs, self.xt = expand_tables_for(pmd)
+
+    def facts(self, dv):
+        """The keywords every ``*_device_bytes`` of the per-pixel consumers takes; ``dv``: device_context's."""
+        tabs, xt = self.tabs, self.xt
+        return dict(D=self.D, nb=self.nb, esize=self.esize, n_cols=self.n_cols, rank=self.rank,
+                    n_entries=len(xt["entries"]) if xt else 0, n_a=int(tabs["a"].size) if tabs else 0,
+                    n_patches=int(xt["n_patches"]) if xt else 0, host_source=not self.on_device,
+                    n_batches=len(self.plan), factors_on_device=dv is not None)
+
+
+class KindBlocks:
+    """The device half: the Expander of the plan's panels as ``ex`` (None when the plan built no tables; ``own_ct``: see
+    Expander) and the walk over the plan's blocks."""
+
+    def __init__(self, ctx, pmd, dv, plan, num_workers, *, own_ct=True):
+        self.ctx, self.plan, self.num_workers = ctx, plan, num_workers
+        self.P, self.code = len(plan.panels), panel_code(plan.panels)
+        self.ex = None
+        if plan.xt is not None:
+            self.ex = Expander(ctx, pmd, dv, plan.tabs, plan.xt, own_ct=own_ct, block_panels=self.P)
+
+    def run(self, each, *, batch=None, before=None, read_movie=True):
+        """One pass in frame order.  ``batch(ptr, elem, b0, n)``, when given, gets every batch of the movie whole, before
+        its blocks (no call without a movie).  For every reconstruction block the panels are expanded into ``ex.block``
+        and ``each(c0, m, yp, elem, xp)`` is called: yp the block's raw frames in place in the batch, of element type
+        elem (None, 0 without a movie), xp the expanded block (None without panels).  ``before(c0, m, yp, elem)``, when
+        given, is called ahead of the block's product and expansion: the place of a step that makes the host wait for
+        the stream (a copy from pageable memory), which there waits for the block before and not for this block's
+        expansion.  ``read_movie=False``: the same blocks, no movie."""
+        from ._lib import ptr
+
+        kp, ex, P, code = self.plan, self.ex, self.P, self.code
+        walk = block_walk(kp.plan, kp.D)
+        xp = ptr(ex.block) if P else None
+
+        def consume(frames, elem, b0, n):
+            if batch is not None and frames is not None:
+                batch(ptr(frames), elem, b0, n)
+            for c0, m, yp in walk(frames, b0):
+                if before is not None:
+                    before(c0, m, yp, elem)
+                if P:
+                    ex.coefficients(c0, m)
+                    ex.expand(m, P, code, yp, elem)
+                each(c0, m, yp, elem, xp)
+
+        read_batches(self.ctx, kp.movie if read_movie else None, [(b0, b1) for b0, b1, _ in kp.plan],
+                     kp.frame_batch_size, self.num_workers, consume)

@@ -4,11 +4,12 @@ export_movie, extract_traces, regressor_maps, summary_images, quantile_images an
 share.  The device context of a PMDArray, how a source is read (host sources through the pinned staging ring of the
 streamed decomposition, device tensors sliced in place), the 1024-frame reconstruction blocks, the walk over the
 blocks of a batch and the Vt columns of one, the uploaded statistics and R s, the host ring that results leave the
-device through, and the argument and device-memory checks the callers have in common.  Rebuilding a block of the
-denoised or residual movie from these is _expand's; where a pass that writes a movie puts its frames (destinations,
-sinks, and the scaffold that opens, finishes and aborts them, movie_pass) is _sink's, the module beside this one.  The
-movie sources, the frame-batch plan and the element types are _movie.py's, the layer below this one and below the
-decomposition driver.  No helper knows its caller.
+device through, and the argument and device-memory checks the callers have in common (check_pmd, name_tuple,
+check_fit).  Rebuilding a block of the denoised or residual movie from these is _expand's, and so are the plan and the
+one block walk of the five consumers that keep per-pixel state (KindPlan, KindBlocks); where a pass that writes a movie
+puts its frames (destinations, sinks, and the scaffold that opens, finishes and aborts them, movie_pass) is _sink's,
+the module beside this one.  The movie sources, the frame-batch plan and the element types are _movie.py's, the layer
+below this one and below the decomposition driver.  No helper knows its caller.
 """
 import contextlib
 
@@ -20,6 +21,13 @@ BLOCK = 1024            # frames per reconstruction block; blocks start on multi
 
 
 # ---- argument checks and plans (no device work) ---------------------------------------------------------------------
+def check_pmd(pmd):
+    from .pmdarray import PMDArray
+
+    if not isinstance(pmd, PMDArray):
+        raise TypeError("pmd must be a localmd_amd.PMDArray, got {}".format(type(pmd).__name__))
+
+
 def name_tuple(value, allowed, word, words):
     """``value``, one name or an iterable of distinct names from ``allowed``, as a tuple; ``word`` / ``words`` say what
     a name is in the error messages ("panel" / "panels")."""

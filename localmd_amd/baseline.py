@@ -27,10 +27,10 @@ do not fit.
 """
 import numpy as np
 
-from ._expand import Expander, expander_bytes, panel_code
+from ._expand import KindBlocks, KindPlan, expander_bytes
 from ._movie import _device_free_bytes
 from ._sink import HOST_SLOTS, _destination, check_bigtiff, device_index, movie_pass
-from ._stream import BLOCK, batch_buffer_bytes, block_plan, block_walk, device_context, read_batches, source_info
+from ._stream import BLOCK, batch_buffer_bytes, check_pmd, device_context
 
 KINDS = ("denoised", "raw")
 METHODS = ("maximin", "minimum")      # the sliding extrema
@@ -270,40 +270,16 @@ def _filter(ctx, K, half, method, q=None):
 
 
 class _Passes:
-    """What the two passes of one call share: the plan, the source, and for the denoised movie the expander with its
-    block."""
+    """The two passes of one call over the blocks of ``blocks`` (KindBlocks): a block is the expanded denoised frames in
+    fp32, or the batch's own raw frames in place."""
 
-    def __init__(self, ctx, pmd, dv, movie, kind, temporal_bin, frame_batch_size, num_workers):
-        self.ctx, self.movie, self.kind, self.bin = ctx, movie, kind, temporal_bin
-        self.fbs, self.nw = frame_batch_size, num_workers
-        self.T, d1, d2 = (int(x) for x in pmd.shape)
-        self.D = d1 * d2
-        self.plan = block_plan(self.T, frame_batch_size)
-        self.walk = block_walk(self.plan, self.D)
-        self.ex = None
-        if kind == "denoised":
-            from .export import expand_tables_for
-
-            tabs, xt = expand_tables_for(pmd)
-            self.ex = Expander(ctx, pmd, dv, tabs, xt, block_panels=1)
-            self.code = panel_code(("denoised",))
+    def __init__(self, ctx, blocks, temporal_bin):
+        self.ctx, self.blocks, self.bin = ctx, blocks, temporal_bin
+        self.T, self.D = blocks.plan.T, blocks.plan.D
 
     def run(self, each):
-        """each(X, elem, c0, m): the m frames from c0 on of every reconstruction block, fp32 from the expander or the
-        batch's own frames in place."""
-        from ._lib import ptr
-
-        def consume(batch, elem, b0, n):
-            for c0, m, yp in self.walk(batch, b0):
-                if self.ex is not None:
-                    self.ex.coefficients(c0, m)
-                    self.ex.expand(m, 1, self.code, None, 0)
-                    each(ptr(self.ex.block), 0, c0, m)
-                else:
-                    each(yp, elem, c0, m)
-
-        read_batches(self.ctx, self.movie if self.ex is None else None, [(b0, b1) for b0, b1, _ in self.plan], self.fbs,
-                     self.nw, consume)
+        """each(X, elem, c0, m): the m frames from c0 on of every reconstruction block."""
+        self.blocks.run(lambda c0, m, yp, elem, xp: each(yp, elem, c0, m) if xp is None else each(xp, 0, c0, m))
 
     def knots(self, half, method, q=None):
         """Pass 1 and the filters: the (n_bins, D) device tensor of the filtered knots."""
@@ -329,39 +305,27 @@ class _Passes:
                           lambda each: self.run(lambda X, elem, c0, m: each(c0, m, X, elem)), write)
 
 
-def _check_common(pmd, movie, kind, temporal_bin, method, q):
-    from .pmdarray import PMDArray
-
-    if not isinstance(pmd, PMDArray):
-        raise TypeError("pmd must be a localmd_amd.PMDArray, got {}".format(type(pmd).__name__))
+def _check_common(pmd, movie, kind, temporal_bin, method, q, frame_batch_size):
+    """(temporal_bin, q, KindPlan) of the checked arguments."""
+    check_pmd(pmd)
     if kind == "residual":
         raise ValueError("the residual's baseline is about 0 and dF/F of it means nothing; choose from {}".format(KINDS))
     _check_name(kind, KINDS, "kind")
     _, q = _check_method(method, q)
     b = _check_bin(temporal_bin)
-    if kind == "raw" and movie is None:
+    raw = kind == "raw"
+    if raw and movie is None:
         raise ValueError("kind 'raw' needs the movie: pass movie=")
-    on_device, esize = source_info(movie, pmd.shape) if kind == "raw" else (False, 4)
-    _check_frames(int(pmd.shape[0]), "the decomposition")
-    return b, on_device, esize, q
+    kp = KindPlan(pmd, movie if raw else None, raw=raw, panels=() if raw else ("denoised",),
+                  frame_batch_size=frame_batch_size)
+    _check_frames(kp.T, "the decomposition")
+    return b, q, kp
 
 
-def _fit(what, pmd, kind, b, esize, on_device, frame_batch_size, dv_active, host_dest, free, method, half):
+def _fit(what, kp, dv, kind, b, host_dest, free, method, half):
     """check_fit before anything is allocated on the device."""
-    T, d1, d2 = (int(x) for x in pmd.shape)
-    n_cols, rank = (int(x) for x in pmd.r.shape)
-    plan = block_plan(T, frame_batch_size)
-    n_ent = n_a = n_patches = 0
-    if kind == "denoised":
-        from .export import expand_tables_for
-
-        tabs, xt = expand_tables_for(pmd)
-        n_ent, n_a, n_patches = len(xt["entries"]), int(tabs["a"].size), int(xt["n_patches"])
-    need = baseline_device_bytes(T=T, D=d1 * d2, temporal_bin=b, nb=plan[0][1] - plan[0][0], esize=esize, kind=kind,
-                                 n_cols=n_cols, rank=rank, n_entries=n_ent, n_a=n_a, n_patches=n_patches,
-                                 host_source=not on_device, n_batches=len(plan), factors_on_device=dv_active,
-                                 host_dest=host_dest, method=method, half=half)
-    check_fit(what, need, free)
+    check_fit(what, baseline_device_bytes(**kp.facts(dv), T=kp.T, temporal_bin=b, kind=kind, host_dest=host_dest,
+                                          method=method, half=half), free)
 
 
 # ---- public entry points -------------------------------------------------------------------------------------------
@@ -394,13 +358,12 @@ def rolling_baseline(pmd, movie=None, *, kind="denoised", window, temporal_bin=1
     that does not fit raises ValueError and says to raise temporal_bin.  Argument errors are raised before any device
     work."""
     window = _check_window(window)
-    b, on_device, esize, q = _check_common(pmd, movie, kind, temporal_bin, method, q)
+    b, q, kp = _check_common(pmd, movie, kind, temporal_bin, method, q, frame_batch_size)
     half = _check_half(half_window(window, b), method)
     T, d1, d2 = (int(x) for x in pmd.shape)
     with device_context(pmd, device, ctx) as (ctx, dv):
-        _fit("rolling_baseline", pmd, kind, b, esize, on_device, frame_batch_size, dv is not None, False,
-             _device_free_bytes(ctx.device), method, half)
-        ps = _Passes(ctx, pmd, dv, movie, kind, b, frame_batch_size, num_workers)
+        _fit("rolling_baseline", kp, dv, kind, b, False, _device_free_bytes(ctx.device), method, half)
+        ps = _Passes(ctx, KindBlocks(ctx, pmd, dv, kp, num_workers), b)
         K = ps.knots(half, method, q)
         ctx.sync()
         knots = K.cpu().numpy().reshape(-1, d1, d2)
@@ -442,7 +405,7 @@ def dff_movie(pmd, out, movie=None, *, kind="denoised", output="dff", baseline=N
         if q is not None:
             raise ValueError("pass q= with window=, not with baseline=: the baseline has its own")
         temporal_bin, method, q = baseline.temporal_bin, baseline.method, baseline.q
-    b, on_device, esize, q = _check_common(pmd, movie, kind, temporal_bin, method, q)
+    b, q, kp = _check_common(pmd, movie, kind, temporal_bin, method, q, frame_batch_size)
     T, d1, d2 = (int(x) for x in pmd.shape)
     if baseline is not None:
         _check_baseline(baseline, (T, d1, d2), kind)
@@ -454,9 +417,8 @@ def dff_movie(pmd, out, movie=None, *, kind="denoised", output="dff", baseline=N
     mode = OUTPUTS.index(output)
 
     with device_context(pmd, dev_index, ctx) as (ctx, dv):
-        _fit("dff_movie", pmd, kind, b, esize, on_device, frame_batch_size, dv is not None, dest.kind != "device",
-             _device_free_bytes(ctx.device), method, half)
-        ps = _Passes(ctx, pmd, dv, movie, kind, b, frame_batch_size, num_workers)
+        _fit("dff_movie", kp, dv, kind, b, dest.kind != "device", _device_free_bytes(ctx.device), method, half)
+        ps = _Passes(ctx, KindBlocks(ctx, pmd, dv, kp, num_workers), b)
         if baseline is None:
             K = ps.knots(half, method, q)
         else:

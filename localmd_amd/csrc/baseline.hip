@@ -475,18 +475,13 @@ int pmd_bin_means(pmd_ctx* ctx, const void* Y, int elem, long ldy, int n, long N
   if (bl_bad_bin(bin)) return pmd_fail(ctx, PMD_ERR_ARG, what, "bin is not a power of two in 1 .. PMD_BASELINE_MAX_BIN");
   if (f0 < 0 || f0 % bin != 0 || f0 + n >= 0x80000000L)
     return pmd_fail(ctx, PMD_ERR_ARG, what, "f0 is negative, not a multiple of bin, or f0 + n >= 2^31");
-  if (elem != PMD_ELEM_F32 && elem != PMD_ELEM_U16 && elem != PMD_ELEM_I16)
-    return pmd_fail(ctx, PMD_ERR_ARG, what, "unknown element type");
+  if (pmd_bad_elem(elem)) return pmd_fail(ctx, PMD_ERR_ARG, what, "unknown element type");
   if (!Y || !K) return pmd_fail(ctx, PMD_ERR_ARG, what, "null pointer");
   if ((N + 255) / 256 > 0x7fffffffL) return pmd_fail(ctx, PMD_ERR_ARG, what, "too many pixels in one call");
   pmd_prof_scope prof__(ctx, "bin_means");
   float* k0 = K + f0 / bin * ldk;      // the block's first knot row
   const int shift = bl_shift(bin);
-  switch (elem) {
-    case PMD_ELEM_F32: launch_bins<float>(ctx, Y, ldy, n, N, bin, shift, k0, ldk); break;
-    case PMD_ELEM_U16: launch_bins<uint16_t>(ctx, Y, ldy, n, N, bin, shift, k0, ldk); break;
-    default: launch_bins<int16_t>(ctx, Y, ldy, n, N, bin, shift, k0, ldk); break;
-  }
+  pmd_with_elem(elem, [&](auto e) { launch_bins<typename decltype(e)::type>(ctx, Y, ldy, n, N, bin, shift, k0, ldk); });
   PMD_LAUNCH_CHECK(ctx, "bin_means_kernel");
   return PMD_OK;
 }
@@ -572,8 +567,7 @@ int pmd_baseline_apply(pmd_ctx* ctx, const void* X, int elem, long ldx, int n, l
   if (bl_bad_bin(bin)) return pmd_fail(ctx, PMD_ERR_ARG, what, "bin is not a power of two in 1 .. PMD_BASELINE_MAX_BIN");
   if (T < 1 || T >= PMD_BASELINE_MAX_FRAMES) return pmd_fail(ctx, PMD_ERR_ARG, what, "T outside 1 .. 2^23 - 1");
   if (f0 < 0 || f0 + n > T) return pmd_fail(ctx, PMD_ERR_ARG, what, "frames f0 .. f0 + n lie outside 0 .. T");
-  if (elem != PMD_ELEM_F32 && elem != PMD_ELEM_U16 && elem != PMD_ELEM_I16)
-    return pmd_fail(ctx, PMD_ERR_ARG, what, "unknown element type");
+  if (pmd_bad_elem(elem)) return pmd_fail(ctx, PMD_ERR_ARG, what, "unknown element type");
   if (!K || !out || (!X && mode != 0)) return pmd_fail(ctx, PMD_ERR_ARG, what, "null pointer");
   if ((N + 255) / 256 > 0x7fffffffL) return pmd_fail(ctx, PMD_ERR_ARG, what, "too many pixels in one call");
   pmd_prof_scope prof__(ctx, "baseline_apply");

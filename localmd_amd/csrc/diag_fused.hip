@@ -185,8 +185,7 @@ int pmd_diag_fused_accumulate(pmd_ctx* ctx, const void* Y, int elem, long ybase,
                               double* frame_ss, void* ws, size_t ws_bytes) {
   CTX_CHECK(ctx);
   const char* what = "pmd_diag_fused_accumulate";
-  if (elem != PMD_ELEM_F32 && elem != PMD_ELEM_U16 && elem != PMD_ELEM_I16)
-    return pmd_fail(ctx, PMD_ERR_ARG, what, "unknown element type");
+  if (pmd_bad_elem(elem)) return pmd_fail(ctx, PMD_ERR_ARG, what, "unknown element type");
   if (d1 < 1 || d2 < 1 || (long)d1 * d2 > 0x7fffffffL || T < 2 || lag < 1 || lag >= T)
     return pmd_fail(ctx, PMD_ERR_ARG, what, "bad shape (d1, d2 >= 1, d1 d2 < 2^31, T >= 2, 1 <= lag < T)");
   if (n < 1 || c0 < 0 || c0 % DF_FPB != 0 || c0 + n > T || ybase < 0 || ybase > c0)
@@ -202,17 +201,12 @@ int pmd_diag_fused_accumulate(pmd_ctx* ctx, const void* Y, int elem, long ybase,
   const long blocks = (n + DF_FPB - 1) / DF_FPB;
   double* partial = (double*)ws;
   double* pss = partial + blocks * DF_NM * D;
-  switch (elem) {
-    case PMD_ELEM_F32:
-      return launch<float>(ctx, (const float*)Y, ybase, W, (const float*)ring, lag, c0, n, d1, d2, mean, ref, moments, frame_ss,
-                           partial, pss);
-    case PMD_ELEM_U16:
-      return launch<uint16_t>(ctx, (const uint16_t*)Y, ybase, W, (const uint16_t*)ring, lag, c0, n, d1, d2, mean, ref, moments,
-                              frame_ss, partial, pss);
-    default:
-      return launch<int16_t>(ctx, (const int16_t*)Y, ybase, W, (const int16_t*)ring, lag, c0, n, d1, d2, mean, ref, moments,
-                             frame_ss, partial, pss);
-  }
+  int rc = PMD_OK;
+  pmd_with_elem(elem, [&](auto e) {
+    using E = typename decltype(e)::type;
+    rc = launch<E>(ctx, (const E*)Y, ybase, W, (const E*)ring, lag, c0, n, d1, d2, mean, ref, moments, frame_ss, partial, pss);
+  });
+  return rc;
 }
 
 }  // extern "C"

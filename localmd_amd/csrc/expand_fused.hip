@@ -121,26 +121,6 @@ void launch_expand(pmd_ctx* ctx, dim3 grid, const float* C, long ldc, int n, lon
                      entries, qmap, A, (const E*)Y, ldy, n_panels, panels, (O*)out, out_frame);
 }
 
-template <typename E>
-void launch_expand_out(pmd_ctx* ctx, int out_elem, dim3 grid, const float* C, long ldc, int n, long D, int d2,
-                       const float* mean, const float* std, const long* patch_ptr, const long* entries, const int* qmap,
-                       const float* A, const void* Y, long ldy, int n_panels, int panels, void* out, long out_frame) {
-  switch (out_elem) {
-    case PMD_ELEM_F32:
-      launch_expand<E, float>(ctx, grid, C, ldc, n, D, d2, mean, std, patch_ptr, entries, qmap, A, Y, ldy, n_panels, panels,
-                              out, out_frame);
-      break;
-    case PMD_ELEM_U16:
-      launch_expand<E, uint16_t>(ctx, grid, C, ldc, n, D, d2, mean, std, patch_ptr, entries, qmap, A, Y, ldy, n_panels,
-                                 panels, out, out_frame);
-      break;
-    default:
-      launch_expand<E, int16_t>(ctx, grid, C, ldc, n, D, d2, mean, std, patch_ptr, entries, qmap, A, Y, ldy, n_panels,
-                                panels, out, out_frame);
-      break;
-  }
-}
-
 }  // namespace
 
 extern "C" {
@@ -155,10 +135,8 @@ int pmd_group_expand(pmd_ctx* ctx, const float* C, long ldc, int n, int d1, int 
   if (n < 0 || d1 < 1 || d2 < 1 || n_panels < 1 || n_panels > 3 || ldc < n || n_patches != (D + EX_PX - 1) / EX_PX)
     return pmd_fail(ctx, PMD_ERR_ARG, what, "bad scalar argument (n >= 0, d1, d2 >= 1, 1..3 panels, ldc >= n, "
                                             "n_patches = ceil(D / 64))");
-  if (y_elem != PMD_ELEM_F32 && y_elem != PMD_ELEM_U16 && y_elem != PMD_ELEM_I16)
-    return pmd_fail(ctx, PMD_ERR_ARG, what, "unknown source element type");
-  if (out_elem != PMD_ELEM_F32 && out_elem != PMD_ELEM_U16 && out_elem != PMD_ELEM_I16)
-    return pmd_fail(ctx, PMD_ERR_ARG, what, "unknown output element type");
+  if (pmd_bad_elem(y_elem)) return pmd_fail(ctx, PMD_ERR_ARG, what, "unknown source element type");
+  if (pmd_bad_elem(out_elem)) return pmd_fail(ctx, PMD_ERR_ARG, what, "unknown output element type");
   bool needs_y = false;
   for (int p = 0; p < n_panels; ++p) {
     const int kind = (panels >> (2 * p)) & 3;
@@ -176,20 +154,12 @@ int pmd_group_expand(pmd_ctx* ctx, const float* C, long ldc, int n, int d1, int 
   const dim3 grid((unsigned)n_patches, (unsigned)n_fb);
   const long out_frame = D * n_panels;
   const void* y = needs_y ? Y : nullptr;
-  switch (y_elem) {
-    case PMD_ELEM_F32:
-      launch_expand_out<float>(ctx, out_elem, grid, C, ldc, n, D, d2, mean, std, patch_ptr, entries, qmap, A, y, ldy,
-                               n_panels, panels, out, out_frame);
-      break;
-    case PMD_ELEM_U16:
-      launch_expand_out<uint16_t>(ctx, out_elem, grid, C, ldc, n, D, d2, mean, std, patch_ptr, entries, qmap, A, y, ldy,
-                                  n_panels, panels, out, out_frame);
-      break;
-    default:
-      launch_expand_out<int16_t>(ctx, out_elem, grid, C, ldc, n, D, d2, mean, std, patch_ptr, entries, qmap, A, y, ldy,
-                                 n_panels, panels, out, out_frame);
-      break;
-  }
+  pmd_with_elem(y_elem, [&](auto e) {
+    pmd_with_elem(out_elem, [&](auto o) {
+      launch_expand<typename decltype(e)::type, typename decltype(o)::type>(
+          ctx, grid, C, ldc, n, D, d2, mean, std, patch_ptr, entries, qmap, A, y, ldy, n_panels, panels, out, out_frame);
+    });
+  });
   PMD_LAUNCH_CHECK(ctx, "group_expand_kernel");
   return PMD_OK;
 }

@@ -346,23 +346,13 @@ extern "C" int pmd_standardize_transpose_typed(pmd_ctx* ctx, const void* movie, 
   pmd_prof_scope prof__(ctx, "standardize_transpose");
   if (D < 1 || nf < 1 || ld < nf)
     return pmd_fail(ctx, PMD_ERR_ARG, "pmd_standardize_transpose_typed", "empty input or leading dimension too small");
+  if (pmd_bad_elem(elem)) return pmd_fail(ctx, PMD_ERR_ARG, "pmd_standardize_transpose_typed", "unknown element type");
   dim3 grid((unsigned)((D + 63) / 64), (unsigned)((ld + 63) / 64));
-  switch (elem) {
-    case PMD_ELEM_F32:
-      hipLaunchKernelGGL(standardize_transpose_kernel<float>, grid, dim3(256), 0, ctx->stream, (const float*)movie, D,
-                         frames, nf, mean, stdv, out, ld);
-      break;
-    case PMD_ELEM_U16:
-      hipLaunchKernelGGL(standardize_transpose_kernel<uint16_t>, grid, dim3(256), 0, ctx->stream, (const uint16_t*)movie,
-                         D, frames, nf, mean, stdv, out, ld);
-      break;
-    case PMD_ELEM_I16:
-      hipLaunchKernelGGL(standardize_transpose_kernel<int16_t>, grid, dim3(256), 0, ctx->stream, (const int16_t*)movie, D,
-                         frames, nf, mean, stdv, out, ld);
-      break;
-    default:
-      return pmd_fail(ctx, PMD_ERR_ARG, "pmd_standardize_transpose_typed", "unknown element type");
-  }
+  pmd_with_elem(elem, [&](auto e) {
+    using E = typename decltype(e)::type;
+    hipLaunchKernelGGL(standardize_transpose_kernel<E>, grid, dim3(256), 0, ctx->stream, (const E*)movie, D, frames, nf,
+                       mean, stdv, out, ld);
+  });
   PMD_LAUNCH_CHECK(ctx, "standardize_transpose_kernel");
   return PMD_OK;
 }
@@ -388,26 +378,16 @@ extern "C" int pmd_gather_frames(pmd_ctx* ctx, const void* src, int elem, long D
   pmd_prof_scope prof__(ctx, "gather_frames");
   if (n <= 0) return PMD_OK;
   if (D < 1) return pmd_fail(ctx, PMD_ERR_ARG, "pmd_gather_frames", "empty frame");
+  if (pmd_bad_elem(elem)) return pmd_fail(ctx, PMD_ERR_ARG, "pmd_gather_frames", "unknown element type");
   const long bx = ((D + 255) / 256 < 64) ? (D + 255) / 256 : 64;
   for (int i0 = 0; i0 < n; i0 += 65535) {
     const int in = (n - i0 < 65535) ? n - i0 : 65535;
     const dim3 grid((unsigned)bx, (unsigned)in);
-    switch (elem) {
-      case PMD_ELEM_F32:
-        hipLaunchKernelGGL(gather_frames_kernel<float>, grid, dim3(256), 0, ctx->stream, (const float*)src, D,
-                           src_rows + i0, dst_rows + i0, (float*)dst);
-        break;
-      case PMD_ELEM_U16:
-        hipLaunchKernelGGL(gather_frames_kernel<uint16_t>, grid, dim3(256), 0, ctx->stream, (const uint16_t*)src, D,
-                           src_rows + i0, dst_rows + i0, (uint16_t*)dst);
-        break;
-      case PMD_ELEM_I16:
-        hipLaunchKernelGGL(gather_frames_kernel<int16_t>, grid, dim3(256), 0, ctx->stream, (const int16_t*)src, D,
-                           src_rows + i0, dst_rows + i0, (int16_t*)dst);
-        break;
-      default:
-        return pmd_fail(ctx, PMD_ERR_ARG, "pmd_gather_frames", "unknown element type");
-    }
+    pmd_with_elem(elem, [&](auto e) {
+      using E = typename decltype(e)::type;
+      hipLaunchKernelGGL(gather_frames_kernel<E>, grid, dim3(256), 0, ctx->stream, (const E*)src, D, src_rows + i0,
+                         dst_rows + i0, (E*)dst);
+    });
     PMD_LAUNCH_CHECK(ctx, "gather_frames_kernel");
   }
   return PMD_OK;

@@ -141,8 +141,7 @@ int pmd_group_project(pmd_ctx* ctx, const void* Y, int elem, int n, long D, cons
   const char* what = "pmd_group_project";
   if (n < 0 || D < 1 || n_groups < 0 || n_wide_rows < 0 || n_partial_rows < 0 || ldz < n)
     return pmd_fail(ctx, PMD_ERR_ARG, what, "bad scalar argument (n >= 0, D >= 1, counts >= 0, ldz >= n)");
-  if (elem != PMD_ELEM_F32 && elem != PMD_ELEM_U16 && elem != PMD_ELEM_I16)
-    return pmd_fail(ctx, PMD_ERR_ARG, what, "unknown element type");
+  if (pmd_bad_elem(elem)) return pmd_fail(ctx, PMD_ERR_ARG, what, "unknown element type");
   if ((n_wide_rows > 0) != (n_partial_rows > 0))
     return pmd_fail(ctx, PMD_ERR_ARG, what, "partial rows and wide rows come together");
   if (n == 0 || n_groups == 0) return PMD_OK;
@@ -155,20 +154,11 @@ int pmd_group_project(pmd_ctx* ctx, const void* Y, int elem, int n, long D, cons
   pmd_prof_scope prof__(ctx, "group_project");
   const dim3 grid((unsigned)((long)n_groups * n_fb));
   float* wsf = (float*)ws;
-  switch (elem) {
-    case PMD_ELEM_F32:
-      hipLaunchKernelGGL(group_project_kernel<float>, grid, dim3(256), 0, ctx->stream, (const float*)Y, n, D, mean, std,
-                         groups, (int)n_fb, pix, A, Z, ldz, wsf);
-      break;
-    case PMD_ELEM_U16:
-      hipLaunchKernelGGL(group_project_kernel<uint16_t>, grid, dim3(256), 0, ctx->stream, (const uint16_t*)Y, n, D, mean,
-                         std, groups, (int)n_fb, pix, A, Z, ldz, wsf);
-      break;
-    default:
-      hipLaunchKernelGGL(group_project_kernel<int16_t>, grid, dim3(256), 0, ctx->stream, (const int16_t*)Y, n, D, mean,
-                         std, groups, (int)n_fb, pix, A, Z, ldz, wsf);
-      break;
-  }
+  pmd_with_elem(elem, [&](auto e) {
+    using E = typename decltype(e)::type;
+    hipLaunchKernelGGL(group_project_kernel<E>, grid, dim3(256), 0, ctx->stream, (const E*)Y, n, D, mean, std, groups,
+                       (int)n_fb, pix, A, Z, ldz, wsf);
+  });
   PMD_LAUNCH_CHECK(ctx, "group_project_kernel");
   if (n_wide_rows > 0) {
     for (int r0 = 0; r0 < n_wide_rows; r0 += 65535) {

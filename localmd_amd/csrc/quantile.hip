@@ -158,28 +158,17 @@ int pmd_pixel_hist_accumulate(pmd_ctx* ctx, const void* Y, int elem, long ldy, l
   if (n < 1 || n >= 0x80000000L) return pmd_fail(ctx, PMD_ERR_ARG, what, "n outside 1 .. 2^31 - 1");
   if (D < 1 || ldy < D) return pmd_fail(ctx, PMD_ERR_ARG, what, "bad scalar argument (D >= 1, ldy >= D)");
   if (pass < 0 || pass > 3) return pmd_fail(ctx, PMD_ERR_ARG, what, "pass outside 0 .. 3");
-  if (elem != PMD_ELEM_F32 && elem != PMD_ELEM_U16 && elem != PMD_ELEM_I16)
-    return pmd_fail(ctx, PMD_ERR_ARG, what, "unknown element type");
+  if (pmd_bad_elem(elem)) return pmd_fail(ctx, PMD_ERR_ARG, what, "unknown element type");
   if (!Y || !hist) return pmd_fail(ctx, PMD_ERR_ARG, what, "null pointer");
   if (pass > 0 && !prefix) return pmd_fail(ctx, PMD_ERR_ARG, what, "a pass after the first needs prefix");
   if ((uintptr_t)hist % 16 != 0) return pmd_fail(ctx, PMD_ERR_ARG, what, "hist is not 16-byte aligned");
   if ((D + HQ_GROUP - 1) / HQ_GROUP > 0x7fffffffL) return pmd_fail(ctx, PMD_ERR_ARG, what, "too many pixels in one call");
   pmd_prof_scope prof__(ctx, "pixel_hist_accumulate");
   const dim3 grid((unsigned)((D + HQ_GROUP - 1) / HQ_GROUP)), block(64 * HQ_WAVES);
-  switch (elem) {
-    case PMD_ELEM_F32:
-      hipLaunchKernelGGL(hist_kernel<float>, grid, block, 0, ctx->stream, (const float*)Y, ldy, n, D, centre, pass, prefix,
-                         hist);
-      break;
-    case PMD_ELEM_U16:
-      hipLaunchKernelGGL(hist_kernel<uint16_t>, grid, block, 0, ctx->stream, (const uint16_t*)Y, ldy, n, D, centre, pass,
-                         prefix, hist);
-      break;
-    default:
-      hipLaunchKernelGGL(hist_kernel<int16_t>, grid, block, 0, ctx->stream, (const int16_t*)Y, ldy, n, D, centre, pass,
-                         prefix, hist);
-      break;
-  }
+  pmd_with_elem(elem, [&](auto e) {
+    using E = typename decltype(e)::type;
+    hipLaunchKernelGGL(hist_kernel<E>, grid, block, 0, ctx->stream, (const E*)Y, ldy, n, D, centre, pass, prefix, hist);
+  });
   PMD_LAUNCH_CHECK(ctx, "hist_kernel");
   return PMD_OK;
 }

@@ -175,8 +175,7 @@ int pmd_regress_accumulate(pmd_ctx* ctx, const void* Y, int elem, long ldy, int 
   if (n < 0 || D < 1 || K < 0 || ldy < D || (K > 0 && (ldx < n || lda < D)))
     return pmd_fail(ctx, PMD_ERR_ARG, what, "bad scalar argument (n, K >= 0, D >= 1, ldy, lda >= D, ldx >= n)");
   if (n > PMD_REGRESS_BLOCK) return pmd_fail(ctx, PMD_ERR_ARG, what, "n > PMD_REGRESS_BLOCK frames in one call");
-  if (elem != PMD_ELEM_F32 && elem != PMD_ELEM_U16 && elem != PMD_ELEM_I16)
-    return pmd_fail(ctx, PMD_ERR_ARG, what, "unknown element type");
+  if (pmd_bad_elem(elem)) return pmd_fail(ctx, PMD_ERR_ARG, what, "unknown element type");
   if (n == 0 || (K == 0 && !mom)) return PMD_OK;
   if (!Y || (K > 0 && (!X || !acc))) return pmd_fail(ctx, PMD_ERR_ARG, what, "null pointer");
   const long n_wg = (D + RG_WG - 1) / RG_WG;
@@ -190,11 +189,9 @@ int pmd_regress_accumulate(pmd_ctx* ctx, const void* Y, int elem, long ldy, int 
     const float* x = X ? X + (long)k0 * ldx : nullptr;
     double* a = acc ? acc + (long)k0 * lda : nullptr;
     double* m = k0 == 0 ? mom : nullptr;
-    switch (elem) {
-      case PMD_ELEM_F32: launch_e<float>(ctx, grid, Y, ldy, n, D, mean, x, ldx, kn, a, lda, m); break;
-      case PMD_ELEM_U16: launch_e<uint16_t>(ctx, grid, Y, ldy, n, D, mean, x, ldx, kn, a, lda, m); break;
-      default: launch_e<int16_t>(ctx, grid, Y, ldy, n, D, mean, x, ldx, kn, a, lda, m); break;
-    }
+    pmd_with_elem(elem, [&](auto e) {
+      launch_e<typename decltype(e)::type>(ctx, grid, Y, ldy, n, D, mean, x, ldx, kn, a, lda, m);
+    });
     k0 += KL;
   } while (k0 < K);
   PMD_LAUNCH_CHECK(ctx, "regress_kernel");

@@ -133,8 +133,7 @@ int pmd_roi_gather(pmd_ctx* ctx, const void* Y, int elem, int n, long D, long n_
   const char* what = "pmd_roi_gather";
   if (n < 0 || D < 1 || n_segs < 0 || n_split < 0 || n_partial_rows < 0 || ldo < n)
     return pmd_fail(ctx, PMD_ERR_ARG, what, "bad scalar argument (n >= 0, D >= 1, counts >= 0, ldo >= n)");
-  if (elem != PMD_ELEM_F32 && elem != PMD_ELEM_U16 && elem != PMD_ELEM_I16)
-    return pmd_fail(ctx, PMD_ERR_ARG, what, "unknown element type");
+  if (pmd_bad_elem(elem)) return pmd_fail(ctx, PMD_ERR_ARG, what, "unknown element type");
   if ((n_split > 0) != (n_partial_rows > 0))
     return pmd_fail(ctx, PMD_ERR_ARG, what, "partial rows and split ROIs come together");
   if (n == 0 || n_segs == 0) return PMD_OK;
@@ -146,20 +145,11 @@ int pmd_roi_gather(pmd_ctx* ctx, const void* Y, int elem, int n, long D, long n_
   pmd_prof_scope prof__(ctx, "roi_gather");
   const dim3 grid((unsigned)(n_segs * n_fb));
   float* wsf = (float*)ws;
-  switch (elem) {
-    case PMD_ELEM_F32:
-      hipLaunchKernelGGL(roi_gather_kernel<float>, grid, dim3(256), 0, ctx->stream, (const float*)Y, n, D, segs, (int)n_fb,
-                         pix, w, out, ldo, wsf);
-      break;
-    case PMD_ELEM_U16:
-      hipLaunchKernelGGL(roi_gather_kernel<uint16_t>, grid, dim3(256), 0, ctx->stream, (const uint16_t*)Y, n, D, segs,
-                         (int)n_fb, pix, w, out, ldo, wsf);
-      break;
-    default:
-      hipLaunchKernelGGL(roi_gather_kernel<int16_t>, grid, dim3(256), 0, ctx->stream, (const int16_t*)Y, n, D, segs,
-                         (int)n_fb, pix, w, out, ldo, wsf);
-      break;
-  }
+  pmd_with_elem(elem, [&](auto e) {
+    using E = typename decltype(e)::type;
+    hipLaunchKernelGGL(roi_gather_kernel<E>, grid, dim3(256), 0, ctx->stream, (const E*)Y, n, D, segs, (int)n_fb, pix, w,
+                       out, ldo, wsf);
+  });
   PMD_LAUNCH_CHECK(ctx, "roi_gather_kernel");
   if (n_split > 0) {
     for (int r0 = 0; r0 < n_split; r0 += 65535) {

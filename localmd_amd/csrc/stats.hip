@@ -244,18 +244,15 @@ int pmd_pixel_stats_accumulate(pmd_ctx* ctx, const void* Y, int elem, long ldy, 
     return pmd_fail(ctx, PMD_ERR_ARG, what, "bin is not a power of two in 1 .. PMD_STATS_BLOCK");
   if (f0 < 0 || f0 % bin != 0 || f0 + n >= 0x80000000L)
     return pmd_fail(ctx, PMD_ERR_ARG, what, "f0 is negative, not a multiple of bin, or f0 + n >= 2^31");
-  if (elem != PMD_ELEM_F32 && elem != PMD_ELEM_U16 && elem != PMD_ELEM_I16)
-    return pmd_fail(ctx, PMD_ERR_ARG, what, "unknown element type");
+  if (pmd_bad_elem(elem)) return pmd_fail(ctx, PMD_ERR_ARG, what, "unknown element type");
   if (!ext && !mom) return pmd_fail(ctx, PMD_ERR_ARG, what, "ext and mom are both NULL");
   if (arg && !ext) return pmd_fail(ctx, PMD_ERR_ARG, what, "arg without ext");
   if (!Y) return pmd_fail(ctx, PMD_ERR_ARG, what, "null pointer");
   if ((D + 255) / 256 > 0x7fffffffL) return pmd_fail(ctx, PMD_ERR_ARG, what, "too many pixels in one call");
   pmd_prof_scope prof__(ctx, "pixel_stats_accumulate");
-  switch (elem) {
-    case PMD_ELEM_F32: launch_e<float>(ctx, Y, ldy, n, D, (int)f0, bin, centre, ext, arg, mom); break;
-    case PMD_ELEM_U16: launch_e<uint16_t>(ctx, Y, ldy, n, D, (int)f0, bin, centre, ext, arg, mom); break;
-    default: launch_e<int16_t>(ctx, Y, ldy, n, D, (int)f0, bin, centre, ext, arg, mom); break;
-  }
+  pmd_with_elem(elem, [&](auto e) {
+    launch_e<typename decltype(e)::type>(ctx, Y, ldy, n, D, (int)f0, bin, centre, ext, arg, mom);
+  });
   PMD_LAUNCH_CHECK(ctx, "stats_kernel");
   return PMD_OK;
 }

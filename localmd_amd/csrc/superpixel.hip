@@ -249,16 +249,11 @@ int pmd_threshold_moments_accumulate(pmd_ctx* ctx, const void* Y, int elem, long
   const char* what = "pmd_threshold_moments_accumulate";
   if (n < 1 || d1 < 1 || d2 < 1) return pmd_fail(ctx, PMD_ERR_ARG, what, "bad scalar argument (n >= 1, d1 >= 1, d2 >= 1)");
   if (ldy < (long)d1 * d2) return pmd_fail(ctx, PMD_ERR_ARG, what, "ldy < d1 * d2");
-  if (elem != PMD_ELEM_F32 && elem != PMD_ELEM_U16 && elem != PMD_ELEM_I16)
-    return pmd_fail(ctx, PMD_ERR_ARG, what, "unknown element type");
+  if (pmd_bad_elem(elem)) return pmd_fail(ctx, PMD_ERR_ARG, what, "unknown element type");
   if (!Y || !thr || !mom) return pmd_fail(ctx, PMD_ERR_ARG, what, "null pointer");
   if ((d2 + TM_COLS - 1) / TM_COLS > 65535) return pmd_fail(ctx, PMD_ERR_ARG, what, "too many columns in one call");
   pmd_prof_scope prof__(ctx, "threshold_moments_accumulate");
-  switch (elem) {
-    case PMD_ELEM_F32: launch_moments<float>(ctx, Y, ldy, n, d1, d2, thr, mom); break;
-    case PMD_ELEM_U16: launch_moments<uint16_t>(ctx, Y, ldy, n, d1, d2, thr, mom); break;
-    default: launch_moments<int16_t>(ctx, Y, ldy, n, d1, d2, thr, mom); break;
-  }
+  pmd_with_elem(elem, [&](auto e) { launch_moments<typename decltype(e)::type>(ctx, Y, ldy, n, d1, d2, thr, mom); });
   PMD_LAUNCH_CHECK(ctx, "threshold_moments_kernel");
   return PMD_OK;
 }

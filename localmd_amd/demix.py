@@ -38,7 +38,8 @@ import numpy as np
 import scipy.sparse
 
 from ._movie import _device_free_bytes
-from ._stream import BLOCK, VtBlocks, check_fit, device_context, factor_bytes, scaled_r, upload_f32
+from ._stream import (BLOCK, VtBlocks, check_fit, check_pmd, device_context, factor_bytes, scaled_r,
+                      upload_f32)
 from .traces import denoised_factors, roi_weights
 
 MAX_COVER = 64        # PMD_HALS_MAX_COVER: ROIs covering one pixel (one lane each)
@@ -160,10 +161,7 @@ def demix(pmd, rois, *, outer_iters=3, sweeps=5, update_footprints=True, nonneg_
     After ``pmd.to_device()`` its context and uploaded factors are reused; every output bit is the same either way.
     Device memory grows with the movie's length as 8 K T bytes (demix_device_bytes); a plan that does not fit raises
     ValueError.  Argument errors are raised before any device work."""
-    from .pmdarray import PMDArray
-
-    if not isinstance(pmd, PMDArray):
-        raise TypeError("pmd must be a localmd_amd.PMDArray, got {}".format(type(pmd).__name__))
+    check_pmd(pmd)
     outer_iters = _check_count(outer_iters, "outer_iters")
     sweeps = _check_count(sweeps, "sweeps")
     T, d1, d2 = (int(x) for x in pmd.shape)

@@ -18,8 +18,8 @@ import numpy as np
 
 from ._lib import Context, ptr
 from ._movie import _device_free_bytes, _stream_batch_frames
-from ._stream import (batch_buffer_bytes, block_plan, check_fit, device_context, mean_std, read_batches, scaled_r,
-                      source_info, upload_f32)
+from ._stream import (batch_buffer_bytes, block_plan, check_fit, check_pmd, device_context, mean_std, read_batches,
+                      scaled_r, source_info, upload_f32)
 
 CHUNK_BYTES = 1 << 30
 
@@ -205,10 +205,7 @@ def _check_fit(need, ring, free, lag):
 
 
 def _check_args(original_movie, pmd, mode, lag):
-    from .pmdarray import PMDArray
-
-    if not isinstance(pmd, PMDArray):
-        raise TypeError("pmd must be a localmd_amd.PMDArray, got {}".format(type(pmd).__name__))
+    check_pmd(pmd)
     shape = tuple(int(x) for x in pmd.shape)
     on_device, esize = source_info(original_movie, shape)
     if mode not in ("max", "mean"):

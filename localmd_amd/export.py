@@ -26,7 +26,7 @@ from ._expand import ENTRY_FIELDS, EXPORT_PATCH, _PANEL_CODE, Expander, expander
 from ._movie import _ELEM, _device_free_bytes
 from ._sink import HOST_SLOTS, _destination, check_bigtiff, device_index, movie_pass  # noqa: F401
 from ._stream import BLOCK as EXPORT_BLOCK, block_plan as export_plan
-from ._stream import batch_buffer_bytes, check_fit, device_context, each_block, name_tuple, source_info
+from ._stream import batch_buffer_bytes, check_fit, check_pmd, device_context, each_block, name_tuple, source_info
 from .projection import MAX_ROWS, P_MAX, ROW_PAD, _pad, tables_for
 
 PANELS = ("raw", "denoised", "residual")
@@ -149,10 +149,7 @@ def export_movie(pmd, out, movie=None, *, panels="denoised", dtype="float32", fr
     "uint16" or "int16" (round half to even, saturating, NaN -> 0: quantize).  After ``pmd.to_device()`` its context
     and uploaded factors are reused.  Argument errors are raised before any device work and before a file is created;
     a file this call created is removed when it fails midway."""
-    from .pmdarray import PMDArray
-
-    if not isinstance(pmd, PMDArray):
-        raise TypeError("pmd must be a localmd_amd.PMDArray, got {}".format(type(pmd).__name__))
+    check_pmd(pmd)
     panels = name_tuple(panels, PANELS, "panel", "panels")
     out_dtype = _out_dtype(dtype)
     check_bigtiff(bigtiff)

@@ -21,10 +21,9 @@ source.  The movie is read once through the scaffold of _stream; device memory d
 """
 import numpy as np
 
-from ._expand import Expander, expander_bytes, interleave, panel_code, split_panels
+from ._expand import KindBlocks, KindPlan, expander_bytes, interleave, panel_code, split_panels
 from ._movie import _device_free_bytes
-from ._stream import (BLOCK, batch_buffer_bytes, block_plan, block_walk, check_fit, device_context, name_tuple,
-                      read_batches, source_info, upload_f32)
+from ._stream import BLOCK, batch_buffer_bytes, check_fit, check_pmd, device_context, name_tuple, upload_f32
 
 KINDS = ("denoised", "raw", "residual")
 STATS = ("sum", "mean", "correlation")
@@ -157,16 +156,11 @@ def regressor_maps(pmd, regressors, movie=None, *, kinds="denoised", stat="sum",
     device tensors (sliced in place).  After ``pmd.to_device()`` its context and uploaded factors are reused.  Every
     map has the same bits for every frame_batch_size and source.  Argument errors are raised before any device work
     and before the movie is read."""
-    from .export import expand_tables_for
-    from .pmdarray import PMDArray
-
-    if not isinstance(pmd, PMDArray):
-        raise TypeError("pmd must be a localmd_amd.PMDArray, got {}".format(type(pmd).__name__))
+    check_pmd(pmd)
     kinds = name_tuple(kinds, KINDS, "kind", "kinds")
     if not isinstance(stat, str) or stat not in STATS:
         raise ValueError("unknown stat {!r}; choose from {}".format(stat, STATS))
     T, d1, d2 = (int(x) for x in pmd.shape)
-    D = d1 * d2
     x64 = prepare_regressors(regressors, T)
     K = x64.shape[0]
     if stat == "mean":
@@ -177,40 +171,29 @@ def regressor_maps(pmd, regressors, movie=None, *, kinds="denoised", stat="sum",
     movie_required = corr or kinds != ("denoised",)
     if movie_required and movie is None:
         raise ValueError("kinds {} with stat {!r} need the movie: pass movie=".format(kinds, stat))
-    on_device, esize = source_info(movie, pmd.shape) if movie is not None else (False, 4)
-    if T == 0:
-        return Maps(**{k: np.zeros((K, d1, d2), dtype=np.float32) for k in kinds})
     # what runs: the raw accumulation, the expanded panels (correlation only), the denoised sums from the factors
     do_raw = "raw" in kinds or (not corr and "residual" in kinds)
     panels = tuple(k for k in ("denoised", "residual") if k in kinds) if corr else ()
     factor_sums = not corr and ("denoised" in kinds or "residual" in kinds)
-    reads_movie = do_raw or "residual" in panels
-    plan = block_plan(T, frame_batch_size)
-    nb = plan[0][1] - plan[0][0]
-    n_cols, rank = (int(x) for x in pmd.r.shape)
-    tabs = xt = None
-    if panels or factor_sums:
-        tabs, xt = expand_tables_for(pmd)
+    kp = KindPlan(pmd, movie, raw=do_raw, panels=panels, frame_batch_size=frame_batch_size, tables=factor_sums)
+    if T == 0:
+        return Maps(**{k: np.zeros((K, d1, d2), dtype=np.float32) for k in kinds})
 
     with device_context(pmd, device, ctx) as (ctx, dv):
-        need = maps_device_bytes(D=D, nb=nb, esize=esize, K=K, n_acc=int(do_raw) + len(panels), n_expand=len(panels),
-                                 n_cols=n_cols, rank=rank, n_entries=len(xt["entries"]) if xt else 0,
-                                 n_a=int(tabs["a"].size) if tabs else 0, n_patches=int(xt["n_patches"]) if xt else 0,
-                                 needs_movie=reads_movie, host_source=not on_device, n_batches=len(plan),
-                                 factors_on_device=dv is not None, factor_sums=factor_sums)
+        need = maps_device_bytes(**kp.facts(dv), K=K, n_acc=int(do_raw) + len(panels), n_expand=len(panels),
+                                 needs_movie=kp.reads_movie, factor_sums=factor_sums)
         check_fit("regressor_maps", need, _device_free_bytes(ctx.device))
-        out = _maps(ctx, pmd, dv, tabs, xt, x64, movie if reads_movie else None, plan, kinds, stat, do_raw, panels,
-                    factor_sums, frame_batch_size, num_workers)
+        out = _maps(ctx, pmd, KindBlocks(ctx, pmd, dv, kp, num_workers, own_ct=bool(panels)), x64, kinds, stat,
+                    factor_sums)
     return Maps(**{k: out[k].reshape(K, d1, d2) for k in kinds})
 
 
-def _maps(ctx, pmd, dv, tabs, xt, x64, movie, plan, kinds, stat, do_raw, panels, factor_sums, frame_batch_size,
-          num_workers):
+def _maps(ctx, pmd, blocks, x64, kinds, stat, factor_sums):
     import torch
     from ._lib import ptr
 
-    T, d1, d2 = (int(x) for x in pmd.shape)
-    D = d1 * d2
+    kp, ex = blocks.plan, blocks.ex
+    T, d1, d2, D, do_raw, panels = kp.T, kp.d1, kp.d2, kp.D, kp.raw, kp.panels
     dev = ctx.device
     K = x64.shape[0]
     corr = stat == "correlation"
@@ -225,8 +208,6 @@ def _maps(ctx, pmd, dv, tabs, xt, x64, movie, plan, kinds, stat, do_raw, panels,
 
     acc_raw = torch.zeros((K, D), dtype=torch.float64, device=dev) if do_raw else None
     mom_raw = torch.zeros(2 * D, dtype=torch.float64, device=dev) if do_raw and corr else None
-    ex = Expander(ctx, pmd, dv, tabs, xt, own_ct=bool(P), block_panels=P) if (P or factor_sums) else None
-    code = panel_code(panels)
     if P:
         # the kernel takes the expanded block as a batch of P D "pixels" whose centring vector is the mean image under
         # the denoised panel and 0 under the residual panel
@@ -237,26 +218,24 @@ def _maps(ctx, pmd, dv, tabs, xt, x64, movie, plan, kinds, stat, do_raw, panels,
     if factor_sums and ex.product:
         g64 = torch.zeros((ex.rank, K), dtype=torch.float64, device=dev)
         gb = torch.empty((ex.rank, K), dtype=torch.float32, device=dev)
-    walk = block_walk(plan, D)
 
-    def consume(batch, elem, b0, n):
-        for c0, m, yp in walk(batch, b0):
-            xb[:, :m].copy_(x_host[:, c0:c0 + m])         # a blocking copy from pageable memory, once per block
-            if do_raw:
-                ctx.call("pmd_regress_accumulate", yp, int(elem), D, m, D, ptr(centre), ptr(xb), BLOCK, K, ptr(acc_raw),
-                         D, ptr(mom_raw))
-            if P:
-                ex.coefficients(c0, m)
-                ex.expand(m, P, code, yp, elem)
-                ctx.call("pmd_regress_accumulate", ptr(ex.block), 0, P * D, m, P * D, ptr(shift), ptr(xb), BLOCK, K,
-                         ptr(acc_ex), P * D, ptr(mom_ex))
-            if factor_sums and ex.product:
-                # G += Vt[:, block] X[:, block]^T: every block product has the same shape; fp64 across the blocks
-                ex.vt.load(c0, m)
-                ctx.call("pmd_gemm", 0, 1, ex.rank, K, m, 1.0, ptr(ex.vt.buf), BLOCK, ptr(xb), BLOCK, 0.0, ptr(gb), K)
-                g64.add_(gb)
+    def before(c0, m, yp, elem):
+        xb[:, :m].copy_(x_host[:, c0:c0 + m])             # a blocking copy from pageable memory, once per block
+        if do_raw:
+            ctx.call("pmd_regress_accumulate", yp, int(elem), D, m, D, ptr(centre), ptr(xb), BLOCK, K, ptr(acc_raw), D,
+                     ptr(mom_raw))
 
-    read_batches(ctx, movie, [(b0, b1) for b0, b1, _ in plan], frame_batch_size, num_workers, consume)
+    def each(c0, m, yp, elem, xp):
+        if P:
+            ctx.call("pmd_regress_accumulate", xp, 0, P * D, m, P * D, ptr(shift), ptr(xb), BLOCK, K, ptr(acc_ex), P * D,
+                     ptr(mom_ex))
+        if factor_sums and ex.product:
+            # G += Vt[:, block] X[:, block]^T: every block product has the same shape; fp64 across the blocks
+            ex.vt.load(c0, m)
+            ctx.call("pmd_gemm", 0, 1, ex.rank, K, m, 1.0, ptr(ex.vt.buf), BLOCK, ptr(xb), BLOCK, 0.0, ptr(gb), K)
+            g64.add_(gb)
+
+    blocks.run(each, before=before)
 
     den_img = None
     if factor_sums:

@@ -22,10 +22,9 @@ The device only counts integers, so every output bit is the same for every batch
 """
 import numpy as np
 
-from ._expand import Expander, expander_bytes, interleave, panel_code, split_panels
+from ._expand import KindBlocks, KindPlan, expander_bytes, interleave, split_panels
 from ._movie import _device_free_bytes
-from ._stream import (batch_buffer_bytes, block_plan, block_walk, check_fit, device_context, name_tuple,
-                      read_batches, source_info, upload_f32)
+from ._stream import batch_buffer_bytes, check_fit, check_pmd, device_context, name_tuple, upload_f32
 from .maps import KINDS
 
 INTERPOLATIONS = ("linear", "lower", "higher", "nearest")
@@ -162,11 +161,7 @@ def quantile_images(pmd, movie=None, *, kinds="denoised", q=0.5, mad=False, inte
     for every order and subset of kinds and q.  Argument errors are raised before any device work and before the movie
     is read; a decomposition of no frames has no order statistics and raises ValueError.  A plan that does not fit the
     free device memory raises ValueError (1 KB per pixel, kind and distinct rank)."""
-    from .export import expand_tables_for
-    from .pmdarray import PMDArray
-
-    if not isinstance(pmd, PMDArray):
-        raise TypeError("pmd must be a localmd_amd.PMDArray, got {}".format(type(pmd).__name__))
+    check_pmd(pmd)
     kinds = name_tuple(kinds, KINDS, "kind", "kinds")
     q = check_q(q)
     if not isinstance(interpolation, str) or interpolation not in INTERPOLATIONS:
@@ -174,11 +169,11 @@ def quantile_images(pmd, movie=None, *, kinds="denoised", q=0.5, mad=False, inte
     if not isinstance(mad, (bool, np.bool_)):
         raise ValueError("mad must be True or False, got {!r}".format(mad))
     mad = bool(mad)
-    T, d1, d2 = (int(x) for x in pmd.shape)
-    D = d1 * d2
     if kinds != ("denoised",) and movie is None:
         raise ValueError("kinds {} need the movie: pass movie=".format(kinds))
-    on_device, esize = source_info(movie, pmd.shape) if movie is not None else (False, 4)
+    kp = KindPlan(pmd, movie, raw="raw" in kinds, panels=tuple(k for k in ("denoised", "residual") if k in kinds),
+                  frame_batch_size=frame_batch_size)
+    T, d1, d2 = kp.T, kp.d1, kp.d2
     if T == 0:
         raise ValueError("the decomposition has no frames: their order statistics do not exist")
     if T >= 2 ** 31:
@@ -186,25 +181,12 @@ def quantile_images(pmd, movie=None, *, kinds="denoised", q=0.5, mad=False, inte
     need = _needed(q, T, interpolation)
     median = _needed((0.5,), T, "linear")[0]
     ranks = sorted({r for lo, hi, _ in need + ([median] if mad else []) for r in (lo, hi)})
-    do_raw = "raw" in kinds
-    panels = tuple(k for k in ("denoised", "residual") if k in kinds)
-    reads_movie = do_raw or "residual" in panels
-    plan = block_plan(T, frame_batch_size)
-    nb = plan[0][1] - plan[0][0]
-    n_cols, rank = (int(x) for x in pmd.r.shape)
-    tabs = xt = None
-    if panels:
-        tabs, xt = expand_tables_for(pmd)
 
     with device_context(pmd, device, ctx) as (ctx, dv):
-        nbytes = quantile_device_bytes(D=D, nb=nb, esize=esize, n_raw=int(do_raw), n_expand=len(panels), n_pos=len(ranks),
-                                       centred=mad, n_cols=n_cols, rank=rank, n_entries=len(xt["entries"]) if xt else 0,
-                                       n_a=int(tabs["a"].size) if tabs else 0,
-                                       n_patches=int(xt["n_patches"]) if xt else 0, needs_movie=reads_movie,
-                                       host_source=not on_device, n_batches=len(plan), factors_on_device=dv is not None)
+        nbytes = quantile_device_bytes(**kp.facts(dv), n_raw=int(kp.raw), n_expand=len(kp.panels), n_pos=len(ranks),
+                                       centred=mad, needs_movie=kp.reads_movie)
         check_fit("quantile_images", nbytes, _device_free_bytes(ctx.device))
-        run = _Rounds(ctx, pmd, dv, tabs, xt, movie if reads_movie else None, plan, do_raw, panels,
-                      reads_movie and esize == 2, frame_batch_size, num_workers)
+        run = _Rounds(ctx, KindBlocks(ctx, pmd, dv, kp, num_workers), kp.reads_movie and kp.esize == 2)
         stat = run.select(ranks, None)                               # kind -> (len(ranks), D) float32
         at = {r: i for i, r in enumerate(ranks)}
         out = {k: np.stack([finish_linear(stat[k][at[lo]], stat[k][at[hi]], frac) if hi != lo else stat[k][at[lo]]
@@ -260,48 +242,39 @@ class _Select:
 
 
 class _Rounds:
-    """What the selection rounds of one quantile_images call share: the expander with its block, the plan."""
+    """The selection rounds of one quantile_images call, over the blocks of ``blocks`` (KindBlocks); ``sixteen``: the
+    movie is read as 16-bit integers."""
 
-    def __init__(self, ctx, pmd, dv, tabs, xt, movie, plan, do_raw, panels, sixteen, frame_batch_size, num_workers):
-        self.ctx, self.pmd, self.movie, self.plan = ctx, pmd, movie, plan
-        self.do_raw, self.panels, self.sixteen = do_raw, panels, sixteen
-        self.fbs, self.nw = frame_batch_size, num_workers
-        _, self.d1, self.d2 = (int(x) for x in pmd.shape)
-        self.D, self.P = self.d1 * self.d2, len(panels)
-        # the histogram kernel takes the expanded block as a batch of P D "pixels"
-        self.ex = Expander(ctx, pmd, dv, tabs, xt, block_panels=self.P) if self.P else None
+    def __init__(self, ctx, blocks, sixteen):
+        self.ctx, self.blocks, self.sixteen = ctx, blocks, sixteen
 
     def select(self, ranks, centres):
         """{kind: (len(ranks), D) float32}: the order statistics ``ranks`` of every kind, of |y - centres[kind]| when
         ``centres`` is given."""
-        from ._lib import ptr
-
-        ctx, D, P, d1, d2, panels, ex = self.ctx, self.D, self.P, self.d1, self.d2, self.panels, self.ex
-        code = panel_code(panels)
+        ctx, kp = self.ctx, self.blocks.plan
+        D, d1, d2, panels = kp.D, kp.d1, kp.d2, kp.panels
+        P = len(panels)
         raw = expanded = None
         raw_passes = 3 if self.sixteen and centres is None else 4
-        if self.do_raw:
+        if kp.raw:
             raw = _Select(ctx, D, ranks, None if centres is None else centres["raw"])
         if P:
+            # the histogram kernel takes the expanded block as a batch of P D "pixels"
             shift = None if centres is None else interleave([centres[k] for k in panels], d1, d2)
             expanded = _Select(ctx, P * D, ranks, shift)
-        walk = block_walk(self.plan, D)
 
         for p in range(4 if P else raw_passes):
-            def consume(batch, elem, b0, n):
-                if raw is not None and p < raw_passes:
-                    raw.accumulate(ctx, ptr(batch), elem, n, p)      # the whole batch in one call
-                if not P:
-                    return
-                for c0, m, yp in walk(batch, b0):
-                    ex.coefficients(c0, m)
-                    ex.expand(m, P, code, yp, elem)
-                    expanded.accumulate(ctx, ptr(ex.block), 0, m, p)
+            def whole(Y, elem, b0, n):
+                raw.accumulate(ctx, Y, elem, n, p)                   # the whole batch in one call
+
+            def each(c0, m, yp, elem, xp):
+                if P:
+                    expanded.accumulate(ctx, xp, 0, m, p)
 
             # a pass that only the denoised panel still needs reads no movie
-            movie = self.movie if (raw is not None and p < raw_passes) or "residual" in panels else None
-            read_batches(ctx, movie, [(b0, b1) for b0, b1, _ in self.plan], self.fbs, self.nw, consume)
-            if raw is not None and p < raw_passes:
+            do_raw = raw is not None and p < raw_passes
+            self.blocks.run(each, batch=whole if do_raw else None, read_movie=do_raw or "residual" in panels)
+            if do_raw:
                 raw.select(ctx, p)
             if expanded is not None:
                 expanded.select(ctx, p)

@@ -19,10 +19,9 @@ source.  The movie is read once through the scaffold of _stream; device memory d
 """
 import numpy as np
 
-from ._expand import Expander, expander_bytes, interleave, panel_code, split_panels
+from ._expand import KindBlocks, KindPlan, expander_bytes, interleave, split_panels
 from ._movie import _device_free_bytes
-from ._stream import (batch_buffer_bytes, block_plan, block_walk, check_fit, device_context, name_tuple,
-                      read_batches, source_info, upload_f32)
+from ._stream import batch_buffer_bytes, check_fit, check_pmd, device_context, name_tuple, upload_f32
 from .maps import GAMMA, KINDS, centring_vector
 
 STATS = ("mean", "std", "min", "max", "argmin", "argmax", "skewness", "kurtosis", "pnr")
@@ -129,41 +128,23 @@ def summary_images(pmd, movie=None, *, kinds="denoised", stats=("mean", "std", "
     ``pmd.to_device()`` its context and uploaded factors are reused.  Every image has the same bits for every
     frame_batch_size and source, for every order and subset of kinds and stats.  Argument errors are raised before any
     device work and before the movie is read; a decomposition of no frames has no extrema and raises ValueError."""
-    from .export import expand_tables_for
-    from .pmdarray import PMDArray
-
-    if not isinstance(pmd, PMDArray):
-        raise TypeError("pmd must be a localmd_amd.PMDArray, got {}".format(type(pmd).__name__))
+    check_pmd(pmd)
     kinds = name_tuple(kinds, KINDS, "kind", "kinds")
     stats = name_tuple(stats, STATS, "stat", "stats")
     temporal_bin = _check_bin(temporal_bin)
-    T, d1, d2 = (int(x) for x in pmd.shape)
-    D = d1 * d2
     if kinds != ("denoised",) and movie is None:
         raise ValueError("kinds {} need the movie: pass movie=".format(kinds))
-    on_device, esize = source_info(movie, pmd.shape) if movie is not None else (False, 4)
-    if T == 0:
+    kp = KindPlan(pmd, movie, raw="raw" in kinds, panels=tuple(k for k in ("denoised", "residual") if k in kinds),
+                  frame_batch_size=frame_batch_size)
+    if kp.T == 0:
         raise ValueError("the decomposition has no frames: their extrema do not exist")
     need = tuple(any(s in names for s in stats) for names in (_EXT_STATS, _ARG_STATS, _MOM_STATS))
-    do_raw = "raw" in kinds
-    panels = tuple(k for k in ("denoised", "residual") if k in kinds)
-    reads_movie = do_raw or "residual" in panels
-    plan = block_plan(T, frame_batch_size)
-    nb = plan[0][1] - plan[0][0]
-    n_cols, rank = (int(x) for x in pmd.r.shape)
-    tabs = xt = None
-    if panels:
-        tabs, xt = expand_tables_for(pmd)
 
     with device_context(pmd, device, ctx) as (ctx, dv):
-        nbytes = summary_device_bytes(D=D, nb=nb, esize=esize, n_raw=int(do_raw), n_expand=len(panels), need_ext=need[0],
-                                      need_arg=need[1], need_mom=need[2], n_cols=n_cols, rank=rank,
-                                      n_entries=len(xt["entries"]) if xt else 0, n_a=int(tabs["a"].size) if tabs else 0,
-                                      n_patches=int(xt["n_patches"]) if xt else 0, needs_movie=reads_movie,
-                                      host_source=not on_device, n_batches=len(plan), factors_on_device=dv is not None)
+        nbytes = summary_device_bytes(**kp.facts(dv), n_raw=int(kp.raw), n_expand=len(kp.panels), need_ext=need[0],
+                                      need_arg=need[1], need_mom=need[2], needs_movie=kp.reads_movie)
         check_fit("summary_images", nbytes, _device_free_bytes(ctx.device))
-        out = _summary(ctx, pmd, dv, tabs, xt, movie if reads_movie else None, plan, stats, do_raw, panels, need,
-                       temporal_bin, frame_batch_size, num_workers)
+        out = _summary(ctx, pmd, KindBlocks(ctx, pmd, dv, kp, num_workers), stats, need, temporal_bin)
     return Summary(stats=stats, temporal_bin=temporal_bin, **{k: out[k] for k in kinds})
 
 
@@ -197,35 +178,26 @@ class _State:
         return tuple(None if t is None else t.cpu().numpy() for t in (self.ext, self.arg, self.mom))
 
 
-def _summary(ctx, pmd, dv, tabs, xt, movie, plan, stats, do_raw, panels, need, temporal_bin, frame_batch_size,
-             num_workers):
-    from ._lib import ptr
-
-    T, d1, d2 = (int(x) for x in pmd.shape)
-    D = d1 * d2
+def _summary(ctx, pmd, blocks, stats, need, temporal_bin):
+    kp = blocks.plan
+    T, d1, d2, D, do_raw, panels = kp.T, kp.d1, kp.d2, kp.D, kp.raw, kp.panels
     P = len(panels)
     mean32 = np.asarray(pmd.mean_img, dtype=np.float32).reshape(-1)
     centre32 = centring_vector(pmd)
     raw = _State(ctx, D, need, centre32) if do_raw else None
     if P:
-        ex = Expander(ctx, pmd, dv, tabs, xt, block_panels=P)
-        code = panel_code(panels)
         # the kernel takes the expanded block as a batch of P D "pixels" whose centring vector is the mean image under
         # the denoised panel and 0 under the residual panel
         centres = {"denoised": mean32, "residual": np.zeros(D, np.float32)}
         expanded = _State(ctx, P * D, need, interleave([centres[k] for k in panels], d1, d2))
-    walk = block_walk(plan, D)
 
-    def consume(batch, elem, b0, n):
-        for c0, m, yp in walk(batch, b0):
-            if do_raw:
-                raw.accumulate(ctx, yp, elem, m, c0, temporal_bin)
-            if P:
-                ex.coefficients(c0, m)
-                ex.expand(m, P, code, yp, elem)
-                expanded.accumulate(ctx, ptr(ex.block), 0, m, c0, temporal_bin)
+    def each(c0, m, yp, elem, xp):
+        if do_raw:
+            raw.accumulate(ctx, yp, elem, m, c0, temporal_bin)
+        if P:
+            expanded.accumulate(ctx, xp, 0, m, c0, temporal_bin)
 
-    read_batches(ctx, movie, [(b0, b1) for b0, b1, _ in plan], frame_batch_size, num_workers, consume)
+    blocks.run(each)
     ctx.sync()
 
     noise = np.asarray(pmd.var_img, dtype=np.float64).reshape(-1)      # the std image, see _stream.mean_std

@@ -20,10 +20,9 @@ Device memory does not grow with the movie's length (superpixel_device_bytes).
 """
 import numpy as np
 
-from ._expand import Expander, expander_bytes, panel_code
+from ._expand import KindBlocks, KindPlan, expander_bytes
 from ._movie import _device_free_bytes
-from ._stream import (batch_buffer_bytes, block_plan, block_walk, check_fit, device_context, read_batches, source_info,
-                      upload_f32)
+from ._stream import batch_buffer_bytes, check_fit, check_pmd, device_context, upload_f32
 from .quantiles import movie_passes, quantile_device_bytes, quantile_images
 
 KINDS = ("denoised", "raw")
@@ -222,11 +221,7 @@ def superpixels(pmd, movie=None, *, kind="denoised", th=2.0, cut_off=0.9, min_si
     has the same bits for every frame_batch_size, source and residency, and for order "C" and "F" of the same movie.
     Argument errors are raised before any device work and before the movie is read; a decomposition of no frames raises
     ValueError, and so does a plan that does not fit the free device memory."""
-    from .export import expand_tables_for
-    from .pmdarray import PMDArray
-
-    if not isinstance(pmd, PMDArray):
-        raise TypeError("pmd must be a localmd_amd.PMDArray, got {}".format(type(pmd).__name__))
+    check_pmd(pmd)
     th, cut_off, min_size, max_size = _check(kind, th, cut_off, min_size, max_size)
     T, d1, d2 = (int(x) for x in pmd.shape)
     D = d1 * d2
@@ -239,28 +234,21 @@ def superpixels(pmd, movie=None, *, kind="denoised", th=2.0, cut_off=0.9, min_si
     raw = kind == "raw"
     if raw and movie is None:
         raise ValueError('kind "raw" needs the movie: pass movie=')
-    on_device, esize = source_info(movie, pmd.shape) if raw else (False, 4)
+    kp = KindPlan(pmd, movie if raw else None, raw=raw, panels=() if raw else ("denoised",),
+                  frame_batch_size=frame_batch_size)
     if T == 0:
         raise ValueError("the decomposition has no frames: their correlations do not exist")
     if D >= 2 ** 31:
         raise ValueError("superpixels labels pixels in int32: {} pixels are too many".format(D))
-    plan = block_plan(T, frame_batch_size)
-    nb = plan[0][1] - plan[0][0]
-    n_cols, rank = (int(x) for x in pmd.r.shape)
-    tabs, xt = (None, None) if raw else expand_tables_for(pmd)
 
     with device_context(pmd, device, ctx) as (ctx, dv):
-        nbytes = superpixel_device_bytes(D=D, T=T, nb=nb, esize=esize, kind=kind, threshold_given=thr is not None,
-                                         n_cols=n_cols, rank=rank, n_entries=len(xt["entries"]) if xt else 0,
-                                         n_a=int(tabs["a"].size) if tabs else 0,
-                                         n_patches=int(xt["n_patches"]) if xt else 0, host_source=not on_device,
-                                         n_batches=len(plan), factors_on_device=dv is not None)
+        nbytes = superpixel_device_bytes(**kp.facts(dv), T=T, kind=kind, threshold_given=thr is not None)
         check_fit("superpixels", nbytes, _device_free_bytes(ctx.device))
         if thr is None:
             qi = quantile_images(pmd, movie if raw else None, kinds=kind, q=0.5, mad=True, frame_batch_size=frame_batch_size,
                                  num_workers=num_workers, ctx=ctx)
             thr = threshold_image(getattr(qi, kind)[0], qi.mad[kind], th)
-        mom = _moments(ctx, pmd, dv, tabs, xt, movie if raw else None, plan, thr, frame_batch_size, num_workers)
+        mom = _moments(ctx, KindBlocks(ctx, pmd, dv, kp, num_workers), thr)
         rho = finish_correlations(mom, T, d1, d2)
         edges = edge_bytes(rho, cut_off)
         root = _components(ctx, edges)
@@ -269,31 +257,23 @@ def superpixels(pmd, movie=None, *, kind="denoised", th=2.0, cut_off=0.9, min_si
                        max_size)
 
 
-def _moments(ctx, pmd, dv, tabs, xt, movie, plan, thr, frame_batch_size, num_workers):
+def _moments(ctx, blocks, thr):
     """(6, D) float64: the sums of pmd_threshold_moments_accumulate over the whole movie."""
     import torch
     from ._lib import ptr
 
-    _, d1, d2 = (int(x) for x in pmd.shape)
-    D = d1 * d2
+    d1, d2, D = blocks.plan.d1, blocks.plan.d2, blocks.plan.D
     thr_d = upload_f32(ctx, thr.reshape(-1))
     mom = torch.zeros((6, D), dtype=torch.float64, device=ctx.device)
-    ex = code = None
-    if movie is None:
-        ex = Expander(ctx, pmd, dv, tabs, xt, block_panels=1)
-        code = panel_code(("denoised",))
-    walk = block_walk(plan, D)
 
-    def consume(batch, elem, b0, n):
-        if ex is None:                                        # raw: the batch in place, any length
-            ctx.call("pmd_threshold_moments_accumulate", ptr(batch), int(elem), D, int(n), d1, d2, ptr(thr_d), ptr(mom))
-            return
-        for c0, m, _ in walk(None, b0):
-            ex.coefficients(c0, m)
-            ex.expand(m, 1, code, None, 0)
-            ctx.call("pmd_threshold_moments_accumulate", ptr(ex.block), 0, D, int(m), d1, d2, ptr(thr_d), ptr(mom))
+    def accumulate(X, elem, n):
+        ctx.call("pmd_threshold_moments_accumulate", X, int(elem), D, int(n), d1, d2, ptr(thr_d), ptr(mom))
 
-    read_batches(ctx, movie, [(b0, b1) for b0, b1, _ in plan], frame_batch_size, num_workers, consume)
+    def each(c0, m, yp, elem, xp):
+        if xp is not None:                                    # denoised: block by block
+            accumulate(xp, 0, m)
+
+    blocks.run(each, batch=lambda Y, elem, b0, n: accumulate(Y, elem, n))     # raw: the batch in place, any length
     ctx.sync()
     return mom.cpu().numpy()
 

@@ -21,8 +21,8 @@ import numpy as np
 import scipy.sparse
 
 from ._movie import _device_free_bytes
-from ._stream import (BLOCK, ToHost, VtBlocks, batch_buffer_bytes, block_plan, block_walk, check_fit, device_context,
-                      factor_bytes, name_tuple, read_batches, scaled_r, source_info, upload_f32)
+from ._stream import (BLOCK, ToHost, VtBlocks, batch_buffer_bytes, block_plan, block_walk, check_fit, check_pmd,
+                      device_context, factor_bytes, name_tuple, read_batches, scaled_r, source_info, upload_f32)
 
 KINDS = ("denoised", "raw", "residual")
 REDUCE = ("mean", "sum")
@@ -258,10 +258,7 @@ def extract_traces(pmd, rois, movie=None, *, kinds=("denoised",), reduce="mean",
     streamed decomposition, uint16 / int16 in their own dtype) and device tensors (sliced in place).  After
     ``pmd.to_device()`` its context and uploaded factors are reused.  Every trace has the same bits for every
     frame_batch_size and source.  Argument errors are raised before any device work and before the movie is read."""
-    from .pmdarray import PMDArray
-
-    if not isinstance(pmd, PMDArray):
-        raise TypeError("pmd must be a localmd_amd.PMDArray, got {}".format(type(pmd).__name__))
+    check_pmd(pmd)
     kinds = name_tuple(kinds, KINDS, "kind", "kinds")
     if reduce not in REDUCE:
         raise ValueError("unknown reduce {!r}; choose from {}".format(reduce, REDUCE))
