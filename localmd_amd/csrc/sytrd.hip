@@ -1096,6 +1096,28 @@ __global__ void narrow_vec_kernel(const double* __restrict__ src, float* __restr
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) dst[i] = (float)src[i];
 }
+// The Rayleigh quotients of refined vectors need not ascend where the fp32 solver's did (inside a cluster, a repeated
+// eigenvalue or a null space they differ by rounding only): rank[i] = place of lam[i] in ascending order, ties by index
+// (counting, n <= SYEVD_REFINE_MAX), sorted[rank[i]] = lam[i].
+__global__ void refine_rank_kernel(const double* __restrict__ lam, int n, int* __restrict__ rank, double* __restrict__ sorted) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double li = lam[i];
+  int r = 0;
+  for (int j = 0; j < n; ++j) {
+    const double lj = lam[j];
+    r += (lj < li || (lj == li && j < i)) ? 1 : 0;
+  }
+  rank[i] = r;
+  sorted[r] = li;
+}
+// narrow_kernel with vector r leaving as memory row rank[r]
+__global__ void narrow_ranked_kernel(const double* __restrict__ src, long lds_, const int* __restrict__ rank, float* __restrict__ dst,
+                                     long ldd, int n) {
+  const int r = blockIdx.y;
+  const long ro = rank[r];
+  for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < n; c += gridDim.x * blockDim.x) dst[ro * ldd + c] = (float)src[(long)r * lds_ + c];
+}
 }  // namespace
 
 int pmd_ctx_scratch2(pmd_ctx* ctx, size_t bytes, void** out) {
@@ -1114,7 +1136,8 @@ int pmd_ctx_scratch2(pmd_ctx* ctx, size_t bytes, void** out) {
 static int refine_steps_for(int n) { return (n > SYEVD_F64_MAX && n <= SYEVD_REFINE_MAX) ? SYEVD_REFINE_STEPS : 0; }
 
 // Ad: widened copy of the input matrix (column-major lower triangle valid), taken BEFORE the fp32 solver overwrote A;
-// A (memory row j = eigenvector j) and w are refined in place.  ws: 5 n^2 + n doubles behind Ad.
+// A (memory row j = eigenvector j) and w are refined in place and leave in ascending order of the refined eigenvalues.
+// ws: 5 n^2 + n doubles behind Ad.
 static int syevd_refine(pmd_ctx* ctx, int n, const double* Ad, float* A, long lda, float* w, double* ws, int steps) {
   pmd_prof_scope prof__(ctx, "syevd_refine_f64");
   const size_t nn = (size_t)n * n;
@@ -1138,9 +1161,13 @@ static int syevd_refine(pmd_ctx* ctx, int n, const double* Ad, float* A, long ld
     PMD_BLAS(ctx, rocblas_dgemm(ctx->blas, rocblas_operation_none, rocblas_operation_none, n, n, n, &one, X, n, S, n, &one, Xn, n));
     double* t = X; X = Xn; Xn = t;
   }
-  hipLaunchKernelGGL(narrow_kernel, dim3((n + 255) / 256, n), dim3(256), 0, ctx->stream, X, (long)n, A, lda, n);
-  hipLaunchKernelGGL(narrow_eigenvalues_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, lam, w, n);
-  PMD_LAUNCH_CHECK(ctx, "narrow_kernel");
+  // ascending order is the contract (and where narrow_eigenvalues_kernel finds max |lambda|); Xn is free by now
+  double* sorted = Xn;
+  int* rank = reinterpret_cast<int*>(Xn + n);
+  hipLaunchKernelGGL(refine_rank_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, lam, n, rank, sorted);
+  hipLaunchKernelGGL(narrow_ranked_kernel, dim3((n + 255) / 256, n), dim3(256), 0, ctx->stream, X, (long)n, rank, A, lda, n);
+  hipLaunchKernelGGL(narrow_eigenvalues_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, sorted, w, n);
+  PMD_LAUNCH_CHECK(ctx, "narrow_ranked_kernel");
   return PMD_OK;
 }
 

@@ -763,19 +763,27 @@ int pmd_sb2st_apply_q2_impl(pmd_ctx* ctx, int n, const float* V2, const float* t
   return PMD_OK;
 }
 
-// stage 1 of the two-stage reduction alone (tests): dense -> band; the workspace is allocated and freed inside
+// stage 1 of the two-stage reduction alone (tests): dense -> band; the workspace is allocated and freed inside.  As on the
+// route itself (pmd_syevd_two_stage works on a copy), a flagged call hands A back as it came: the caller reduces it another way.
 extern "C" int pmdk_sy2sb(pmd_ctx* ctx, int n, float* A, long lda, float* tau1, int* flag_host) {
   CTX_CHECK(ctx);
-  const size_t bytes = pmd_sy2sb_workspace_bytes_impl(n);
-  void* ws = nullptr;
+  const size_t bytes = pmd_sy2sb_workspace_bytes_impl(n), ab = (size_t)n * lda * sizeof(float);
+  void *ws = nullptr, *keep = nullptr;
   if (hipMalloc(&ws, bytes) != hipSuccess) return pmd_fail(ctx, PMD_ERR_HIP, "pmdk_sy2sb", "hipMalloc");
+  if (hipMalloc(&keep, ab) != hipSuccess) {
+    (void)hipFree(ws);
+    return pmd_fail(ctx, PMD_ERR_HIP, "pmdk_sy2sb", "hipMalloc");
+  }
+  (void)hipMemcpyAsync(keep, A, ab, hipMemcpyDeviceToDevice, ctx->stream);
   const int rc = pmd_sy2sb_impl(ctx, n, A, lda, tau1, flag_host, ws, bytes);
+  if (rc == PMD_OK && *flag_host) (void)hipMemcpyAsync(A, keep, ab, hipMemcpyDeviceToDevice, ctx->stream);
   (void)hipStreamSynchronize(ctx->stream);
   (void)hipFree(ws);
+  (void)hipFree(keep);
   return rc;
 }
 
-// stages 1 + 2 (tests): dense -> band -> tridiagonal; d[n], e[n - 1] on the device
+// stages 1 + 2 (tests): dense -> band -> tridiagonal; d[n], e[n - 1] on the device (*flag_host != 0: stage 2 did not run)
 extern "C" int pmdk_sytrd2(pmd_ctx* ctx, int n, float* A, long lda, float* tau1, float* d, float* e, int* flag_host) {
   CTX_CHECK(ctx);
   const size_t b1 = pmd_sy2sb_workspace_bytes_impl(n), b2 = pmd_sb2st_workspace_bytes_impl(n);
@@ -787,7 +795,7 @@ extern "C" int pmdk_sytrd2(pmd_ctx* ctx, int n, float* A, long lda, float* tau1,
   }
   int rc = pmd_sy2sb_impl(ctx, n, A, lda, tau1, flag_host, w1, b1);
   float *V2 = nullptr, *tau2 = nullptr;
-  if (rc == PMD_OK) rc = pmd_sb2st_impl(ctx, n, A, lda, d, e, &V2, &tau2, w2, b2);
+  if (rc == PMD_OK && !*flag_host) rc = pmd_sb2st_impl(ctx, n, A, lda, d, e, &V2, &tau2, w2, b2);
   (void)hipStreamSynchronize(ctx->stream);
   (void)hipFree(w1);
   (void)hipFree(w2);

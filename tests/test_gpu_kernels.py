@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from oracle import pmd_oracle as O, philox
+from tests.eig_ref import householder_q
 from tests.util import context_under, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -408,12 +409,7 @@ def test_sytrd_own_kernels_reconstruct(gpu_ctx, n):
     S = _sym_matrix(rng, n)
     Am, d, e, tau = _run_sytrd(gpu_ctx, S, 1)
     assert np.all(np.isfinite(d)) and np.all(np.isfinite(e)) and np.all(np.isfinite(tau))
-    Q = np.eye(n)
-    for j in range(n - 2, -1, -1):
-        v = np.zeros(n)
-        v[j + 1] = 1.0
-        v[j + 2:] = Am[j, j + 2:]
-        Q -= tau[j] * np.outer(v, v @ Q)
+    Q = householder_q(Am, tau)
     Tm = np.diag(d.astype(np.float64)) + np.diag(e.astype(np.float64), 1) + np.diag(e.astype(np.float64), -1)
     S64 = S.astype(np.float64)
     scale = np.abs(S64).max() * np.sqrt(n)
