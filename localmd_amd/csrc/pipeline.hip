@@ -41,7 +41,7 @@ struct tile_la {
   }
 
   // nmat = eigenvectors of the summed leading n x n blocks of gpart, by descending eigenvalue (mode 1: scaled by
-  // 1/sqrt(lambda), directions with lambda <= tol * lambda_max zeroed)
+  // 1/sqrt(lambda), directions with lambda <= tol * lambda_max zeroed; mode 2: those directions zeroed, no scaling)
   int eig(int slices, int n, int mode, double tol, double* lam_out, int n_tiles) const {
     if (wide()) return pmd_launch_wide_eig(ctx, gpart, slices, rp, n, mode, tol, nmat, lam_out, n_tiles, eig_ws, eig_ws_bytes);
     return pmd_launch_small_eig(ctx, gpart, slices, n, mode, tol, nmat, lam_out, n_tiles);
@@ -358,7 +358,10 @@ extern "C" int pmd_tiles_residual(pmd_ctx* ctx, const float* Xw, long ldx, long 
   RUN(la.sketch_basis(p.yt, p.dpad, d, p.l, p.nref, p.qt, n));
   RUN(pmd_launch_tile_atx_rp(ctx, p.ar, p.ld_b, nullptr, 0, d, d, p.qt, srd, p.dpad, p.bm, srb, p.ld_b, n, p.nb, 1, p.nref));
   RUN(la.gram(p.bm, p.ld_b, p.nb, n, 1));
-  RUN(la.eig(1, p.nref, 0, 0.0, la.lam, n));
+  // A direction the residual does not have (lambda <= 1e-10 lambda_max, the cut of the first window's whitening; every
+  // direction of an all-zero residual) gets a zero vector, not the arbitrary unit vector the QR of the sketch leaves there:
+  // such a vector is not orthogonal to E.  Its statistics are 0 / 0, it fails, and the scan keeps it like any other failure.
+  RUN(la.eig(1, p.nref, 2, 1e-10, la.lam, n));
   // new components of this window: min(max_components, bins, pixels) of them exist (see pmd_tiles_decompose_staged)
   const int rn = std::min(r, std::min(p.nb, p.nref));
   RUN(la.rowmix(p.qt, p.dpad, p.nref, rn, p.unew, p.dpad, d, n));

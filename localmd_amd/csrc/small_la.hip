@@ -29,6 +29,23 @@ __global__ __launch_bounds__(256) void small_qr_kernel(const float* __restrict__
   __syncthreads();
 
   const int col = tid >> 2, sub = tid & 3;  // four threads per column
+  // Squared norms of the columns as loaded, the yardstick of the dependence test below; tau[k] holds the one of column k
+  // until step k replaces it.
+  {
+    double cn = 0.0;
+    if (col < l)
+      for (int i = sub; i < P; i += 4) { const double v = (double)M[col * ldm + i]; cn += v * v; }
+    cn += __shfl_xor(cn, 1);
+    cn += __shfl_xor(cn, 2);
+    if (sub == 0) tau[col] = cn;
+  }
+  __syncthreads();
+  // What is left of a column that depends on the earlier ones is rounding residue.  Reflecting on it would build the null
+  // columns of Q from residue of residue - with identical rows (a constant tile) each level is smaller by a factor eps
+  // until the squares underflow, and the result then depends on the scale of the data.  Such a column gets tau = 0 (its
+  // Q column is the unit vector rotated by the earlier reflectors): left^2 <= dep_tol * |column|^2, far below anything a
+  // column with content of its own leaves (fp64 storage 1e-12 of the norm, fp32 storage 1e-6).
+  const double dep_tol = sizeof(ST) == sizeof(double) ? 1e-24 : 1e-12;
   for (int k = 0; k < nref; ++k) {
     // sigma = sum_{i>k} Y[i][k]^2
     double part = 0.0;
@@ -43,7 +60,7 @@ __global__ __launch_bounds__(256) void small_qr_kernel(const float* __restrict__
       const double sigma = scratch[0];
       const double alpha = (double)M[k * ldm + k];
       double t = 0.0, scale = 0.0, beta = alpha;
-      if (sigma > 0.0) {
+      if (sigma > 0.0 && alpha * alpha + sigma > dep_tol * tau[k]) {
         const double nrm = sqrt(alpha * alpha + sigma);
         beta = (alpha >= 0.0) ? -nrm : nrm;
         t = (beta - alpha) / beta;
@@ -144,6 +161,7 @@ extern "C" int pmdk_small_qr(pmd_ctx* ctx, const float* Yt, long y_tile_stride, 
 // Nout[tile][c'][c] = eigenvector c (descending eigenvalue), component c'.
 //   mode 0: plain eigenvectors
 //   mode 1: column c scaled by 1/sqrt(lambda_c); columns with lambda_c <= tol*lambda_max zeroed
+//   mode 2: plain eigenvectors, columns with lambda_c <= tol*lambda_max (or lambda_c <= 0) zeroed
 // lam_out[tile][c] = eigenvalue c (descending); entries >= n are zero.
 // By Householder tridiagonalisation (LAPACK dsytd2 'L' conventions), in-place formation of Q (dorg2r on the shifted array,
 // as dorgtr does) and the implicit QL iteration with the rotations accumulated into Q (EISPACK tql2) - all in ONE wave on
@@ -340,6 +358,7 @@ __global__ __launch_bounds__(64) void small_eig_ql_kernel(const double* __restri
     const double lmax = pmd_readlane_f64(lam, 0);
     double scl = 1.0;
     if (mode == 1) scl = (lam > tol * lmax && lam > 0.0) ? 1.0 / sqrt(lam) : 0.0;
+    else if (mode == 2) scl = (lam > tol * lmax && lam > 0.0) ? 1.0 : 0.0;
     double* no = Nout + (long)blockIdx.x * 4096;
     for (int r = 0; r < 64; ++r) no[r * 64 + lane] = (r < n && live) ? A[r * LD + src] * scl : 0.0;
     lam_out[(long)blockIdx.x * 64 + lane] = live ? lam : 0.0;

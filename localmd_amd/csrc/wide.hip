@@ -7,7 +7,7 @@
 //   wide_gram   : G[tile][slice][rp][rp] = In In^T over a slice of positions, fp64 accumulation of fp32 inputs
 //   wide_eig    : symmetric eigendecomposition of the summed n x n Gram matrices (rocSOLVER dsyevd, strided batch),
 //                 vectors ordered by descending eigenvalue; mode 1 = scaled by 1/sqrt(lambda) with the null rule of
-//                 small_eig (lambda <= tol * lambda_max -> zero column)
+//                 small_eig (lambda <= tol * lambda_max -> zero column), mode 2 = the null rule without the scaling
 //   wide_rowmix : Out[tile][c][x] = sum_c' N[tile][c'][c] In[tile][c'][x], fp64 accumulation, in-place safe
 // Same numerical policy as the 64-row path: every Gram matrix behind an SVD in fp64 from the fp32
 // data, eigenvectors in fp64.  The sequences of steps are those of the 64-row path, written once in pipeline.hip; there
@@ -125,6 +125,9 @@ __global__ void wide_eig_finish_kernel(const double* __restrict__ A, const doubl
       if (mode == 1) {
         const double lam = wt[src];
         v = (lam > tol * lmax && lam > 0.0) ? v / sqrt(lam) : 0.0;
+      } else if (mode == 2) {
+        const double lam = wt[src];
+        v = (lam > tol * lmax && lam > 0.0) ? v : 0.0;
       }
     }
     Nout[(long)tile * rp * rp + i] = v;

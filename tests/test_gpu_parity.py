@@ -923,3 +923,101 @@ def test_tile_batches_and_single_copy_plan_match_the_default_path(gpu_ctx):
             strong = a.s > 1e-2 * a.s[0]
             assert np.all((np.abs(x.s - a.s) / a.s)[strong] <= tol[strong]), np.max((np.abs(x.s - a.s) / a.s / tol)[strong])
             assert PM.probes(x, a, mov.shape, n=400) < 2e-4
+
+
+# Constant content: (what is overwritten, background_rank, further arguments).  The values are integers c with T c < 2^24.
+_CONSTANT_KINDS = {
+    "dead pixels": (("pixels",), 0, {}),
+    "dead row": (("row",), 2, {}),
+    "interior constant tile": (("tile",), 0, {}),
+    "saturated block": (("saturated",), 2, {}),
+    "zero pixel": (("zero pixel",), 0, {"compute_normalizer": False}),
+    "dead column + pixels": (("column", "pixels"), 2, {}),
+    "half dead": (("half",), 0, {}),
+    "constant border band": (("band",), 2, {}),
+    "interior constant tile, residual windows": (("tile",), 2, {"window_chunks": 160}),
+    "dead row, max_components 60": (("row",), 0, {"max_components": 60}),
+}
+
+
+def _constant_movie(what, trial):
+    """(movie (T, 40, 50), mask of the constant pixels, their values)."""
+    T, d1, d2 = 320, 40, 50
+    mov = _movie(T, d1, d2, seed=70 + trial)
+    value = np.full((d1, d2), np.nan, dtype=np.float32)
+    rng = np.random.default_rng(trial)
+    if "pixels" in what:
+        idx = rng.integers(0, d1 * d2, 12)
+        value.reshape(-1)[idx] = 100.0
+    if "row" in what:
+        value[d1 // 2, :] = 7.0
+    if "column" in what:
+        value[:, 3] = 55.0
+    if "tile" in what:
+        value[:22, :22] = 100.0
+    if "saturated" in what:
+        value[5:15, 8:20] = 4095.0
+    if "zero pixel" in what:
+        value[4, 4] = 0.0
+    if "half" in what:
+        value[:, :d2 // 2] = 1.0
+    if "band" in what:
+        value[:3, :] = value[-3:, :] = value[:, :3] = value[:, -3:] = 17.0
+    mask = ~np.isnan(value)
+    mov[:, mask] = value[mask]
+    assert float(np.nanmax(value)) * T < 2 ** 24
+    return mov, mask, value
+
+
+@pytest.mark.parametrize("kind", list(_CONSTANT_KINDS))
+def test_full_pipeline_constant_pixels_rows_and_tiles(gpu_ctx, kind):
+    """Movies with dead and saturated pixels, dead rows and columns, a constant half, an all-constant tile and a constant
+    border band on all four sides (what register_movie(border=<constant>) and register_piecewise leave), through the
+    driver against the oracle: what INTEGRATION.md ("All-constant tiles") promises.  One kind runs with residual windows
+    (pmd_tiles_residual on a constant tile), one at the generic width (max_components = 60).
+
+    The statistics images within the tolerances of the other parity tests; every factor finite on both sides; tile ranks
+    equal (an all-constant tile keeps one failing component per window, as in the reference); the oracle never has fewer
+    singular values, at most one more per kept component of an all-constant tile - such a component is a zero vector
+    here, an arbitrary unit vector with a zero trace there - and those are below 1e-5 s_1; the fit of the standardised
+    movie on random probes within 3 % + 1e-6 of the oracle's.  Measured on MI355X: one all-constant tile 46 / 46
+    components, three (half dead) 26 / 26, one fitted in two windows 45 / 47 with the oracle's extra values at 1.0e-8 s_1
+    and 8.3e-9 s_1; no difference in the kinds without an all-constant tile.
+
+    A constant pixel with an integer value c, T c < 2^24: the fp32 mean is exact, the standardised trace exactly zero, and
+    pmd[:, i, j] equals c bit for bit, expanded on the host and after to_device()."""
+    from localmd_amd import grid
+    from tests.test_gpu_fuzz import probe_fit
+
+    what, bg, extra_kw = _CONSTANT_KINDS[kind]
+    trial = list(_CONSTANT_KINDS).index(kind)
+    mov, mask, value = _constant_movie(what, trial)
+    T, d1, d2 = mov.shape
+    kw = dict(max_components=5, background_rank=bg, thresholds=(1.0, 1.7))
+    kw.update(extra_kw)
+    pmd, diag, ref = _compare_full(gpu_ctx, mov, (20, 20), T, **kw)
+    np.testing.assert_allclose(pmd.mean_img, ref.mean_img, rtol=1e-5)
+    np.testing.assert_allclose(pmd.var_img, ref.std_img, rtol=2e-4)
+    for res in (pmd, ref):
+        assert all(np.all(np.isfinite(x)) for x in (res.s, res.r, res.v, res.u.data)), kind
+    it1, it2 = grid.tile_origins((d1, d2), (20, 20))
+    constant = np.array([bool(mask[k:k + 20, j:j + 20].all()) for k in it1 for j in it2])
+    n_constant, n_null = int(constant.sum()), int(diag["tile_ranks"][constant].sum())
+    extra = len(ref.s) - len(pmd.s)
+    fit = (probe_fit(pmd, mov, ref.mean_img, ref.std_img, "F"), probe_fit(ref, mov, ref.mean_img, ref.std_img, "F"))
+    print(f"\n{kind}: tile ranks {diag['tile_ranks'].tolist()} / {ref.diag['tile_ranks'].tolist()}, all-constant tiles {n_constant}, "
+          f"their kept components {n_null}, components {len(pmd.s)} / {len(ref.s)}, oracle's extra s / s_1 {(ref.s[len(pmd.s):] / ref.s[0]).tolist()}, fit {fit[0]:.5f} / {fit[1]:.5f}")
+    np.testing.assert_array_equal(diag["tile_ranks"], ref.diag["tile_ranks"])
+    assert ("tile" in what or "half" in what) == (n_constant > 0)
+    assert 0 <= extra <= n_null, (kind, extra, n_constant, n_null)
+    assert np.all(ref.s[len(pmd.s):] < 1e-5 * ref.s[0]), ref.s[len(pmd.s):]
+    assert abs(fit[0] - fit[1]) < 0.03 * fit[1] + 1e-6, fit
+    expected = np.broadcast_to(value[mask], (T, int(mask.sum())))
+    host = pmd[:][:, mask]
+    assert host.dtype == np.float32 and np.array_equal(host, expected), (kind, "host", float(np.abs(host - expected).max()))
+    pmd.to_device(ctx=gpu_ctx)
+    try:
+        got = pmd[:][:, mask]
+    finally:
+        pmd.to_host()
+    assert got.dtype == np.float32 and np.array_equal(got, expected), (kind, "device", float(np.abs(got - expected).max()))

@@ -183,28 +183,34 @@ class _Run:
 def _device_run(ctx, name, thr, max_fail):
     """One pmd_tiles_residual call as _fit_tiles_in_windows makes it, on fresh copies of the bases.  A guard tile behind the
     last one in every per-tile array."""
+    c, inp = CASES[name], _inputs(name)
+    return _call(ctx, inp["X"], inp["pix"], inp["E"], c["bases"], c["block"], c["L"], c["a"], c["r"], thr, max_fail,
+                 _omega_indices(name))
+
+
+def _call(ctx, X, pix, E, bases, block, L, a, r, thr, max_fail, omega_indices):
+    """pmd_tiles_residual on the window X (D x L) with the tile table pix and the bases E[t] (d x bases[t])."""
     torch = _t()
     lib = ctx.lib
-    c, inp = CASES[name], _inputs(name)
-    (b1, b2), L, a, r = c["block"], c["L"], c["a"], c["r"]
-    n, d, D = inp["n"], inp["d"], inp["D"]
+    b1, b2 = block
+    n, d, D = len(bases), b1 * b2, X.shape[0]
     rp, dpad, ld = int(lib.pmd_tile_rpad(r)), int(lib.pmd_tile_dpad(d)), int(lib.pmd_time_ld(L))
     assert rp == (128 if r + 10 > 64 else 64)
     xw = torch.zeros((D, ld), dtype=torch.float32, device=ctx.device)
-    xw[:, :L] = _dev(ctx, inp["X"])
+    xw[:, :L] = _dev(ctx, X)
     u0 = np.zeros((n + 1, rp, dpad), dtype=np.float32)
     for t in range(n):
-        u0[t, :c["bases"][t], :d] = inp["E"][t].T
+        u0[t, :bases[t], :d] = E[t].T
     u0[n] = 7.0
     ucur = _dev(ctx, u0)
-    counts = _dev(ctx, list(c["bases"]) + [-99], np.int32)
+    counts = _dev(ctx, list(bases) + [-99], np.int32)
     stats = torch.zeros((n + 1, rp, 2), dtype=torch.float32, device=ctx.device)
     good = torch.zeros((n + 1, rp), dtype=torch.int32, device=ctx.device)
     keep = torch.zeros((n + 1, rp), dtype=torch.int32, device=ctx.device)
     stats[n], good[n], keep[n] = 7.0, -5, -5
-    i0, step = _omega_indices(name)
+    i0, step = omega_indices
     ws = ctx.workspace(lib.pmd_tiles_residual_workspace_bytes(n, b1, b2, r, a, L, D))
-    pix_dev = _dev(ctx, inp["pix"], np.int32)
+    pix_dev = _dev(ctx, pix, np.int32)
     ctx.call("pmd_tiles_residual", P(xw), ld, D, L, P(pix_dev), n, b1, b2, r, a, float(thr[0]),
              float(thr[1]), max_fail, SEED, i0, step, P(ucur), P(counts), P(stats), P(good), P(keep), P(ws), ws.numel())
     ctx.sync()
@@ -353,6 +359,70 @@ def test_tiles_residual_vs_float64_oracle(gpu_ctx, name):
     assert share <= 0.10, (name, knife)
     assert n_compared > 0
     assert et_dev <= ET_U_FACTOR * et_ref, (name, et_dev, et_ref)
+
+
+DEGENERATE_THR = (2.5, 1.0)   # above the spatial statistic of any field of a few pixels, below the temporal one of white traces
+
+
+def _degenerate_windows(r):
+    """Three disjoint 10 x 10 tiles (tile t is rows [100 t, 100 t + 100) of the window): one whose window lies exactly in
+    the span of its three basis rows, one all-zero window with the same basis, one all-zero window with an empty basis.
+    The basis rows are indicators of 4, 16 and 64 pixels over 2, 4 and 8 (orthonormal exactly in fp32), the traces
+    rounded sinusoids: every value is an integer."""
+    b1 = b2 = 10
+    d, L = b1 * b2, (96 if r + 10 <= 64 else 400)
+    E = np.zeros((d, 3), dtype=np.float32)
+    E[0:4, 0], E[10:26, 1], E[30:94, 2] = 0.5, 0.25, 0.125
+    B = np.stack([np.round(40 * np.sin(2 * np.pi * (k + 1) * np.arange(L) / L + 0.3 * k)) for k in range(3)])
+    X = np.zeros((3 * d, L), dtype=np.float32)
+    X[:d] = ((E != 0).astype(np.float64) @ B).astype(np.float32)
+    assert np.array_equal(E.T.astype(np.float64) @ E, np.eye(3)) and np.array_equal(X, np.round(X))
+    assert np.array_equal(E.astype(np.float64) @ (E.T.astype(np.float64) @ X[:d]), X[:d])
+    pix = np.arange(3 * d, dtype=np.int32).reshape(3, d)
+    return dict(X=X, pix=pix, E=[E, E, E[:, :0]], bases=[3, 3, 0], block=(b1, b2), L=L, a=4, d=d)
+
+
+@pytest.mark.parametrize("r", [6, 60])
+def test_tiles_residual_on_explained_and_all_zero_windows(gpu_ctx, r):
+    """pmd_tiles_residual where nothing is left to find (64 and 128 component rows): a window that its basis explains
+    exactly, an all-zero window with a basis and one without, max_fail in {1, 2, 3}.
+
+    Rows [0, counts_before) of Ucur keep their bits; Ucur and the counts are finite (the statistics of a zero vector are
+    0 / 0 = NaN, which never passes); every new row is zero or of norm <= 1 + 1e-5, rows from the new count on stay zero and
+    the guard tile is unchanged; counts_after - counts_before <= max_fail; at max_fail = 1 counts_after equals the count of
+    single_residual_block_md in float64 (one kept failure per window, as in the reference); the new rows of the all-zero
+    windows are exactly zero."""
+    ctx = gpu_ctx
+    w = _degenerate_windows(r)
+    d, L, a, bases = w["d"], w["L"], w["a"], w["bases"]
+    n = len(bases)
+    src = DeviceSource(ctx, SEED)
+    i0, step = 11, 3
+    for mf in MAX_FAILS:
+        run = _call(ctx, w["X"], w["pix"], w["E"], bases, w["block"], L, a, r, DEGENERATE_THR, mf, (i0, step))
+        assert np.array_equal(_bits(run.u[n]), _bits(run.u0[n])) and run.counts[n] == -99
+        assert np.all(run.stats[n] == 7.0) and np.all(run.good[n] == -5) and np.all(run.keep[n] == -5)
+        assert np.all(np.isfinite(run.u))
+        for t, base in enumerate(bases):
+            after = int(run.counts[t])
+            assert np.array_equal(_bits(run.u[t, :base]), _bits(run.u0[t, :base])), ("existing components changed", r, mf, t)
+            assert base <= after <= base + mf, (r, mf, t, base, after)
+            assert np.all(_bits(run.u[t, after:]) == 0), ("rows beyond the new count", r, mf, t)
+            norms = np.linalg.norm(run.u[t, base:after].astype(np.float64), axis=1)
+            print(f"\nr = {r}, max_fail {mf}, tile {t}: count {base} -> {after}, norms of the new rows {norms.tolist()}, "
+                  f"statistics {run.stats[t, :max(after - base, 1)].tolist()}")
+            assert np.all(norms <= 1 + 1e-5), (r, mf, t, norms)
+            assert np.all(run.u[t, base:after, d:] == 0), ("padding of the appended rows", r, mf, t)
+            if t > 0:
+                assert np.all(_bits(run.u[t, base:after]) == 0), ("an all-zero window gave a nonzero row", r, mf, t)
+            if mf == 1:
+                block = w["X"][t * d:(t + 1) * d].reshape(w["block"] + (L,), order="F")
+                existing = w["E"][t].reshape(w["block"] + (base,), order="F")
+                om = src.omega(philox.STREAM_TILE_OMEGA, i0 + t * step, L // a, r + 10)
+                with O.arbiter_precision(), np.errstate(invalid="ignore"):
+                    _, good, _, _ = O.single_residual_block_md(block, existing, om, r, a, *DEGENERATE_THR)
+                kept = int(O.filter_by_failures(np.asarray(good).flatten() > 0, 1).sum())
+                assert after == base + min(kept, r - base), (r, t, after, base, kept)
 
 
 @pytest.mark.parametrize("rp", [64, 128])

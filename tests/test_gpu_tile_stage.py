@@ -13,13 +13,9 @@ block), the assertion is K_device <= FACTOR x K_oracle32 (FACTOR below), where K
 single-precision LAPACK against the float64 oracle, evaluated in the test on the same inputs; likewise for the relative
 errors of sqrt(lam) and of the two statistics.
 """
-import ctypes
-
 import numpy as np
 import pytest
 
-from localmd_amd import grid
-from oracle import pmd_oracle as O
 from tests import tile_stage_ref as R
 from tests.util import DeviceSource, context_under, rel_err
 
@@ -40,114 +36,9 @@ def _t():
     return torch
 
 
-def P(t):
-    from localmd_amd._lib import ptr
-
-    return ptr(t)
-
-
-def _dev(ctx, a, dtype=None):
-    return _t().from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(ctx.device)
-
-
-def _poisoned(ctx, shape, dtype):
-    torch = _t()
-    x = torch.empty(shape, dtype=dtype, device=ctx.device)
-    x.view(torch.uint8).fill_(0xFF)
-    return x
-
-
-def _untouched(t):
-    return bool((t.contiguous().view(_t().uint8) == 0xFF).all())
-
-
-class _Run:
-    pass
-
-
-def _device_run(ctx, name, thr, max_fail, n_tiles=None, staged=False, download=True):
-    """One pmd_tiles_decompose call as the driver makes it (staged: pmd_tiles_decompose_staged with stages 1, 2, 4 and
-    the hook arrays read between the calls), on a workspace and outputs full of NaN bytes, a guard tile behind the last
-    one of every output."""
-    torch, lib = _t(), ctx.lib
-    c = R.CASES[name]
-    (d1, d2), (b1, b2), T = R.case_dims(name)
-    a, r, D, d = c["a"], c["r"], d1 * d2, b1 * b2
-    pix_all, _ = R.tiles(name)
-    n = len(pix_all) if n_tiles is None else n_tiles
-    pool_q, pool_idx, pool_w, _ = grid.pooling_maps((b1, b2), c["pool"])
-    Pn = pool_q.shape[0]
-    rp, dpad, ld = int(lib.pmd_tile_rpad(r)), int(lib.pmd_tile_dpad(d)), int(lib.pmd_time_ld(T))
-    xf = torch.zeros((D, ld), dtype=torch.float32, device=ctx.device)
-    xf[:, :T] = _dev(ctx, R.planted_movie(c["movie"]).reshape(D, T))
-    out = _Run()
-    out.n, out.rp, out.d, out.T, out.re = n, rp, d, T, R.r_eff(name)
-    out.ut = _poisoned(ctx, (n + 1, rp, dpad), torch.float32)
-    out.v = _poisoned(ctx, (n + 1, rp, ld), torch.float32)
-    out.stats = _poisoned(ctx, (n + 1, rp, 2), torch.float32)
-    out.good = _poisoned(ctx, (n + 1, rp), torch.int32)
-    out.keep = _poisoned(ctx, (n + 1, rp), torch.int32)
-    out.ranks = _poisoned(ctx, (n + 1,), torch.int32)
-    out.lam = _poisoned(ctx, (n + 1, rp), torch.float64)
-    nbytes = int(lib.pmd_tiles_workspace_bytes(n, b1, b2, Pn, r, a, T, ld, D))
-    assert nbytes > 0
-    ws = ctx.workspace(nbytes)
-    ws.fill_(0xFF)
-    i0, step = R.omega_indices(name)
-    tables = [_dev(ctx, pix_all[:n], np.int32), _dev(ctx, pool_q, np.int32), _dev(ctx, pool_idx, np.int32), _dev(ctx, pool_w, np.float32)]
-    args = (P(xf), ld, D, T, P(tables[0]), n, b1, b2, P(tables[1]), pool_q.shape[1], Pn, P(tables[2]), P(tables[3]), r, a,
-            float(thr[0]), float(thr[1]), max_fail, R.SEED, i0, step, P(out.ut), P(out.v), ld, P(out.stats), P(out.good),
-            P(out.keep), P(out.ranks), P(out.lam), P(ws), ws.numel())
-    if not staged:
-        ctx.call("pmd_tiles_decompose", *args)
-    else:
-        off_v, off_s = ctypes.c_size_t(0), ctypes.c_size_t(0)
-        assert lib.pmd_tiles_hook_offsets(n, b1, b2, Pn, r, a, T, ld, D, ctypes.byref(off_v), ctypes.byref(off_s)) == 0
-        assert off_v.value + n * rp * ld * 4 <= nbytes and off_s.value + n * rp * dpad * 4 <= nbytes
-        ctx.call("pmd_tiles_decompose_staged", *args, 1)
-        ctx.sync()
-        out.v_ds = ws[off_v.value:off_v.value + n * rp * ld * 4].view(torch.float32).view(n, rp, ld)[:, :out.re, :T].cpu().numpy()
-        ctx.call("pmd_tiles_decompose_staged", *args, 2)
-        ctx.sync()
-        out.S = ws[off_s.value:off_s.value + n * rp * dpad * 4].view(torch.float32).view(n, rp, dpad)[:, :out.re, :d].cpu().numpy()
-        ctx.call("pmd_tiles_decompose_staged", *args, 4)
-    ctx.sync()
-    # what must hold after every call, checked where the arrays are: the guard tiles, and zeros from r_eff on
-    re = out.re
-    for arr in (out.ut, out.v, out.stats, out.good, out.keep, out.ranks, out.lam):
-        assert _untouched(arr[n:n + 1]), "guard tile written"
-    assert not bool((out.ut[:n, re:] != 0).any()), "rows of Ut from r_eff on"
-    assert not bool((out.v[:n, re:, :T] != 0).any()), "rows of V from r_eff on"
-    assert not bool((out.stats[:n, re:] != 0).any()), "rows of stats from r_eff on"
-    assert not bool((out.good[:n, re:] != 0).any()) and not bool((out.keep[:n, re:] != 0).any())
-    assert not bool((out.lam[:n, re:] != 0).any()), "lam_out from r_eff on"
-    assert not bool((out.ut[:n, :, d:] != 0).any()), "padding of Ut"
-    out.dev_ut, out.dev_v = out.ut, out.v
-    out.stats, out.good, out.keep = out.stats[:n].cpu().numpy(), out.good[:n].cpu().numpy(), out.keep[:n].cpu().numpy()
-    out.ranks, out.lam = out.ranks[:n].cpu().numpy(), out.lam[:n].cpu().numpy()
-    if download:
-        out.ut, out.v = out.ut[:n, :re, :d].cpu().numpy(), out.v[:n, :re, :T].cpu().numpy()
-    else:
-        out.ut = out.v = None
-    return out
-
-
-def _check_decisions(name, run, thr, max_fail, patterns):
-    """good, keep and ranks follow exactly from the statistics the device returned (no knife edge enters)."""
-    re = run.re
-    thr32 = (np.float32(thr[0]), np.float32(thr[1]))
-    sp, tp = run.stats[:, :re, 0], run.stats[:, :re, 1]
-    good = (sp < thr32[0]) & (tp < thr32[1])
-    np.testing.assert_array_equal(run.good[:, :re], good.astype(np.int32), err_msg=f"{name} {thr} {max_fail}")
-    for t in range(run.n):
-        kept = O.filter_by_failures(good[t].copy(), max_fail)
-        np.testing.assert_array_equal(run.keep[t, :re], kept.astype(np.int32), err_msg=f"{name} tile {t}")
-        nk = int(kept.sum())
-        assert run.ranks[t] == nk, (name, t, run.ranks[t], nk)
-        if np.any(good[t, 1:nk] & ~good[t, :nk - 1][:len(good[t, 1:nk])]):
-            patterns.add("pass after a failure")
-        if nk < re:
-            patterns.add("cut by max_fail")
+# the call itself, its guard tiles and the exact check of the decisions are shared with tests/test_gpu_tile_degenerate.py
+_device_run = R.device_run
+_check_decisions = R.check_decisions
 
 
 _ORACLES = {}

@@ -1,5 +1,5 @@
 """
-The inputs of tests/test_gpu_tile_kernels_wide.py and tests/test_gpu_tile_stage.py are admissible: proven here on the CPU
+The inputs of tests/test_gpu_tile_kernels_wide.py, tests/test_gpu_tile_stage.py and tests/test_gpu_tile_degenerate.py are admissible: proven here on the CPU
 from the oracles alone (omegas of oracle.philox.PhiloxSource, which test_rng_matches_numpy_restatement pins to the
 device's), before a GPU sees them.
 """
@@ -101,3 +101,62 @@ def test_planted_case_is_admissible(name):
     assert R.decision_patterns(stats64, own) == {"pass after a failure", "cut by max_fail"}
     knife = sum(not R.margin_ok(sp, tp, thr) for sp, tp in stats_all for thr in (own, pass_all))
     assert knife / (len(stats_all) * 2) <= 0.10
+
+
+@functools.lru_cache(maxsize=None)
+def _degenerate_refs(name):
+    return R.case_oracles(name, philox.PhiloxSource(R.SEED))
+
+
+@pytest.mark.parametrize("name", sorted(R.DEGENERATE))
+def test_degenerate_family_is_admissible(name):
+    """The tiles of tile_stage_ref.KINDS in the narrow (Zn) and the wide (Zw) case, as conditions on the inputs of
+    tests/test_gpu_tile_degenerate.py:
+      (a) zero, low3, rank1 and sparse2 hold integers and have exactly rho = 0, 3, 1, 2 nonzero singular values in float64
+          (the others below 1e-12 of the first), and so has the pooled, temporally binned tile: pooling hides no component
+          from the sketch;
+      (b) their nonzero singular values lie within 1e3 of each other, far above the 1e-5 relative whitening cut;
+      (c) under the float64 oracle the rho leading components pass the case's thresholds and component rho fails, every
+          statistic of these farther than KNIFE_EDGE from its threshold (a NaN statistic fails): the oracle's rank at
+          max_fail = 1 is rho + 1.
+    The deadrows and live tiles have full rank (72 live pixels / min(pixels, frames)), at least three separated components
+    each, a nonzero fp32 yardstick and no strong component of any oracle nearer than KNIFE_EDGE to a threshold."""
+    refs = _degenerate_refs(name)
+    own = R.thresholds(name)[0]
+    (b1, b2), T = R.case_dims(name)[1:]
+    d = b1 * b2
+    assert R.movie_rows(name).shape == (len(R.KINDS) * d, T) and R.movie_rows(name).dtype == np.float32
+    assert np.array_equal(R.tiles(name)[0], np.arange(len(R.KINDS) * d).reshape(len(R.KINDS), d))
+    for t, kind in enumerate(R.KINDS):
+        X = R.tile_block(name, t).reshape((d, T), order="F").astype(np.float64)
+        assert np.array_equal(X, R.movie_rows(name)[t * d:(t + 1) * d])
+        r64 = refs[t]["f64"]
+        assert r64.u.shape == (d, R.r_eff(name)) and r64.v.shape == (R.r_eff(name), T)
+        sv = np.linalg.svd(X, compute_uv=False)
+        sv_p = np.linalg.svd(R.pooled_binned(name, t), compute_uv=False)
+        if kind in R.RHO:
+            rho = R.RHO[kind]
+            assert np.array_equal(X, np.round(X)) and np.abs(X).max() * T < 2 ** 24
+            for s in (sv, sv_p):
+                assert np.all(s[:rho] > 0) and np.all(s[rho:] <= 1e-12 * max(s[0], 1e-300)), (name, kind, s[:rho + 2])
+                assert rho == 0 or s[0] <= 1e3 * s[rho - 1], (name, kind, s[:rho])
+            sp, tp = r64.sp[:rho + 1], r64.tp[:rho + 1]
+            with np.errstate(invalid="ignore"):
+                good = (sp < np.float32(own[0])) & (tp < np.float32(own[1]))
+            assert good[:rho].all() and not good[rho], (name, kind, sp, tp)
+            fin = np.isfinite(sp) & np.isfinite(tp)
+            assert fin[:rho].all() and R.margin_ok(sp[fin], tp[fin], own), (name, kind, sp, tp)
+            assert R.oracle_rank(r64, own, 1) == rho + 1, (name, kind)
+            print(f"\n{name} {kind}: sigma {sv[:rho]}, pooled and binned {sv_p[:rho]}, oracle ranks "
+                  f"{[R.oracle_rank(r64, own, mf) for mf in R.MAX_FAILS]}")
+        else:
+            live_pixels = 72 if kind == "deadrows" else d
+            assert np.linalg.matrix_rank(X) == min(live_pixels, T), (name, kind)
+            sig = np.linalg.norm(r64.v, axis=1)
+            _, strong, sep = R.separation(sig)
+            assert sep.sum() >= 3, (name, kind, int(sep.sum()))
+            r32 = refs[t]["f32s"]
+            s0 = R.block_s0(name, t)
+            assert R.vector_K(r32.u, r64.u, sig, s0, sep, 0) > 0 and R.vector_K(r32.v, r64.v, sig, s0, sep, 1) > 0
+            for m in R.MODES:
+                assert R.margin_ok(refs[t][m].sp[strong], refs[t][m].tp[strong], own), (name, kind, m)

@@ -1,12 +1,13 @@
 """
 Inputs and float64 restatements shared by the tests of the first temporal window of the tile stage (test infrastructure
 only): tests/test_tile_stage_ref.py proves on the CPU, from the oracles alone, that the inputs are admissible;
-tests/test_gpu_tile_kernels_wide.py and tests/test_gpu_tile_stage.py run the device on them.
+tests/test_gpu_tile_kernels_wide.py, tests/test_gpu_tile_stage.py and tests/test_gpu_tile_degenerate.py run the device on them.
 
 Two parts:
   - the Cholesky whitening of the 64-row path (small_chol_kernel): its inputs and the pivot rule restated in NumPy;
   - planted movies for pmd_tiles_decompose, the float64 / fp32 oracles of every tile (oracle.pmd_oracle.single_block_md),
-    the separation criteria and the error measure K.
+    the separation criteria and the error measure K; the family of degenerate tiles (DEGENERATE, KINDS);
+  - the device call of pmd_tiles_decompose with its guard tiles (device_run) and the exact check of its decisions.
 """
 import contextlib
 import functools
@@ -140,9 +141,85 @@ MIN_SEPARATED = {"A": (30, 0, 0), "B": (30, 0, 0), "C": (30, 5, 0), "D": (30, 5,
 MANY_CALLS = (4095, 4096)
 MANY_SAMPLE = 64
 
+# Degenerate tiles: constant, dead and low-rank content next to ordinary tiles in one launch.  The tiles are disjoint, tile t is
+# rows [t d, (t + 1) d) of one pixel-major matrix (pixel q = i + b1 j of the tile).  The first four kinds hold small integers
+# (every value, product and rank exact in fp32); RHO is their rank.  "live" is an ordinary planted tile (planted() with K
+# components), "deadrows" one with image rows 4-5 and image column 0 zeroed.
+KINDS = ("zero", "low3", "rank1", "sparse2", "deadrows", "live", "live")
+RHO = {"zero": 0, "low3": 3, "rank1": 1, "sparse2": 2}
+LIVE_TILES = (5, 6)
+# The spatial threshold stands above the statistic of a single live pixel (20 / 9: "sparse2" has two such pixels), the
+# temporal one in the widest gap of the float64 oracle's temporal statistics over all tiles (Zn: 0.53 | 1.11, Zw: 0.97 | 1.31):
+# the null directions fail on the temporal statistic.
+DEGENERATE = {
+    "Zn": dict(block=(10, 10), T=96, a=4, pool=2, r=6, K=12, ratio=0.7, noise=0.01, thr=(2.5, 0.76)),
+    "Zw": dict(block=(10, 10), T=400, a=4, pool=1, r=60, K=100, ratio=0.96, noise=0.01, thr=(2.5, 1.12)),
+}
+SCALES = (2.0 ** 24, 2.0 ** -24)
+
+
+def _sinusoid(T, amp, cycles, phase):
+    return np.round(amp * np.sin(2.0 * np.pi * cycles * np.arange(T) / T + phase))
+
+
+def _bump(b1, b2, amp, ci, cj, width):
+    i, j = np.meshgrid(np.arange(b1), np.arange(b2), indexing="ij")
+    return np.round(amp * np.exp(-((i - ci) ** 2 + (j - cj) ** 2) / (2.0 * width ** 2)))
+
+
+@functools.lru_cache(maxsize=None)
+def degenerate_rows(name):
+    """(len(KINDS) d, T) float32: the tiles of KINDS one behind the other."""
+    c = DEGENERATE[name]
+    (b1, b2), T = c["block"], c["T"]
+    d = b1 * b2
+    out = np.zeros((len(KINDS), d, T), dtype=np.float64)
+    for t, kind in enumerate(KINDS):
+        if kind == "low3":
+            F = np.stack([_bump(b1, b2, 9, 3, 3, 2.0), _bump(b1, b2, 9, 6, 7, 2.5), np.ones((b1, b2))]).reshape((3, d), order="F")
+            B = np.stack([_sinusoid(T, 12, 1, 0.0), _sinusoid(T, 12, 2, np.pi / 2), _sinusoid(T, 12, 3, 0.5)])
+            out[t] = F.T @ B
+        elif kind == "rank1":
+            out[t] = _sinusoid(T, 40, 2, 0.3)[None, :]
+        elif kind == "sparse2":
+            out[t, 2 + b1 * 3] = _sinusoid(T, 50, 1.5, 0.0)
+            out[t, 7 + b1 * 6] = _sinusoid(T, 30, 2.5, np.pi / 2)
+        elif kind in ("deadrows", "live"):
+            rng = np.random.default_rng(zlib.crc32(f"tile-stage/{name}/{t}".encode()))
+            blk = planted((b1, b2), T, c["K"], c["ratio"], c["noise"], rng)
+            if kind == "deadrows":
+                blk[4:6, :, :] = 0
+                blk[:, 0, :] = 0
+            out[t] = blk.reshape((d, T), order="F")
+    assert np.abs(out[:4]).max() < 2 ** 12 and np.array_equal(out[:4], np.round(out[:4]))
+    return np.ascontiguousarray(out.reshape(len(KINDS) * d, T), dtype=np.float32)
+
+
+def pooled_binned(name, t):
+    """The pooled, temporally binned block of tile t as single_block_md forms it, float64 (pooled pixels, bins)."""
+    c = cfg(name)
+    block = tile_block(name, t).astype(np.float64)
+    with O.arbiter_precision():
+        pooled = O.downsample_average_pooling(block, c["pool"])
+    return np.mean(np.reshape(pooled, (pooled.shape[0] * pooled.shape[1], c["a"], block.shape[2] // c["a"]), order="F"), axis=1)
+
+
+def oracle_rank(ref, thr, max_fail):
+    """Components that filter_by_failures keeps from the statistics of an oracle tile (a NaN statistic fails)."""
+    with np.errstate(invalid="ignore"):
+        good = (ref.sp < np.float32(thr[0])) & (ref.tp < np.float32(thr[1]))
+    return int(O.filter_by_failures(good.copy(), max_fail).sum())
+
+
+def cfg(name):
+    """The entry of CASES or of DEGENERATE (below) under that name."""
+    return CASES[name] if name in CASES else DEGENERATE[name]
+
 
 def case_dims(name):
-    c = CASES[name]
+    c = cfg(name)
+    if name in DEGENERATE:
+        return (c["block"][0], c["block"][1] * len(KINDS)), c["block"], c["T"]
     m = MOVIES[c["movie"]]
     return m["fov"], c["block"], m["T"]
 
@@ -150,21 +227,18 @@ def case_dims(name):
 def r_eff(name):
     """min(r, bins, pooled pixels): the components that exist (decomposition.py:59-73: u_final[:, :rank] of a sketch
     of r + 10 columns)."""
-    c = CASES[name]
+    c = cfg(name)
     (_, _), (b1, b2), T = case_dims(name)
     pooled = -(-b1 // c["pool"]) * -(-b2 // c["pool"])
     return min(c["r"], T // c["a"], pooled)
 
 
-@functools.lru_cache(maxsize=None)
-def planted_movie(movie):
+def planted(fov, T, K, ratio, noise, rng):
     """X = F diag(amp) B sqrt(D T) + noise N(0, 1), float32 (d1, d2, T): F unit-norm fields and B unit-norm traces, the
     first six smooth (Gaussian filtered) except the second field, which is white like every later one; amp_k = ratio^k."""
     from scipy.ndimage import gaussian_filter, gaussian_filter1d
 
-    m = MOVIES[movie]
-    (d1, d2), T, K = m["fov"], m["T"], m["K"]
-    rng = np.random.default_rng(zlib.crc32(f"tile-stage/{movie}".encode()))
+    d1, d2 = fov
     D = d1 * d2
     F = rng.standard_normal((K, d1, d2))
     B = rng.standard_normal((K, T))
@@ -175,9 +249,16 @@ def planted_movie(movie):
     F = F.reshape(K, D)
     F /= np.linalg.norm(F, axis=1, keepdims=True)
     B /= np.linalg.norm(B, axis=1, keepdims=True)
-    amp = m["ratio"] ** np.arange(K)
-    X = (F.T * amp) @ B * np.sqrt(D * T) + m["noise"] * rng.standard_normal((D, T))
+    amp = ratio ** np.arange(K)
+    X = (F.T * amp) @ B * np.sqrt(D * T) + noise * rng.standard_normal((D, T))
     return np.ascontiguousarray(X.reshape(d1, d2, T), dtype=np.float32)
+
+
+@functools.lru_cache(maxsize=None)
+def planted_movie(movie):
+    """The planted movie of MOVIES[movie] (see planted), float32 (d1, d2, T)."""
+    m = MOVIES[movie]
+    return planted(m["fov"], m["T"], m["K"], m["ratio"], m["noise"], np.random.default_rng(zlib.crc32(f"tile-stage/{movie}".encode())))
 
 
 @functools.lru_cache(maxsize=None)
@@ -185,6 +266,9 @@ def tiles(name):
     """(pix (n, d) int32, origins (n, 2)): the driver's overlapping grid; the many-tiles case has an origin at every pixel
     offset 0 .. 64 of both dimensions (4225 tiles)."""
     fov, block, _ = case_dims(name)
+    if name in DEGENERATE:
+        d = block[0] * block[1]
+        return np.arange(len(KINDS) * d, dtype=np.int32).reshape(len(KINDS), d), np.zeros((len(KINDS), 2), dtype=np.int64)
     if name == "many":
         it1 = it2 = list(range(fov[0] - block[0] + 1))
     else:
@@ -194,6 +278,15 @@ def tiles(name):
     return pix, origins
 
 
+@functools.lru_cache(maxsize=None)
+def movie_rows(name):
+    """The pixel-major matrix (D, T) float32 that the tile table of a case indexes."""
+    if name in DEGENERATE:
+        return degenerate_rows(name)
+    fov, _, T = case_dims(name)
+    return planted_movie(CASES[name]["movie"]).reshape(fov[0] * fov[1], T)
+
+
 def omega_indices(name):
     """omega_index0 and omega_index_step as the driver forms them (t_lo * n_win + widx, n_win)."""
     n_win = 2 + len(name) % 3
@@ -201,14 +294,17 @@ def omega_indices(name):
 
 
 def omega_of_tile(src, name, t):
-    c = CASES[name]
+    c = cfg(name)
     _, _, T = case_dims(name)
     i0, step = omega_indices(name)
     return src.omega(philox.STREAM_TILE_OMEGA, i0 + t * step, T // c["a"], c["r"] + 10)
 
 
 def tile_block(name, t):
-    fov, (b1, b2), _ = case_dims(name)
+    fov, (b1, b2), T = case_dims(name)
+    if name in DEGENERATE:
+        d = b1 * b2
+        return degenerate_rows(name)[t * d:(t + 1) * d].reshape((b1, b2, T), order="F")
     k, j = tiles(name)[1][t]
     return planted_movie(CASES[name]["movie"])[k:k + b1, j:j + b2, :]
 
@@ -234,7 +330,7 @@ def oracle_tile(name, t, omega, mode):
     """single_block_md of tile t.  u (d, r_eff), v (r_eff, T) = sigma V, the two statistics, and the two intermediate
     arrays the denoiser hooks see: v_ds (r_eff, T) and S = block_2d v_mat_basis^T (d, r_eff), and s_ds, the singular values
     of the pooled, binned block."""
-    c = CASES[name]
+    c = cfg(name)
     block = tile_block(name, t)
     seen = {}
 
@@ -312,7 +408,7 @@ def margin_ok(sp, tp, thr):
 
 def thresholds(name):
     """The case's own pair, rounded to fp32 (the device takes floats), and the pair that passes everything."""
-    s, t = CASES[name]["thr"]
+    s, t = cfg(name)["thr"]
     return [(float(np.float32(s)), float(np.float32(t))), PASS_ALL]
 
 
@@ -408,3 +504,130 @@ def block_s0(name, t):
     """Largest singular value of the tile's block."""
     b = tile_block(name, t)
     return float(np.linalg.norm(b.reshape((b.shape[0] * b.shape[1], -1), order="F").astype(np.float64), 2))
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# pmd_tiles_decompose on the device (used by the tests marked gpu only; torch is imported where it is needed)
+# ------------------------------------------------------------------------------------------------------------------
+def _t():
+    import torch
+
+    return torch
+
+
+def P(t):
+    from localmd_amd._lib import ptr
+
+    return ptr(t)
+
+
+def to_device(ctx, a, dtype=None):
+    return _t().from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(ctx.device)
+
+
+def poisoned(ctx, shape, dtype):
+    """A device array whose every byte is 0xFF (NaN in both float types, -1 as int32)."""
+    torch = _t()
+    x = torch.empty(shape, dtype=dtype, device=ctx.device)
+    x.view(torch.uint8).fill_(0xFF)
+    return x
+
+
+def untouched(t):
+    return bool((t.contiguous().view(_t().uint8) == 0xFF).all())
+
+
+class Run:
+    pass
+
+
+def device_run(ctx, name, thr, max_fail, n_tiles=None, staged=False, download=True, scale=1.0, first_tile=0):
+    """One pmd_tiles_decompose call as the driver makes it (staged: pmd_tiles_decompose_staged with stages 1, 2, 4 and
+    the hook arrays read between the calls), on a workspace and outputs full of NaN bytes, a guard tile behind the last
+    one of every output.  The call holds the tiles first_tile .. first_tile + n_tiles - 1 of the case with the sketch
+    matrices they have in the call of all tiles; the movie is multiplied by scale (a power of two)."""
+    import ctypes
+
+    torch, lib = _t(), ctx.lib
+    c = cfg(name)
+    (d1, d2), (b1, b2), T = case_dims(name)
+    a, r, D, d = c["a"], c["r"], d1 * d2, b1 * b2
+    pix_all, _ = tiles(name)
+    n = len(pix_all) - first_tile if n_tiles is None else n_tiles
+    assert first_tile + n <= len(pix_all)
+    pool_q, pool_idx, pool_w, _ = grid.pooling_maps((b1, b2), c["pool"])
+    Pn = pool_q.shape[0]
+    rp, dpad, ld = int(lib.pmd_tile_rpad(r)), int(lib.pmd_tile_dpad(d)), int(lib.pmd_time_ld(T))
+    xf = torch.zeros((D, ld), dtype=torch.float32, device=ctx.device)
+    xf[:, :T] = to_device(ctx, movie_rows(name) * np.float32(scale))
+    out = Run()
+    out.n, out.rp, out.d, out.T, out.re = n, rp, d, T, r_eff(name)
+    out.ut = poisoned(ctx, (n + 1, rp, dpad), torch.float32)
+    out.v = poisoned(ctx, (n + 1, rp, ld), torch.float32)
+    out.stats = poisoned(ctx, (n + 1, rp, 2), torch.float32)
+    out.good = poisoned(ctx, (n + 1, rp), torch.int32)
+    out.keep = poisoned(ctx, (n + 1, rp), torch.int32)
+    out.ranks = poisoned(ctx, (n + 1,), torch.int32)
+    out.lam = poisoned(ctx, (n + 1, rp), torch.float64)
+    nbytes = int(lib.pmd_tiles_workspace_bytes(n, b1, b2, Pn, r, a, T, ld, D))
+    assert nbytes > 0
+    ws = ctx.workspace(nbytes)
+    ws.fill_(0xFF)
+    i0, step = omega_indices(name)
+    tables = [to_device(ctx, pix_all[first_tile:first_tile + n], np.int32), to_device(ctx, pool_q, np.int32),
+              to_device(ctx, pool_idx, np.int32), to_device(ctx, pool_w, np.float32)]
+    args = (P(xf), ld, D, T, P(tables[0]), n, b1, b2, P(tables[1]), pool_q.shape[1], Pn, P(tables[2]), P(tables[3]), r, a,
+            float(thr[0]), float(thr[1]), max_fail, SEED, i0 + first_tile * step, step, P(out.ut), P(out.v), ld, P(out.stats),
+            P(out.good), P(out.keep), P(out.ranks), P(out.lam), P(ws), ws.numel())
+    if not staged:
+        ctx.call("pmd_tiles_decompose", *args)
+    else:
+        off_v, off_s = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        assert lib.pmd_tiles_hook_offsets(n, b1, b2, Pn, r, a, T, ld, D, ctypes.byref(off_v), ctypes.byref(off_s)) == 0
+        assert off_v.value + n * rp * ld * 4 <= nbytes and off_s.value + n * rp * dpad * 4 <= nbytes
+        ctx.call("pmd_tiles_decompose_staged", *args, 1)
+        ctx.sync()
+        out.v_ds = ws[off_v.value:off_v.value + n * rp * ld * 4].view(torch.float32).view(n, rp, ld)[:, :out.re, :T].cpu().numpy()
+        ctx.call("pmd_tiles_decompose_staged", *args, 2)
+        ctx.sync()
+        out.S = ws[off_s.value:off_s.value + n * rp * dpad * 4].view(torch.float32).view(n, rp, dpad)[:, :out.re, :d].cpu().numpy()
+        ctx.call("pmd_tiles_decompose_staged", *args, 4)
+    ctx.sync()
+    # what must hold after every call, checked where the arrays are: the guard tiles, and zeros from r_eff on
+    re = out.re
+    for arr in (out.ut, out.v, out.stats, out.good, out.keep, out.ranks, out.lam):
+        assert untouched(arr[n:n + 1]), "guard tile written"
+    assert not bool((out.ut[:n, re:] != 0).any()), "rows of Ut from r_eff on"
+    assert not bool((out.v[:n, re:, :T] != 0).any()), "rows of V from r_eff on"
+    assert not bool((out.stats[:n, re:] != 0).any()), "rows of stats from r_eff on"
+    assert not bool((out.good[:n, re:] != 0).any()) and not bool((out.keep[:n, re:] != 0).any())
+    assert not bool((out.lam[:n, re:] != 0).any()), "lam_out from r_eff on"
+    assert not bool((out.ut[:n, :, d:] != 0).any()), "padding of Ut"
+    out.dev_ut, out.dev_v = out.ut, out.v
+    out.stats, out.good, out.keep = out.stats[:n].cpu().numpy(), out.good[:n].cpu().numpy(), out.keep[:n].cpu().numpy()
+    out.ranks, out.lam = out.ranks[:n].cpu().numpy(), out.lam[:n].cpu().numpy()
+    if download:
+        out.ut, out.v = out.ut[:n, :re, :d].cpu().numpy(), out.v[:n, :re, :T].cpu().numpy()
+    else:
+        out.ut = out.v = None
+    return out
+
+
+def check_decisions(name, run, thr, max_fail, patterns):
+    """good, keep and ranks follow exactly from the statistics the device returned (no knife edge enters; a NaN statistic
+    is a failure, as in the reference's comparison)."""
+    re = run.re
+    thr32 = (np.float32(thr[0]), np.float32(thr[1]))
+    sp, tp = run.stats[:, :re, 0], run.stats[:, :re, 1]
+    with np.errstate(invalid="ignore"):
+        good = (sp < thr32[0]) & (tp < thr32[1])
+    np.testing.assert_array_equal(run.good[:, :re], good.astype(np.int32), err_msg=f"{name} {thr} {max_fail}")
+    for t in range(run.n):
+        kept = O.filter_by_failures(good[t].copy(), max_fail)
+        np.testing.assert_array_equal(run.keep[t, :re], kept.astype(np.int32), err_msg=f"{name} tile {t}")
+        nk = int(kept.sum())
+        assert run.ranks[t] == nk, (name, t, run.ranks[t], nk)
+        if np.any(good[t, 1:nk] & ~good[t, :nk - 1][:len(good[t, 1:nk])]):
+            patterns.add("pass after a failure")
+        if nk < re:
+            patterns.add("cut by max_fail")
