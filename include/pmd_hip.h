@@ -690,19 +690,62 @@ int pmd_transpose_affine(pmd_ctx* ctx, const float* src, long lds_, long rows, i
                          const float* shift, float* dst, long ldd);
 
 /* ---- kernel-level entry points (used by the parity tests; same kernels as above) ---------- */
+/* The four contractions of csrc/tile_gemm.hip.  Every per-tile [comp][x] array has 64 rows, all of which exist.  Pixel q of
+ * a tile is row pix[tile * pix_stride + q] of X (entries q >= d of a pix row are never looked at), or row
+ * tile * row0_stride + q when pix is NULL.  X and every per-tile array are 16-byte aligned with leading dimensions and tile
+ * strides that are multiples of 4 floats, unless a paragraph says otherwise.  tests/test_gpu_tile_contractions.py pins what
+ * follows.
+ *
+ * tile_atx:  Out[tile][c][t] = sum_{q < d} A[tile][c][q] X[pixel q][t],  c < 64, t < T.
+ *   A[tile][64][a_ld], a_ld >= pmd_tile_dpad(d), columns [d, pmd_tile_dpad(d)) ZERO (they meet pixel rows that are not the
+ *   tile's); a_tile_stride 0 shares one A between the tiles.
+ *   X is read in whole chunks of 32 frames: frames [0, round_up(T, 32)) of every pixel row are read (ldx at least that).  What
+ *   they hold from T on need not be zero, it only reaches the output columns of the same index.  For 256 < d <= 400 and
+ *   ldx >= 32 (ceil(T / 32) + 2) - pmd_time_ld(T) is - the LDS-DMA kernel runs and also fetches, and drops, up to two chunks
+ *   behind the last one; with a shorter ldx, or PMD_ATX_DMA=0, the register-staged kernel of the same shape runs.
+ *   Out[tile][64][ldo], ldo >= round_up(T, 32): all 64 rows, columns [0, round_up(T, 32)) are written, those from T on with
+ *   whatever the padding of X gives.  For d <= 1024 no other column is touched.  For d > 1024 the slices of 1024 pixels add
+ *   up by atomicAdd: the whole 64 x ldo block of every tile is cleared first, so columns from round_up(T, 32) on end as
+ *   zeros (no driver keeps anything there), and the rounding order, hence the last bit, may differ from run to run.
+ *   slices: the chunks are dealt to at most this many workgroups per tile. */
 int pmdk_tile_atx(pmd_ctx* ctx, const float* X, long ldx, const int* pix, int pix_stride, long row0_stride, int d,
                   const float* A, long a_tile_stride, int a_ld, float* Out, long out_tile_stride, long ldo, int n_tiles,
                   int T, int slices);
-/* the same with the number of rows of A that carry data (rows >= `rows` are zero): <= 16 rows on 1024-pixel tiles and 33-50 rows
- * on 257-400-pixel tiles run specialised kernels that leave the output rows beyond the last 16-row tile they touch unwritten */
+/* the same with the number of rows of A that carry data (rows >= `rows` are zero): <= 16 rows on tiles of 801 to 1024
+ * pixels run a specialised kernel that leaves rows >= 16 of Out unwritten; any other hint changes nothing */
 int pmdk_tile_atx_rows(pmd_ctx* ctx, const float* X, long ldx, const int* pix, int pix_stride, long row0_stride, int d,
                        const float* A, long a_tile_stride, int a_ld, float* Out, long out_tile_stride, long ldo, int n_tiles,
                        int T, int slices, int rows);
+/* tile_xbt:  sum_slice S[tile][slice][c][q] = sum_{t < T} B[tile][c][t] X[pixel q][t],  c < 64, q < d.
+ *   B[tile][64][ldb] (b_tile_stride 0: shared).  Both operands are read in whole groups of 16 frames and nothing is masked
+ *   along time: frames [0, round_up(T, 16)) of the d pixel rows and of all 64 rows of B are read, nothing behind them.  In
+ *   frames [T, round_up(T, 16)) X must be ZERO - the drivers clear every movie copy behind its last fitted frame - and B must
+ *   be finite; B need not be zero there (a trace array keeps there whatever tile_atx left).
+ *   S[tile][slices][64][s_ld], s_ld >= 16 ceil(d / 16): the frame groups are dealt to at most `slices` slices and the caller
+ *   sums all the slices it asked for.  A slice with work gets rows 0..63, columns [0, 16 ceil(d / 16)), zeros in columns
+ *   >= d, and keeps the rest of its rows; slices without work (there are fewer frame groups than slices, or their rounded-up
+ *   share leaves the last slices none: T = 133 on four slices fills three) are cleared over their whole s_slice_stride.
+ *   s_slice_stride 0 is for slices = 1. */
 int pmdk_tile_xbt(pmd_ctx* ctx, const float* X, long ldx, const int* pix, int pix_stride, long row0_stride, int d,
                   const float* B, long b_tile_stride, long ldb, float* S, long s_tile_stride, long s_slice_stride,
                   int s_ld, int n_tiles, int T, int slices);
+/* tile_gram:  sum_slice G[tile][slice][i][j] = sum_{x < len} In[tile][i][x] In[tile][j][x]  in fp64,  i, j < 64.
+ *   In[tile][64][ld], ld >= len: all 64 rows are read, never outside [0, ld) of a row, and positions >= len are masked: they
+ *   may hold anything, NaN included.  Any ld, tile_stride and alignment is served (the fp64-MFMA kernel needs ld % 4 == 0,
+ *   ld >= 16, tile_stride % 4 == 0 and a 16-byte aligned base; the scalar kernel takes the rest, and everything under
+ *   PMD_GRAM_MFMA=0).
+ *   G[tile][slices][64][64] doubles: every slice is written in full; slice s covers positions
+ *   [s c, (s + 1) c), c = round_up(ceil(len / slices), 32), and is zero when that range is empty.  The sum over the slices
+ *   is symmetric to the bit. */
 int pmdk_tile_gram(pmd_ctx* ctx, const float* In, long tile_stride, long ld, int len, int n_tiles, int slices,
                    double* G);
+/* tile_rowmix:  Out[tile][c][x] = (float) sum_{c' < n_in} N[tile][c'][c] In[tile][c'][x]  (fp64 sum, one rounding),
+ *   c < n_out, x < len; rows [n_out, 64) of Out are set to zero up to len; nothing from len on is written.
+ *   N[tile][64][64] doubles (n_tile_stride 0: shared): the whole block is read, entries outside n_in x n_out are masked.
+ *   In[tile][64][ld_in]: all 64 rows are read, rows >= n_in masked; positions < len, and in the 64-position MFMA kernel
+ *   < round_up(len, 4) (it runs only when ld_in holds them), those from len on without effect.  Masked entries may hold
+ *   anything, NaN included.  Out == In with equal strides is allowed.  Any ld and alignment is served: without 16-byte
+ *   aligned rows, or with len < 4, the 64-position kernel gives way to the 16-position one. */
 int pmdk_tile_rowmix(pmd_ctx* ctx, const float* In, long in_tile_stride, long ld_in, const double* N,
                      long n_tile_stride, int n_in, int n_out, float* Out, long out_tile_stride, long ld_out, int len,
                      int n_tiles);
