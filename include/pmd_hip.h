@@ -749,8 +749,42 @@ int pmdk_tile_gram(pmd_ctx* ctx, const float* In, long tile_stride, long ld, int
 int pmdk_tile_rowmix(pmd_ctx* ctx, const float* In, long in_tile_stride, long ld_in, const double* N,
                      long n_tile_stride, int n_in, int n_out, float* Out, long out_tile_stride, long ld_out, int len,
                      int n_tiles);
+/* The other kernels of the 64-row main path (csrc/small_la.hip and the pooling part of csrc/prep.hip).
+ * tests/test_gpu_tile_small_la.py pins the four paragraphs that follow; tests/small_la_ref.py derives their bounds.
+ *
+ * small_qr:  Qt[tile][c][q] = Q[q][c] of the reduced Householder QR of the P x l matrix Y[q][c] = Yt[tile][c][q],
+ *   c < nref = min(P, l), q < P, with LAPACK's conventions (dgeqr2 + dorg2r: beta = -sign(alpha) norm), so that on a matrix
+ *   of full rank the columns agree with LAPACK's sign included.  One workgroup per tile.
+ *   Read: rows c < l, columns q < P of every Yt tile, nothing else (any y_ld >= P, any y_tile_stride, no alignment).
+ *   Written: rows c < nref, columns q < P of every Qt tile.  Rows [nref, 64), columns [P, q_ld) and whatever lies between
+ *   the tiles are left alone: a caller that wants zeros there clears the buffer first.
+ *   Storage: the matrix is held in LDS with the odd leading dimension ldm = P | 1, in fp64 while
+ *   l ldm 8 + 2608 <= 150 KB (l = 60: P <= 313), in fp32 beyond that (every store to it then rounds to fp32; the arithmetic
+ *   stays fp64), and l ldm 4 + 2608 <= 160 KB must hold (l = 64: P <= 629).  l > 64 or a matrix that does not fit:
+ *   PMD_ERR_UNSUPPORTED, nothing is launched or written, the context stays usable.
+ *   Dependence rule: a column of which, after the earlier reflectors, no more than left^2 <= dep_tol |column as loaded|^2
+ *   remains (dep_tol 1e-24 in fp64 storage, 1e-12 in fp32 storage), or exactly nothing below its diagonal, gets tau = 0: its
+ *   Q column is the unit vector under the earlier reflectors.  Q has nref orthonormal columns whatever the rank, and Y = Q Q^T Y
+ *   up to sqrt(dep_tol) of a column's norm.  The rule is relative and every operation is exact under a power-of-two scale:
+ *   Y 2^k gives the same bits (short of overflow and underflow). */
 int pmdk_small_qr(pmd_ctx* ctx, const float* Yt, long y_tile_stride, int y_ld, int P, int l, float* Qt,
                   long q_tile_stride, int q_ld, int n_tiles);
+/* small_eig:  eigendecomposition of M[tile] = 1/2 sum_k (G_k + G_k^T), the leading n x n blocks of the `slices` 64 x 64
+ *   blocks of G[tile][slices][64][64] summed in their order and symmetrised; 1 <= n <= 64 (else PMD_ERR_UNSUPPORTED).
+ *   Read: the leading n x n block of every slice, nothing outside it (the default kernel; under PMD_SMALL_EIG=rocsolver the
+ *   batch goes through pmdk_wide_eig at rp = 64, which reads the same entries).  The block must be FINITE: a NaN or Inf in
+ *   it is not detected and the output is then undefined.
+ *   Written: all of Nout[tile][64][64] and lam_out[tile][64].  lam_out[c], c < n: the eigenvalues in descending order;
+ *   Nout[c'][c]: component c' of the eigenvector of lam_out[c]; exact zeros outside n x n and in lam_out from n on.
+ *   mode 0: the orthonormal eigenvectors.
+ *   mode 2: the same columns, those with lam_c <= tol lam_0 or lam_c <= 0 zeroed (lam_0 is the largest eigenvalue, signed:
+ *           a matrix without a positive eigenvalue gives all zeros; tol = 0 still drops every non-positive direction).
+ *   mode 1: the kept columns of mode 2 times 1 / sqrt(lam_c): N^T M N = I on them.
+ *   The rule is applied to the eigenvalues as returned, so an eigenvalue that is zero in exact arithmetic and comes out as
+ *   +1e-17 lam_0 is kept at tol = 0; callers pass a tol well above the solver's accuracy (1e-12 max|lam| absolute).
+ *   Default kernel: one wave per problem, Householder tridiagonalisation (a column with nothing below its subdiagonal
+ *   is passed over: diagonal and tridiagonal input), Q formed in place, implicit QL with accumulated rotations.  Kept
+ *   columns of mode 2 are those of mode 0 bit for bit, those of mode 1 differ from column / sqrt(lam) by three roundings. */
 int pmdk_small_eig(pmd_ctx* ctx, const double* G, int slices, int n, int mode, double tol, double* Nout,
                    double* lam_out, int n_tiles);
 /* Cholesky whitening of the 64-row path: G[tile][slices][64][64], Nout[tile][64][64] = inverse of the upper factor of the
@@ -767,9 +801,33 @@ int pmdk_wide_eig(pmd_ctx* ctx, const double* G, int slices, int rp, int n, int 
 /* pmdk_tile_rowmix at any rp: N[tile][rp][rp] (n_tile_stride 0: shared); rows [n_out, rp) of Out are zeroed up to len */
 int pmdk_wide_rowmix(pmd_ctx* ctx, const float* In, long in_tile_stride, long ld_in, const double* N, long n_tile_stride,
                      int rp, int n_in, int n_out, float* Out, long out_tile_stride, long ld_out, int len, int n_tiles);
+/* tile_pool_bin:  xbar[c][cb] = mean_{tau < a} X[c][a cb + tau],  c < n_rows, cb < nbins  (scratch, ld_ab floats a row);
+ *   abar[tile][p][cb] = mean over the pixels q of window p of xbar[pix[tile d + q]][cb],  p < P, cb < nbins, where window p
+ *   is the entries >= 0 of pool_q[p][0 .. pool_max) (local pixel ids, -1 = padding; every window has at least one pixel).
+ *   Read: frames [0, a nbins) of the n_rows rows of X - frames behind them, the remainder of T / a included, are never
+ *   read -, all of pix and pool_q.  Written: columns [0, nbins) of rows [0, n_rows) of xbar and of rows [0, P) of every abar
+ *   tile (abar[tile] starts at tile * tile_stride, row p at p * ld_ab); columns from nbins on, rows of xbar from n_rows on
+ *   and whatever lies between the tiles are left alone.  Any n_rows, n_tiles and nbins (launch chunks of 32768 rows / tiles,
+ *   a grid-stride loop over the bins).
+ *   Summation order, fp32 throughout: a bin is summed frame by frame from zero and multiplied by the rounded 1 / a; a window
+ *   is summed in the order of pool_q from zero and multiplied by the rounded 1 / count.  Hence
+ *   |xbar - exact| <= (a + 1) 2^-24 mean|x| and |abar - exact| <= (a + count + 2) 2^-24 (window mean of the bin means of |x|),
+ *   and small integers with a and every count a power of two come out exact. */
 int pmdk_tile_pool_bin(pmd_ctx* ctx, const float* X, long ldx, long n_rows, const int* pix, int n_tiles, int d,
                        const int* pool_q, int pool_max, int P, int a, int nbins, float* xbar, float* abar, long ld_ab,
                        long tile_stride);
+/* roughness:  stats[tile][c][0] = spatial, stats[tile][c][1] = temporal roughness statistic of component c < r
+ *   (evaluation.py:84-126): the mean absolute difference of vertical and horizontal neighbours of the b1 x b2 image
+ *   Ut[tile][c][i + b1 j] over the mean absolute pixel, and mean_{0 < t < T - 1} |v[t-1] + v[t+1] - 2 v[t]| over mean_t |v[t]|
+ *   of the trace v = V[tile][c][.].  An all-zero row gives NaN (0 / 0), as the reference does; T >= 3 and b1 b2 >= 2.
+ *   Read: columns [0, b1 b2) of rows c < r of Ut, columns [0, T) of rows c < r of V; nothing behind them, no other row.
+ *   Written: stats[tile][c][.] for c < r only, rows [r, 64) are left alone (the keep/discard scan clears them); with
+ *   Ut == NULL only the temporal, with V == NULL only the spatial statistic is written.
+ *   Summation order, fp32 throughout: spatial - one wave, lane k adds the terms of pixels k, k + 64, .. (ceil(b1 b2 / 64)
+ *   terms), six butterfly steps, then sum of the two difference sums, the two divisions by the counts and the quotient;
+ *   temporal - 256 threads, thread k adds frames k, k + 256, .., six butterfly steps in each wave, (w0 + w1) + (w2 + w3)
+ *   across the waves, the two divisions by T - 2 and T and the quotient.  The second difference is formed as
+ *   (v[t-1] + v[t+1]) - 2 v[t]: its rounding error is absolute in |v|, 2^-24 |v[t-1] + v[t+1]|, not relative to the result. */
 int pmdk_roughness(pmd_ctx* ctx, const float* Ut, long u_tile_stride, int u_ld, int b1, int b2, const float* V,
                    long v_tile_stride, long v_ld, int T, int r, float* stats, int n_tiles);
 int pmdk_syevd(pmd_ctx* ctx, int n, float* A, long lda, float* w, float* work, int* info);
