@@ -9,10 +9,30 @@
  * Conventions
  *   - every function returns int32: 0 = OK, negative = error; pmd_last_error(ctx) has the text
  *   - all pointers are DEVICE pointers owned by the caller unless the name ends in _host
- *   - all work is enqueued on the context's HIP stream; functions that must read a result on
- *     the host (pmd_orthogonalize, pmd_projected_svd) synchronise that stream themselves
- *   - scratch memory is a caller-provided workspace; *_workspace_bytes() sizes it
- *   - one context per (host thread, device); distinct contexts are independent
+ *   - all work is enqueued on the context's HIP stream (the one given to pmd_ctx_create or pmd_ctx_set_stream): own
+ *     kernels, memsets and copies, rocBLAS and rocSOLVER through the context's handle, hipBLASLt per call.  Nothing goes to
+ *     the null stream, so a caller may order a call behind its own work on that stream and nowhere else.
+ *     Functions that must read a result on the host synchronise that stream themselves, once or more: pmd_orthogonalize,
+ *     pmd_orthogonalize_factored, pmd_orthogonalize_chol, pmd_chol_inverse, pmd_projected_svd, pmd_projected_svd_factored,
+ *     pmd_psvd_finish, pmd_grid_components, pmdk_syevd, pmdk_sy2sb, pmdk_sytrd2, pmd_profile_query, pmd_ctx_sync; pmd_gemm
+ *     and pmd_gram_mtgm where they run fp16-piece products (the operands' exponents are read back); any call that grows
+ *     library-owned scratch (the eigensolver's, the split products'), pmd_scratch_trim when it frees some, and
+ *     pmd_comm_destroy.  Every other entry point only enqueues.
+ *   - scratch memory is a caller-provided workspace; *_workspace_bytes() (*_work_floats()) sizes it.  The workspace starts
+ *     on a 256-byte boundary (the library aligns offsets inside it, not addresses).  Its contents on entry are irrelevant
+ *     and nothing is kept in it between calls, except where an entry point says so (pmd_stats_stream_*, the staged tile
+ *     pipeline, the M^T copy of pmd_gram_mtgm).  A NULL or too-small workspace is refused with PMD_ERR_WORKSPACE (-3)
+ *     before anything is launched, written or copied: outputs, inputs and the workspace are as they were, and the context
+ *     stays usable (pmd_sliding_extremum / pmd_sliding_quantile report it as PMD_ERR_ARG, pmd_grid_components and the two
+ *     pmd_*_moments a NULL one, as any NULL pointer; the two correlations take any size from one frame's partials up).
+ *     Nothing outside [ws, ws + ws_bytes) is touched, and the result does not depend on how much more than the reported
+ *     size is passed.
+ *   - one context per (host thread, device); distinct contexts are independent, also when their streams run at the same
+ *     time.  A context owns device scratch that it grows on demand; pmd_scratch_trim frees that of the large products, and
+ *     neither growing nor trimming changes a result
+ *   (tests/test_gpu_abi_conventions.py: exact size, guard bands and contents for every entry point that takes a workspace
+ *   but pmd_sliding_extremum, whose own test has them; refusal and untouched outputs for the decomposition's stages, the
+ *   consumers' own tests hold theirs; the stream for every way the library reaches the GPU, not for every entry point.)
  *
  * Layouts
  *   movie        Y[t][c]            frames-first, c = i*d2 + j (what the dataset hands over)

@@ -161,6 +161,8 @@ __global__ __launch_bounds__(256) void chol_panel_kernel(float* __restrict__ P, 
 static int chol_lower_rm(pmd_ctx* ctx, int n, float* A, long ld, int* info, float* tmp, float* linv, int abs_last_pivot) {
   pmd_prof_scope prof__(ctx, "cholesky");
   PMD_HIP(ctx, hipMemsetAsync(info, 0, sizeof(int), ctx->stream));
+  // (belt and braces: strtri writes the whole block, zeros in the other triangle included, and chol_panel_kernel masks that
+  // triangle; no result depends on this clear)
   PMD_HIP(ctx, hipMemsetAsync(linv, 0, sizeof(float) * CHOL_NB * CHOL_NB, ctx->stream));
   const float one = 1.f, minus1 = -1.f;
   // PMD_CHOL_CHAIN=rocblas: the earlier chain (strtri on the block, panel by sgemm into a copy) for A/B runs
@@ -337,13 +339,13 @@ extern "C" int pmd_chol_inverse(pmd_ctx* ctx, float* C, int m, long ldc, int abs
   int* info = ar.take_n<int>(4);
   float* chol_tmp = ar.take_n<float>((size_t)m * CHOL_NB);
   float* chol_linv = ar.take_n<float>((size_t)CHOL_NB * CHOL_NB);
-  if (ar.overflow) return pmd_fail(ctx, PMD_ERR_WORKSPACE, "pmd_chol_inverse", "workspace too small");
+  const bool f64 = m <= CHOL_F64_MAX && m >= 1 && !ctx->routes.cholesky_rocsolver;
+  double* Cd = f64 ? ar.take_n<double>((size_t)m * m) : nullptr;
+  if (ar.overflow) return pmd_fail(ctx, PMD_ERR_WORKSPACE, "pmd_chol_inverse", "workspace too small");   // (*ok_host untouched)
   *ok_host = 0;
   int hinfo = 0;
-  if (m <= CHOL_F64_MAX && m >= 1 && !ctx->routes.cholesky_rocsolver) {
+  if (f64) {
     pmd_prof_scope prof__(ctx, "cholesky_f64");
-    double* Cd = ar.take_n<double>((size_t)m * m);
-    if (ar.overflow) return pmd_fail(ctx, PMD_ERR_WORKSPACE, "pmd_chol_inverse", "workspace too small");
     PMD_HIP(ctx, hipMemsetAsync(info, 0, 2 * sizeof(int), ctx->stream));
     hipLaunchKernelGGL(chol_widen_kernel, dim3((m + 255) / 256, m), dim3(256), 0, ctx->stream, C, ldc, Cd, (long)m, m);
     PMD_LAUNCH_CHECK(ctx, "chol_widen_kernel");
@@ -396,6 +398,9 @@ extern "C" int pmd_chol_inverse(pmd_ctx* ctx, float* C, int m, long ldc, int abs
 extern "C" int pmd_orthogonalize_chol(pmd_ctx* ctx, const float* M, int Rc, int m, long ldm, const float* GM, long ldgm,
                                       float* Et_out, long lde, int* ok_host, void* ws, size_t ws_bytes) {
   CTX_CHECK(ctx);
+  // both halves carve the same workspace: refuse one that the second half would refuse before the first has launched anything
+  if (!ws || ws_bytes < std::max(pmd_gram_mtgm_workspace_bytes(Rc, m), pmd_chol_inverse_workspace_bytes(m)))
+    return pmd_fail(ctx, PMD_ERR_WORKSPACE, "pmd_orthogonalize_chol", "workspace too small");
   RUN(pmd_gram_mtgm(ctx, M, Rc, m, ldm, GM, ldgm, Et_out, lde, ws, ws_bytes));
   return pmd_chol_inverse(ctx, Et_out, m, lde, 0, ok_host, ws, ws_bytes);
 }

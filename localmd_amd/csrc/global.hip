@@ -258,7 +258,7 @@ extern "C" size_t pmd_orthogonalize_workspace_bytes(int R, int m, int has_m) {
   b += (size_t)m * sizeof(float) * 4 + (size_t)m * sizeof(int) + 4096;  // w, work, scale, perm, info
   if (has_m) b += (size_t)R * m * sizeof(float) + (size_t)m * m * sizeof(float);  // GM, C
   b += (size_t)m * m * sizeof(float);                                             // Et
-  return b + 8192;
+  return b + 8192;   // slack by design: the 4096 above already covers the at most 8 x 255 bytes of arena padding
 }
 
 extern "C" int pmd_orthogonalize(pmd_ctx* ctx, float* G, int R, const float* M, int m, long ldm, float* P_out, long ldp,

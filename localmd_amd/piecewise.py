@@ -218,7 +218,7 @@ def patch_workspace_bytes(n, pg):
     ey, ex = pg.max_deviation
     tiles = -(-pg.patch[0] // TILE_ROWS) * -(-pg.patch[1] // TILE_COLS)
     per = 4 * pg.P * tiles * (2 * ey + 1) * (2 * ex + 1)
-    return max(1, min(int(n), WS_TARGET // per)) * per
+    return max(1, min(int(n), WS_TARGET // per)) * per if int(n) >= 1 else 0     # (the library sizes no frames at 0)
 
 
 def surface_frames(m, pg):

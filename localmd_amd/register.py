@@ -193,7 +193,7 @@ def correlate_workspace_bytes(n, d1, d2, my, mx):
     """pmd_shift_correlate_workspace_bytes on the host: the tile partials of min(n, 64 MB worth of) frames."""
     tiles = -(-(d1 - 2 * my) // TILE_ROWS) * -(-(d2 - 2 * mx) // TILE_COLS)
     per = 4 * tiles * (2 * my + 1) * (2 * mx + 1)
-    return max(1, min(int(n), WS_TARGET // per)) * per
+    return max(1, min(int(n), WS_TARGET // per)) * per if int(n) >= 1 else 0     # (the library sizes no frames at 0)
 
 
 def register_device_bytes(*, d1, d2, nb, esize, host_source, n_batches, my=None, mx=None, n_sample=0, out_esize=0,
