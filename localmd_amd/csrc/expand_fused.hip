@@ -148,7 +148,7 @@ int pmd_group_expand(pmd_ctx* ctx, const float* C, long ldc, int n, int d1, int 
   if (!mean || !std || !patch_ptr || !out || (needs_y && !Y) || (n_entries > 0 && (!C || !entries || !qmap || !A)))
     return pmd_fail(ctx, PMD_ERR_ARG, what, "null pointer");
   if (needs_y && ldy < D) return pmd_fail(ctx, PMD_ERR_ARG, what, "ldy < d1 d2");
-  const long n_fb = (n + EX_FB - 1) / EX_FB;
+  const long n_fb = ((long)n + EX_FB - 1) / EX_FB;   // (in long: n + 63 overflows an int from 2^31 - 64 on)
   if (n_patches > 0x7fffffffL || n_fb > 65535) return pmd_fail(ctx, PMD_ERR_ARG, what, "too many patches / frames in one call");
   pmd_prof_scope prof__(ctx, "group_expand");
   const dim3 grid((unsigned)n_patches, (unsigned)n_fb);

@@ -149,7 +149,7 @@ int pmd_group_project(pmd_ctx* ctx, const void* Y, int elem, int n, long D, cons
     return pmd_fail(ctx, PMD_ERR_ARG, what, "null pointer");
   if (ws_bytes < pmd_group_project_workspace_bytes(n_partial_rows, n) || (n_partial_rows > 0 && !ws))
     return pmd_fail(ctx, PMD_ERR_WORKSPACE, what, "workspace too small");
-  const long n_fb = (n + PJ_FB - 1) / PJ_FB;
+  const long n_fb = ((long)n + PJ_FB - 1) / PJ_FB;   // (in long: n + 63 overflows an int from 2^31 - 64 on)
   if ((long)n_groups * n_fb > 0x7fffffffL) return pmd_fail(ctx, PMD_ERR_ARG, what, "too many groups x frame blocks");
   pmd_prof_scope prof__(ctx, "group_project");
   const dim3 grid((unsigned)((long)n_groups * n_fb));

@@ -140,7 +140,7 @@ int pmd_roi_gather(pmd_ctx* ctx, const void* Y, int elem, int n, long D, long n_
   if (!Y || !segs || !pix || !w || !out || (n_split > 0 && !split)) return pmd_fail(ctx, PMD_ERR_ARG, what, "null pointer");
   if (ws_bytes < pmd_roi_gather_workspace_bytes(n_partial_rows, n) || (n_partial_rows > 0 && !ws))
     return pmd_fail(ctx, PMD_ERR_WORKSPACE, what, "workspace too small");
-  const long n_fb = (n + RG_FB - 1) / RG_FB;
+  const long n_fb = ((long)n + RG_FB - 1) / RG_FB;   // (in long: n + 63 overflows an int from 2^31 - 64 on)
   if (n_segs * n_fb > 0x7fffffffL) return pmd_fail(ctx, PMD_ERR_ARG, what, "too many segments x frame blocks");
   pmd_prof_scope prof__(ctx, "roi_gather");
   const dim3 grid((unsigned)(n_segs * n_fb));

@@ -81,6 +81,26 @@ def normals(seed: int, stream: int, index: int, n: int) -> np.ndarray:
     return z.reshape(-1)[:n]
 
 
+def normals_many(seed: int, stream: int, indices, n: int) -> np.ndarray:
+    """``normals`` for many array indices at once: (len(indices), n) float32, the same words and the same fp32 Box-Muller."""
+    n_blocks = (n + 3) // 4
+    indices = np.asarray(indices, dtype=np.uint64).reshape(-1)
+    ctr = np.zeros((indices.size, n_blocks, 4), dtype=np.uint32)
+    ctr[:, :, 0] = np.arange(n_blocks, dtype=np.uint32)[None, :]
+    ctr[:, :, 2] = (indices & np.uint64(0xFFFFFFFF)).astype(np.uint32)[:, None]
+    ctr[:, :, 3] = np.uint32(stream & 0xFFFFFFFF)
+    key = np.array([seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF], dtype=np.uint32)
+    w = philox4x32_10(ctr.reshape(-1, 4), key)
+    two_m24 = np.float32(2.0 ** -24)
+    u = ((w >> np.uint32(8)).astype(np.float32) + np.float32(0.5)) * two_m24
+    r0 = np.sqrt(np.float32(-2.0) * np.log(u[:, 0]))
+    r1 = np.sqrt(np.float32(-2.0) * np.log(u[:, 2]))
+    th0 = np.float32(2.0 * np.pi) * u[:, 1]
+    th1 = np.float32(2.0 * np.pi) * u[:, 3]
+    z = np.stack([r0 * np.cos(th0), r0 * np.sin(th0), r1 * np.cos(th1), r1 * np.sin(th1)], axis=1).astype(np.float32)
+    return z.reshape(indices.size, n_blocks * 4)[:, :n]
+
+
 class PhiloxSource:
     """Random source handed to the oracle when no device stream is injected."""
 

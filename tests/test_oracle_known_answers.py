@@ -180,3 +180,17 @@ def test_end_to_end_oracle_invariants_and_golden():
         np.testing.assert_allclose(res.std_img, g["std_img"], rtol=1e-5)
         np.testing.assert_allclose(res.s, g["s"], rtol=1e-3)
         np.testing.assert_allclose(np.array(res.diag["thresholds"]), g["thresholds"], rtol=1e-4)
+
+
+def test_normals_many_equals_normals_index_by_index():
+    """The vectorised form the launch-cut test of pmd_rng_normal compares 32771 arrays with is the restatement itself."""
+    from oracle import philox
+
+    seed = 0x1234ABCD5678
+    indices = [0, 7, 32768 * 3 + 11, 2 ** 32 - 1]
+    for n in (1, 15, 16):
+        many = philox.normals_many(seed, 4, indices, n)
+        assert many.shape == (len(indices), n) and many.dtype == np.float32
+        for row, index in zip(many, indices):
+            assert np.array_equal(row, philox.normals(seed, 4, index, n))
+
