@@ -417,6 +417,29 @@ int pmd_shift_apply(pmd_ctx* ctx, const void* X, int elem, long frame_stride, lo
                     const int* ishift, const float* wts, int border, float fill, void* out, int out_elem,
                     long out_frame_stride, long out_row_stride);
 
+/* Separable spatial filtering of frames (localmd_amd/spatial.py, csrc/spatial.hip): the high-pass that one-photon movies
+ * need before template matching, and the band-passed movie their correlation images start from.  X holds n frames of
+ * d1 x d2 with the element types and strides of pmd_shift_apply; out likewise.  wy_host holds 2 ry + 1 floats, wx_host
+ * 2 rx + 1; both are HOST arrays, read when the call is made and handed to the kernel by value, so there is no device
+ * table, no workspace and no synchronisation.  0 <= ry <= min(PMD_FILTER_MAX_RADIUS, d1), rx the same against d2.
+ *   a(y, x) = float(f[refl(y)][refl(x)]), refl(i) = -1 - i below 0 and 2 d - 1 - i from d on (SciPy's mode="reflect";
+ *     one reflection suffices because r <= d).
+ *   Row pass, per source row: h[y][x] is the chain acc = fl(wx[0] a_0), acc = fl(acc + fl(wx[j] a_j)) over ascending j
+ *     with a_j = a(y, x + j - rx); s[y][x] is the chain of fp32 adds of the same a_j, ascending.
+ *   Column pass: G is the same kind of chain with wy over h[refl(y + i - ry)][x], S the add chain over s.
+ *   out = quant(fl(fl(fl(centre a(y, x)) + G) - fl(box S))); the centre term is left out when centre == 0, the box term
+ *     and all of s / S when box == 0.  No contraction anywhere; quant is that of pmd_shift_apply (16-bit outputs round
+ *     half to even, saturate, NaN -> 0).
+ * The bits of an output pixel depend on the frame, the weights and the geometry only: not on n, the strides, the
+ * alignment of X / out, the input element type beyond its values, or the tile the pixel falls in.
+ * Errors (PMD_ERR_ARG, nothing is launched): n < 0, sides outside 1 .. PMD_SHIFT_MAX_DIM, a radius out of range, an
+ * unknown elem / out_elem, a stride shorter than a row or a frame, a NULL pointer, X and out overlapping.  n == 0
+ * launches nothing and returns PMD_OK.  The call only enqueues, on the context's stream. */
+#define PMD_FILTER_MAX_RADIUS 32
+int pmd_spatial_filter(pmd_ctx* ctx, const void* X, int elem, long frame_stride, long row_stride, int n, int d1, int d2,
+                       int ry, int rx, const float* wy_host, const float* wx_host, float centre, float box, void* out,
+                       int out_elem, long out_frame_stride, long out_row_stride);
+
 /* Piecewise-rigid motion correction (localmd_amd/piecewise.py, csrc/piecewise.hip): patch surfaces around every frame's
  * rigid peak, and the warp by the smooth field the patch shifts span.  max_shift = (my, mx) as above; max_deviation =
  * (ey, ex), each in 1 .. PMD_PATCH_MAX_DEV.  oy = my + ey, ox = mx + ex.

@@ -19,6 +19,7 @@ from .superpixels import Superpixels, superpixels
 from .deconvolve import Deconvolved, deconvolve, estimate_decay
 from .register import Registration, RegisteredMovie, register_movie, apply_shifts, subpixel_peak
 from .piecewise import PiecewiseRegistration, WarpedMovie, register_piecewise, apply_field, warp_frames
+from .spatial import SpatialFilter, spatial_filter, filter_frames, filter_movie
 
 PMDDataset = lazy_data_loader  # the name the reference's README uses (README.md:67)
 
@@ -31,4 +32,5 @@ __all__ = [
     "Superpixels", "superpixels", "Deconvolved", "deconvolve", "estimate_decay",
     "Registration", "RegisteredMovie", "register_movie", "apply_shifts", "subpixel_peak",
     "PiecewiseRegistration", "WarpedMovie", "register_piecewise", "apply_field", "warp_frames",
+    "SpatialFilter", "spatial_filter", "filter_frames", "filter_movie",
 ]

@@ -65,6 +65,7 @@ SIGNATURES = {
     "pmd_shift_correlate": (c_i, [c_p, c_p, c_i, c_l, c_l, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_sz]),
     "pmd_shift_peak": (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p]),
     "pmd_shift_apply": (c_i, [c_p, c_p, c_i, c_l, c_l, c_i, c_i, c_i, c_p, c_p, c_i, c_f, c_p, c_i, c_l, c_l]),
+    "pmd_spatial_filter": (c_i, [c_p, c_p, c_i, c_l, c_l, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_f, c_f, c_p, c_i, c_l, c_l]),
     "pmd_patch_correlate_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i]),
     "pmd_patch_correlate": (c_i, [c_p, c_p, c_i, c_l, c_l, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p,
                                   c_p, c_p, c_p, c_p, c_sz]),

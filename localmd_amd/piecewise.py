@@ -38,7 +38,7 @@ from ._movie import _ELEM, _stream_dtype
 from ._stream import BLOCK
 from .dataset import lazy_data_loader
 from .register import (Registration, _is_int, _quantize, _resolve_dtype, apply_args, check_border, check_max_shift,
-                       motion_pass, register_args, register_device_bytes, subpixel_peak, valid_rect)
+                       check_prefilter, motion_pass, register_args, register_device_bytes, subpixel_peak, valid_rect)
 
 MAX_DEV = 7                  # PMD_PATCH_MAX_DEV
 MAX_PATCHES = 4096           # PMD_PATCH_MAX
@@ -228,15 +228,15 @@ def surface_frames(m, pg):
 
 
 def piecewise_device_bytes(*, d1, d2, nb, esize, host_source, n_batches, gy, gx, pg=None, n_sample=0, out_esize=4,
-                           host_dest=False):
+                           host_dest=False, prefilter=False):
     """Device bytes register_piecewise / apply_field hold on d1 x d2 frames read in batches of nb; no term grows with the
     movie's length.  Those of register_movie (register_device_bytes); for the estimate (pg given) t' of the patches, the tile
     partials of one launch group, the patch surfaces of one sub-block and the patch peak tables of one block; the grid
-    of one block and the four field tables."""
+    of one block and the four field tables; ``prefilter`` adds register_movie's term."""
     blk = min(BLOCK, nb)
     my, mx = pg.max_shift if pg is not None else (None, None)
     need = register_device_bytes(d1=d1, d2=d2, nb=nb, esize=esize, host_source=host_source, n_batches=n_batches, my=my,
-                                 mx=mx, n_sample=n_sample, out_esize=out_esize, host_dest=host_dest)
+                                 mx=mx, n_sample=n_sample, out_esize=out_esize, host_dest=host_dest, prefilter=prefilter)
     if pg is not None:
         ey, ex = pg.max_deviation
         sub = surface_frames(blk, pg)
@@ -250,9 +250,10 @@ class PiecewiseRegistration:
     (dy, dx of every patch of every frame), ``integer_shifts`` (T, gy, gx, 2) int32, ``peak`` (T, gy, gx) float32,
     ``fallback`` (T, gy, gx) bool (the patch took the frame's rigid shift), ``at_limit`` (K, 3) the (t, i, j) whose
     peak lies on the edge of the deviation range (a warning, not an error), ``centers`` (yc, xc), ``starts``, ``patch``,
-    ``stride``, ``max_shift``, ``max_deviation``, ``template``, ``border`` and ``valid`` (y0, y1, x0, x1), valid_rect
-    over all patch shifts: the field is a convex combination of them, so no sample of a pixel inside it came from
-    outside the image.  ``field(t)`` is the (d1, d2, 2) fp32 field of frame t with the kernel's bits."""
+    ``stride``, ``max_shift``, ``max_deviation``, ``template``, ``border``, ``prefilter`` (that of the rigid step) and
+    ``valid`` (y0, y1, x0, x1), valid_rect over all patch shifts: the field is a convex combination of them, so no
+    sample of a pixel inside it came from outside the image.  ``field(t)`` is the (d1, d2, 2) fp32 field of frame t with
+    the kernel's bits."""
 
     def __init__(self, rigid, shifts, integer_shifts, peak, fallback, pg, template, border="nearest"):
         self.rigid = rigid
@@ -263,6 +264,7 @@ class PiecewiseRegistration:
         self.centers, self.starts, self.patch, self.stride = pg.centers, pg.starts, pg.patch, pg.stride
         self.max_shift, self.max_deviation = pg.max_shift, pg.max_deviation
         self.template, self.border = np.asarray(template, dtype=np.float32), border
+        self.prefilter = getattr(rigid, "prefilter", None)
         self.valid = valid_rect(self.shifts, pg.d1, pg.d2)
         dev = self.integer_shifts - rigid.integer_shifts[:, None, None, :]
         lim = (np.abs(dev) == np.array(self.max_deviation, dtype=np.int32)).any(axis=-1) & ~self.fallback
@@ -427,7 +429,7 @@ def _out_dtype(dtype):
 
 def register_piecewise(movie, out=None, *, max_shift=15, patch=128, stride=96, max_deviation=3, template=None,
                        template_frames=200, template_iters=2, subpixel=True, border="nearest", dtype=None,
-                       frame_batch_size=10000, num_workers=0, bigtiff=None, device=None, ctx=None):
+                       frame_batch_size=10000, num_workers=0, bigtiff=None, prefilter=None, device=None, ctx=None):
     """Estimate a smooth shift field per frame of ``movie`` (the sources of register_movie) against a template and write
     the corrected movie ``out[t, y, x] = movie[t] sampled at (y + s_y, x + s_x)`` to ``out`` (the destinations of
     register_movie; None: only estimate).  Returns a PiecewiseRegistration.
@@ -443,7 +445,9 @@ def register_piecewise(movie, out=None, *, max_shift=15, patch=128, stride=96, m
     The field of a frame is bilinear between the patch centres and constant beyond the outermost ones; the frame is
     sampled bilinearly in fp32, each operation rounded on its own.
 
-    ``template``, ``template_frames``, ``template_iters`` as in register_movie (the refinement is rigid).  ``border``:
+    ``template``, ``template_frames``, ``template_iters`` and ``prefilter`` as in register_movie (the refinement is
+    rigid; with a prefilter the rigid and the patch surfaces are those of the filtered frames and the filtered
+    template, and the warp reads the unfiltered frames).  ``border``:
     "nearest" or a number.  ``dtype``: "float32" (None), "uint16", "int16".
 
     Reads: the template's sample frames once, then every frame of the movie once.  Every output bit is the same for every
@@ -451,18 +455,22 @@ def register_piecewise(movie, out=None, *, max_shift=15, patch=128, stride=96, m
     (piecewise_device_bytes is checked before anything is allocated).  Argument errors are raised before any device work
     and before a file is created; a file this call created is removed when it fails midway.  ``out`` must not share
     memory with the movie."""
-    info, pg, template, out_dtype, dest = register_args(
-        movie, out, lambda d1, d2: PatchGrid(d1, d2, max_shift, max_deviation, patch, stride), template, template_frames,
-        template_iters, frame_batch_size, bigtiff, border, lambda src: _out_dtype(dtype), device, ctx)
+    info, (pg, filt), template, out_dtype, dest = register_args(
+        movie, out, lambda d1, d2: (PatchGrid(d1, d2, max_shift, max_deviation, patch, stride),
+                                    check_prefilter(prefilter, d1, d2)),
+        template, template_frames, template_iters, frame_batch_size, bigtiff, border, lambda src: _out_dtype(dtype), device,
+        ctx)
     (my, mx), subpixel = pg.max_shift, bool(subpixel)
     estimate = dict(my=my, mx=mx, template=template, template_frames=int(template_frames),
                     template_iters=int(template_iters), subpixel=subpixel, surfaces=False)
     found, _ = motion_pass(
         "register_piecewise", movie, info, dest, out_dtype, int(frame_batch_size), num_workers, device, ctx,
-        functools.partial(piecewise_device_bytes, gy=pg.gy, gx=pg.gx, pg=pg), estimate=estimate,
+        functools.partial(piecewise_device_bytes, gy=pg.gy, gx=pg.gx, pg=pg, prefilter=filt is not None),
+        estimate=estimate, prefilter=filt,
         patches=lambda ctx, cap: _PatchEstimator(ctx, pg, cap),
         applier=lambda ctx, cap: _Warper(ctx, pg.d1, pg.d2, pg.gy, pg.gx, pg.centers, cap, border, _ELEM[out_dtype]))
-    rigid = Registration(found["shifts"], found["arg"], found["peak"], found["template"], pg.max_shift, border)
+    rigid = Registration(found["shifts"], found["arg"], found["peak"], found["template"], pg.max_shift, border,
+                         prefilter=filt)
     return PiecewiseRegistration(rigid, found["patch_shifts"], found["ints"], found["ppeak"], found["fallback"], pg,
                                  found["template"], border)
 

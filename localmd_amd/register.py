@@ -36,6 +36,7 @@ from ._movie import _ELEM, _device_elem, _device_free_bytes, _stream_dtype
 from ._sink import HOST_SLOTS, _destination, _optional_destination, check_bigtiff, device_index, movie_pass
 from ._stream import BLOCK, batch_buffer_bytes, block_plan, check_fit, device_context, each_block
 from .dataset import lazy_data_loader
+from .spatial import SpatialFilter, as_filter, filter_image, run_filter
 
 MAX_SHIFT = 31               # PMD_SHIFT_MAX
 MIN_WINDOW = 8               # PMD_SHIFT_MIN_WINDOW
@@ -68,6 +69,16 @@ def check_max_shift(max_shift, d1, d2):
         raise ValueError("max_shift {} leaves a window of {} x {} pixels of the {} x {} frame; it must hold at least "
                          "{} x {}".format((my, mx), d1 - 2 * my, d2 - 2 * mx, d1, d2, MIN_WINDOW, MIN_WINDOW))
     return my, mx
+
+
+def check_prefilter(prefilter, d1, d2):
+    """The SpatialFilter of ``prefilter`` (None, a sigma or a pair of sigmas: a band-pass, or a SpatialFilter) for
+    d1 x d2 frames, or None."""
+    if prefilter is None:
+        return None
+    filt = as_filter(prefilter)
+    filt.check_frame(d1, d2)
+    return filt
 
 
 def window_template(template, my, mx):
@@ -197,12 +208,13 @@ def correlate_workspace_bytes(n, d1, d2, my, mx):
 
 
 def register_device_bytes(*, d1, d2, nb, esize, host_source, n_batches, my=None, mx=None, n_sample=0, out_esize=0,
-                          host_dest=False, surfaces=False):
+                          host_dest=False, surfaces=False, prefilter=False):
     """Device bytes register_movie / apply_shifts hold on d1 x d2 frames read in batches of nb; no term grows with the
     movie's length.  The frame batches (two for a host source of more than one batch), and for the estimate (my, mx
     given) t', the tile partials of one launch group, the surfaces of one 1024-frame block (twice when they leave
     through the host ring) and the peak tables; for the template the n_sample sample frames, raw and shifted; for a
-    host destination the output ring of two blocks; the per-frame tables of a block."""
+    host destination the output ring of two blocks; the per-frame tables of a block; with a prefilter the fp32
+    scratch of one filtered block, the filtered sample and the template's two images."""
     D = d1 * d2
     blk = min(BLOCK, nb)
     need = batch_buffer_bytes(nb, D, esize, host_source, n_batches)
@@ -211,6 +223,8 @@ def register_device_bytes(*, d1, d2, nb, esize, host_source, n_batches, my=None,
         need += 4 * (d1 - 2 * my) * (d2 - 2 * mx) + correlate_workspace_bytes(max(blk, n_sample), d1, d2, my, mx)
         need += (2 if surfaces else 1) * 4 * ns * max(blk, n_sample) + 48 * max(blk, n_sample)
         need += n_sample * D * (esize + 4) + 2 * 4 * D
+        if prefilter:
+            need += 4 * blk * D + 4 * n_sample * D + 2 * 4 * D
     if host_dest:
         need += HOST_SLOTS * blk * D * out_esize
     return need + 24 * blk + (1 << 20)
@@ -222,15 +236,18 @@ class Registration:
     without a finite entry), ``template`` (d1, d2) float32, ``max_shift`` (my, mx), ``valid`` (y0, y1, x0, x1), the
     rectangle that no frame filled from outside the image (crop to it before decomposing), ``at_limit``, the frames
     whose peak lies on the edge of the search range (their true shift may be larger: a warning, not an error),
-    ``border``, and ``surfaces`` (T, 2 my + 1, 2 mx + 1) float32 when asked for, else None."""
+    ``border``, ``surfaces`` (T, 2 my + 1, 2 mx + 1) float32 when asked for, else None, and ``prefilter``, the
+    SpatialFilter the frames and the template were matched through, or None (``template`` is the unfiltered image
+    either way)."""
 
-    def __init__(self, shifts, integer_shifts, peak, template, max_shift, border="nearest", surfaces=None):
+    def __init__(self, shifts, integer_shifts, peak, template, max_shift, border="nearest", surfaces=None,
+                 prefilter=None):
         self.shifts = np.asarray(shifts, dtype=np.float64).reshape(-1, 2)
         self.integer_shifts = np.asarray(integer_shifts, dtype=np.int32).reshape(-1, 2)
         self.peak = np.asarray(peak, dtype=np.float32).reshape(-1)
         self.template = np.asarray(template, dtype=np.float32)
         self.max_shift = (int(max_shift[0]), int(max_shift[1]))
-        self.border, self.surfaces = border, surfaces
+        self.border, self.surfaces, self.prefilter = border, surfaces, prefilter
         d1, d2 = self.template.shape
         self.valid = valid_rect(self.shifts, d1, d2)
         lim = np.abs(self.integer_shifts) == np.array(self.max_shift, dtype=np.int32)[None, :]
@@ -394,9 +411,11 @@ def sample_frames(T, template_frames):
     return np.unique(np.round(np.linspace(0, T - 1, n)).astype(np.int64))
 
 
-def _build_template(ctx, est, movie, T, d1, d2, np_dtype, on_device, template_frames, template_iters):
+def _build_template(ctx, est, movie, T, d1, d2, np_dtype, on_device, template_frames, template_iters, filt=None):
     """The mean of the sample frames, refined template_iters times: register the sample to the current template with
-    integer shifts, apply them (nearest border), average.  Torch does the averaging."""
+    integer shifts, apply them (nearest border), average.  Torch does the averaging.  With ``filt`` the sample is
+    filtered once and every iteration matches the filtered sample against the filtered current template; the shifts
+    are applied to the unfiltered sample, so the template stays an unfiltered image."""
     import ctypes as C
     import torch
 
@@ -407,9 +426,14 @@ def _build_template(ctx, est, movie, T, d1, d2, np_dtype, on_device, template_fr
     if template_iters:
         ap = _Applier(ctx, d1, d2, n, "nearest", 0)
         R = torch.empty((n, d1 * d2), dtype=torch.float32, device=ctx.device)
+        M, m_elem = S, elem                                 # what is matched
+        if filt is not None:
+            M, m_elem = torch.empty((n, d1 * d2), dtype=torch.float32, device=ctx.device), 0
+            run_filter(ctx, filt, C.c_void_p(S.data_ptr()), elem, n, d1, d2, C.c_void_p(M.data_ptr()))
         for _ in range(template_iters):
-            est.set_template(tmpl.cpu().numpy().reshape(d1, d2))
-            arg, _, _ = est.run(C.c_void_p(S.data_ptr()), elem, 0, n)
+            current = tmpl.cpu().numpy().reshape(d1, d2)
+            est.set_template(current if filt is None else filter_image(ctx, filt, current))
+            arg, _, _ = est.run(C.c_void_p(M.data_ptr()), m_elem, 0, n)
             ap.run(C.c_void_p(S.data_ptr()), elem, n, arg.astype(np.float64), C.c_void_p(R.data_ptr()))
             tmpl = R.mean(dim=0)
     return tmpl.cpu().numpy().reshape(d1, d2)
@@ -423,7 +447,7 @@ def _check_counts(template_frames, template_iters):
 
 
 def motion_pass(what, movie, info, dest, out_dtype, frame_batch_size, num_workers, device, ctx, device_bytes, *,
-                estimate=None, patches=None, applier=None, given=None):
+                estimate=None, patches=None, applier=None, given=None, prefilter=None):
     """The one pass of register_movie / apply_shifts and of register_piecewise / apply_field: per 1024-frame block
     estimate the shifts or take them from ``given`` (indexed by frame), and apply them into ``dest`` when there is one
     (_sink.movie_pass).  Returns (what the estimate found, what dest.close() returned).
@@ -433,7 +457,10 @@ def motion_pass(what, movie, info, dest, out_dtype, frame_batch_size, num_worker
     the ``found`` tables template, arg, peak, shifts.  ``patches(ctx, cap)``: None, or what refines a block's rigid
     shifts (piecewise._PatchEstimator: set_template, tables, refine).  ``applier(ctx, cap)``: an _Applier or a
     piecewise._Warper, built when there is a destination.  ``device_bytes(**terms)``: the caller's device-memory bound
-    on the terms the pass knows, checked before anything is allocated."""
+    on the terms the pass knows, checked before anything is allocated.  ``prefilter``: None, or the SpatialFilter the
+    estimate looks through: every block is filtered into an fp32 scratch that the rigid and the patch estimator read,
+    the template is filtered with the same kernel, and the applier still reads the unfiltered block."""
+    import ctypes as C
     from ._stream import ToHost
 
     T, d1, d2, on_device, np_dtype = info
@@ -449,29 +476,39 @@ def motion_pass(what, movie, info, dest, out_dtype, frame_batch_size, num_worker
                             host_dest=dest is not None and dest.kind != "device")
         check_fit(what, need, _device_free_bytes(ctx.device))
         cap = max(1, min(BLOCK, nb))
-        est = pest = ring = None
+        est = pest = ring = scratch = None
         if estimate is not None:
             my, mx, template = estimate["my"], estimate["mx"], estimate["template"]
             if template is None:
                 pre = _Estimator(ctx, d1, d2, my, mx, max(1, n_sample))
                 template = _build_template(ctx, pre, movie, T, d1, d2, np_dtype, on_device, estimate["template_frames"],
-                                           estimate["template_iters"])
+                                           estimate["template_iters"], prefilter)
                 del pre
             if estimate["surfaces"]:
                 ring = ToHost(ctx, 1, T * (2 * my + 1) * (2 * mx + 1))
             est = _Estimator(ctx, d1, d2, my, mx, cap, ring)
-            est.set_template(template)
+            matched = template                              # what the estimators match: the template as the frames are seen
+            if prefilter is not None:
+                import torch
+
+                matched = filter_image(ctx, prefilter, template)
+                scratch = torch.empty(cap * d1 * d2, dtype=torch.float32, device=ctx.device)
+            est.set_template(matched)
             found.update(template=template, arg=np.zeros((T, 2), np.int32), peak=np.zeros(T, np.float32),
                          shifts=np.zeros((T, 2), np.float64))
             if patches is not None:
                 pest = patches(ctx, cap)
-                pest.set_template(template)
+                pest.set_template(matched)
                 found.update(pest.tables(T))
         ap = applier(ctx, cap) if dest is not None else None
 
         def write(c0, m, yp, elem, out):
             if est is not None:
-                arg, peak, neigh = est.run(yp, elem, c0, m)
+                seen, seen_elem = yp, elem
+                if scratch is not None:
+                    seen, seen_elem = C.c_void_p(scratch.data_ptr()), 0
+                    run_filter(ctx, prefilter, yp, elem, m, d1, d2, seen)
+                arg, peak, neigh = est.run(seen, seen_elem, c0, m)
                 sh = arg.astype(np.float64)
                 if estimate["subpixel"]:
                     sh = sh + subpixel_peak(neigh)
@@ -479,7 +516,7 @@ def motion_pass(what, movie, info, dest, out_dtype, frame_batch_size, num_worker
                 found["arg"][sl], found["peak"][sl], found["shifts"][sl] = arg, peak, sh
                 if pest is not None:
                     # est.arg still holds the integer peaks of this block on the device: they are the centres
-                    sh = pest.refine(yp, elem, m, est.arg, arg, sh, estimate["subpixel"], found, sl)
+                    sh = pest.refine(seen, seen_elem, m, est.arg, arg, sh, estimate["subpixel"], found, sl)
             else:
                 sh = given[c0:c0 + m]
             if out is not None:
@@ -564,7 +601,7 @@ def apply_args(what, movie, out, given_of, frame_batch_size, bigtiff, border, ou
 
 def register_movie(movie, out=None, *, max_shift=15, template=None, template_frames=200, template_iters=2,
                    subpixel=True, border="nearest", dtype=None, frame_batch_size=10000, num_workers=0, bigtiff=None,
-                   return_surfaces=False, device=None, ctx=None):
+                   return_surfaces=False, prefilter=None, device=None, ctx=None):
     """Estimate one rigid shift per frame of ``movie`` ((T, d1, d2): NumPy arrays and memmaps, any lazy_data_loader
     (TiffArray included), CPU tensors, device tensors; the sources of export_movie) against a template, and write the
     corrected movie ``out[t, y, x] = movie[t, y + dy_t, x + dx_t]`` to ``out`` (the destinations of export_movie: a
@@ -580,6 +617,12 @@ def register_movie(movie, out=None, *, max_shift=15, template=None, template_fra
     ``template``: a (d1, d2) image, or None: the mean of min(T, template_frames) evenly spaced frames (one strided
     read), refined ``template_iters`` times by registering those frames to it with integer shifts and averaging.
 
+    ``prefilter``: None, or a spatial filter the shifts are estimated through: a sigma or a pair (sy, sx) (the
+    band-pass of spatial_filter), or a SpatialFilter.  Every frame and the template are filtered before they are
+    matched and the shifts are applied to the unfiltered frames; one-photon movies, whose smooth background is fixed
+    in the sensor frame, need it.  ``template`` is given, built and returned as an unfiltered image, so
+    ``template=reg.template, prefilter=reg.prefilter`` reproduces a run.
+
     ``border``: "nearest" (samples outside the frame are those of the nearest edge pixel) or a number that replaces
     them.  ``dtype``: "float32", "uint16", "int16" (round half to even, saturating, NaN -> 0), or None: the movie's
     own dtype when every shift is an integer (``subpixel=False``), else float32.  Integer-shift frames are copied bit
@@ -591,18 +634,20 @@ def register_movie(movie, out=None, *, max_shift=15, template=None, template_fra
     movie's length (register_device_bytes is checked before anything is allocated); ``return_surfaces=True`` brings the
     (T, 2 my + 1, 2 mx + 1) surfaces to the host through a ring.  Argument errors are raised before any device work
     and before a file is created; a file this call created is removed when it fails midway.  ``out`` must not share memory with the movie."""
-    info, (my, mx), template, out_dtype, dest = register_args(
-        movie, out, lambda d1, d2: check_max_shift(max_shift, d1, d2), template, template_frames, template_iters,
+    info, ((my, mx), filt), template, out_dtype, dest = register_args(
+        movie, out, lambda d1, d2: (check_max_shift(max_shift, d1, d2), check_prefilter(prefilter, d1, d2)), template,
+        template_frames, template_iters,
         frame_batch_size, bigtiff, border, lambda src: _resolve_dtype(dtype, src, not subpixel), device, ctx)
     _, d1, d2 = info[:3]
     estimate = dict(my=my, mx=mx, template=template, template_frames=int(template_frames),
                     template_iters=int(template_iters), subpixel=bool(subpixel), surfaces=bool(return_surfaces))
     found, _ = motion_pass("register_movie", movie, info, dest, out_dtype, int(frame_batch_size), num_workers, device, ctx,
-                           functools.partial(register_device_bytes, my=my, mx=mx, surfaces=bool(return_surfaces)),
-                           estimate=estimate,
+                           functools.partial(register_device_bytes, my=my, mx=mx, surfaces=bool(return_surfaces),
+                                             prefilter=filt is not None),
+                           estimate=estimate, prefilter=filt,
                            applier=lambda ctx, cap: _Applier(ctx, d1, d2, cap, border, _ELEM[out_dtype]))
     return Registration(found["shifts"], found["arg"], found["peak"], found["template"], (my, mx), border,
-                        found.get("surfaces"))
+                        found.get("surfaces"), filt)
 
 
 def apply_shifts(movie, out, shifts, *, border="nearest", dtype=None, frame_batch_size=10000, num_workers=0,
