@@ -376,6 +376,36 @@ int pmd_oasis_ar1(pmd_ctx* ctx, const float* Y, long ldy, long T, long n_prob, c
                   const int* pw_row, const float* pw, long ldpw, float* C, long ldc, float* S, long lds, double* rss,
                   int* n_pools, void* ws, size_t ws_bytes);
 
+/* Spike inference for an AR(2) model with a finite rise time (deconvolve(p=2), csrc/oasis2.hip): the greedy pooled solver
+ * of Friedrich, Zhou & Paninski 2017, Alg. 3, with O(1) merges.  Arguments and conventions are those of pmd_oasis_ar1
+ * except: par[5 p .. 5 p + 4] = g1, g2, lam, s_min, b (admissible: the roots 0 <= r <= d < 1 of z^2 - g1 z - g2 are real,
+ * so g1 >= 0, g2 <= 0; trusted), and tab_row[p] selects three consecutive rows of tab (ldtab >= T + 2 apart), built by the
+ * caller (deconvolve.ar2_tables): H[i] = h_{i-1}, i = 0 .. T + 1, with h_{-1} = 0, h_0 = 1, h_j = g1 h_{j-1} + g2 h_{j-2};
+ * HH[l] = sum_{j<l} h_j^2 and HK[l] = sum_{j<l} h_j h_{j-1}, l = 0 .. T.  The kernel only indexes them.  It minimises
+ * 1/2 |c + b - y|^2 + lam sum_t s_t over s_t = c_t - g1 c_{t-1} - g2 c_{t-2} >= 0 (c_{-1} = c_{-2} = 0, s_0 = c_0 >= 0
+ * free), greedily: the value under a pool is held fixed while the pool is refitted, so for g2 != 0 the result is close
+ * to the optimum, not the optimum.  Every fp32 operation below is rounded on its own (no contraction; each product and
+ * each sum written here is one operation, evaluated left to right inside its brackets), divisions are IEEE, denormals
+ * are kept.  A pool is (v, w, N, M, t0, l); gw of a pool is g2 * w of the pool underneath, g2 * 0 for the bottom pool.
+ *   penalties: mu = lam * ((1 - g1) - g2), mu1 = lam * (1 - g1); pen_t = mu for t < T - 2, mu1 for t = T - 2, lam for
+ *     t = T - 1; y' = (y[t] - b) - pen_t.
+ *   forward, t = 0 .. T - 1: push (v, w, N, M, t0, l) = (y', y', y', 0, t, 1); when it is the bottom pool, v and w are
+ *     (y' > 0 ? y' : 0) and N stays y'.  While there are >= 2 pools, with k the pool under the top, m = l_k:
+ *     pred = H[m+1] * v_k + H[m] * gw_k; if not v_top < pred + s_min, stop.  Merge: gm = g2 * M_top;
+ *     N_k = N_k + (H[m+1] * N_top + H[m] * gm); M_k = M_k + (H[m] * N_top + H[m-1] * gm); l_k += l_top; pop; set pool k
+ *     with l = l_k: v_k = (N_k - gw_k * HK[l]) / HH[l]; the bottom pool alone: v_k = v_k > 0 ? v_k : 0;
+ *     w_k = H[l] * v_k + H[l-1] * gw_k.  HH[l] >= 1.  A NaN never compares true and never merges; every iteration pops
+ *     a pool, so the loop ends on any input.
+ *   fill, pool k: c[t0_k + j] = H[j+1] * v_k + H[j] * gw_k for j < l_k; s = 0 except at the first frame t of a pool
+ *     k >= 1, where d = c[t] - g1 * c[t-1], then for t >= 2 d = d - g2 * c[t-2], and s[t] = d > 0 ? d : 0.
+ *   residual: as pmd_oasis_ar1.  n_pools is the final depth.
+ * The bits of a problem depend on its column, its five parameters and its three table rows only.
+ * ws: 24 T n_prob bytes, which is pmd_oasis_ar1_workspace_bytes(T, 2 n_prob): five words per pool and one spare.
+ * Errors (nothing is launched): as pmd_oasis_ar1, with ldtab < T + 2 in the place of ldpw < T + 1. */
+int pmd_oasis_ar2(pmd_ctx* ctx, const float* Y, long ldy, long T, long n_prob, const int* col, const float* par,
+                  const int* tab_row, const float* tab, long ldtab, float* C, long ldc, float* S, long lds, double* rss,
+                  int* n_pools, void* ws, size_t ws_bytes);
+
 /* Rigid motion correction by template matching (localmd_amd/register.py, csrc/register.hip).  A frame is d1 x d2; the
  * window is rows [my, d1 - my) x columns [mx, d2 - mx) of the template, h x w pixels, h, w >= PMD_SHIFT_MIN_WINDOW.
  * tp is the fp32 template on the window minus its mean, row-major h x w.  With sy = dy + my, sx = dx + mx the surface of

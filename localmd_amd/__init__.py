@@ -16,7 +16,8 @@ from .quantiles import quantile_images
 from .baseline import Baseline, rolling_baseline, dff_movie, trace_baseline
 from .demix import Demixed, demix
 from .superpixels import Superpixels, superpixels
-from .deconvolve import Deconvolved, deconvolve, estimate_decay
+from .deconvolve import (Deconvolved, deconvolve, estimate_decay, estimate_ar2, ar2_from_roots,
+                         ar2_from_time_constants)
 from .register import Registration, RegisteredMovie, register_movie, apply_shifts, subpixel_peak
 from .piecewise import PiecewiseRegistration, WarpedMovie, register_piecewise, apply_field, warp_frames
 from .spatial import SpatialFilter, spatial_filter, filter_frames, filter_movie
@@ -30,6 +31,7 @@ __all__ = [
     "regressor_maps", "event_regressors", "summary_images", "quantile_images",
     "Baseline", "rolling_baseline", "dff_movie", "trace_baseline", "Demixed", "demix",
     "Superpixels", "superpixels", "Deconvolved", "deconvolve", "estimate_decay",
+    "estimate_ar2", "ar2_from_roots", "ar2_from_time_constants",
     "Registration", "RegisteredMovie", "register_movie", "apply_shifts", "subpixel_peak",
     "PiecewiseRegistration", "WarpedMovie", "register_piecewise", "apply_field", "warp_frames",
     "SpatialFilter", "spatial_filter", "filter_frames", "filter_movie",

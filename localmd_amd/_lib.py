@@ -61,6 +61,7 @@ SIGNATURES = {
     "pmd_grid_components": (c_i, [c_p, c_i, c_i, c_p, c_p, c_p, c_sz]),
     "pmd_oasis_ar1_workspace_bytes": (c_sz, [c_l, c_l]),
     "pmd_oasis_ar1": (c_i, [c_p, c_p, c_l, c_l, c_l, c_p, c_p, c_p, c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_p, c_p, c_sz]),
+    "pmd_oasis_ar2": (c_i, [c_p, c_p, c_l, c_l, c_l, c_p, c_p, c_p, c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_p, c_p, c_sz]),
     "pmd_shift_correlate_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i, c_i]),
     "pmd_shift_correlate": (c_i, [c_p, c_p, c_i, c_l, c_l, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_sz]),
     "pmd_shift_peak": (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p]),

@@ -1,0 +1,522 @@
+"""AR(2) spike inference on the GPU (localmd_amd.deconvolve(p=2), csrc/oasis2.hip): pmd_oasis_ar2 through the C ABI bit
+for bit against its NumPy emulation (tests/oasis2_ref.py) over the trace lengths where the penalties and the register
+pools change (1 to 5 frames), around a wave of problems and longer; special traces; invariance over the requested outputs,
+the split into calls and the position of a problem; the workspace (exactly 24 T n_prob bytes between guard bands) and the
+error codes; deconvolve(p=2) end to end against the package's own search driven by the emulation, over workspace caps;
+p=1 unchanged; the growth of device memory with the trace length; and rows of Y or C 2^20 + 3 elements apart."""
+import ctypes as C
+import functools
+import importlib
+
+import numpy as np
+import pytest
+
+import localmd_amd
+from tests import bigbuf as B
+from tests import oasis2_ref as R2
+from tests import oasis_ref as R1
+from tests import test_gpu_large_offsets as L
+
+DX = importlib.import_module("localmd_amd.deconvolve")     # the module: the package exports the function under the same name
+
+pytestmark = pytest.mark.gpu
+big = L.big                                       # the module-scoped 8.6 GB buffer of the large-offset tests
+
+PMD_ERR_ARG, PMD_ERR_WORKSPACE = -2, -3
+SIGMA = 0.3
+ROOTS = ((0.95, 0.5), (0.9, 0.3), (0.5, 0.0), (0.97, 0.8))     # (d, r) of column k: ROOTS[k % 4]
+GUARD = 512                                       # bytes of guard band on either side of the workspace
+EMULATION_ERR2 = 4.71e-7                          # fp32 against float64, the value measured in tests/test_deconvolve_ar2_host.py
+EMULATION_ERR1 = 4.18e-7                          # the same of the AR(1) solver, tests/test_deconvolve_host.py
+
+
+def _t():
+    import torch
+
+    return torch
+
+
+def P(t):
+    from localmd_amd._lib import ptr
+
+    return ptr(t)
+
+
+def _dev(ctx, a, dtype):
+    return _t().from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(ctx.device)
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.int32)
+
+
+def _pairs(K):
+    return np.stack([DX.ar2_from_roots(*ROOTS[k % 4]) for k in range(K)]).astype(np.float32)
+
+
+def _ar2_traces(seed, T, K):
+    """(T, K) float32: column k an AR(2) trace with the roots ROOTS[k % 4], sparse events and noise."""
+    rng = np.random.default_rng(seed)
+    g = _pairs(K).astype(np.float64)
+    s = (rng.random((T, K)) < 0.08) * rng.uniform(0.5, 2.0, (T, K))
+    c = np.zeros((T, K))
+    for t in range(T):
+        c[t] = (c[t - 1] * g[:, 0] if t else 0.0) + (c[t - 2] * g[:, 1] if t > 1 else 0.0) + s[t]
+    return (c + SIGMA * rng.standard_normal((T, K))).astype(np.float32)
+
+
+def _problems(seed, n_prob, K):
+    """col (repeats, no order), par = (g1, g2 of the column, lam, s_min, b): every third problem has lam = 0, the others
+    a positive one; s_min > 0 and b != 0 on a part of them."""
+    rng = np.random.default_rng(seed)
+    col = rng.integers(0, K, n_prob).astype(np.int32)
+    if n_prob >= K:
+        col[:K] = rng.permutation(K)
+    par = np.zeros((n_prob, 5), dtype=np.float32)
+    par[:, :2] = _pairs(K)[col]
+    par[:, 2] = np.where(np.arange(n_prob) % 3 == 0, 0.0, rng.uniform(0.1, 1.5, n_prob))
+    par[:, 3] = np.where(rng.random(n_prob) < 0.4, rng.uniform(0.05, 0.4, n_prob), 0.0)
+    par[:, 4] = np.where(rng.random(n_prob) < 0.5, rng.uniform(-0.3, 0.3, n_prob), 0.0)
+    return col, par
+
+
+def _tables(pairs, T, pad=0):
+    """(3 P, T + 2 + pad): the three rows of every pair, the padding NaN."""
+    pairs = np.asarray(pairs, dtype=np.float32).reshape(-1, 2)
+    tab = np.full((3 * len(pairs), T + 2 + pad), np.nan, dtype=np.float32)
+    tab[:, :T + 2] = DX.ar2_tables(pairs[:, 0], pairs[:, 1], T).reshape(3 * len(pairs), T + 2)
+    return tab
+
+
+def _emulate(Y, col, par, tab_row, tab):
+    """(C (T, n), S (T, n), rss (n,), n_pools (n,)) of the problems by the fp32 emulation; equal problems are solved once."""
+    T, n = Y.shape[0], len(col)
+    Ce, Se = np.zeros((T, n), dtype=np.float32), np.zeros((T, n), dtype=np.float32)
+    rss, npl, seen = np.zeros(n), np.zeros(n, dtype=np.int32), {}
+    for p in range(n):
+        key = (int(col[p]), int(tab_row[p]), par[p].tobytes())
+        if key not in seen:
+            rows = tab[tab_row[p]:tab_row[p] + 3, :T + 2]
+            seen[key] = R2.oasis_ar2(Y[:, col[p]], par[p, 0], par[p, 1], par[p, 2], par[p, 3], par[p, 4], np.float32, rows)
+        Ce[:, p], Se[:, p], rss[p], npl[p] = seen[key]
+    return Ce, Se, rss, npl
+
+
+def _device(ctx, Y, col, par, tab_row, tab, want="CSRN", pad=(0, 0, 0), fill=0xFF):
+    """pmd_oasis_ar2 on the device with the outputs named in ``want`` (C, S, Rss, N_pools) and ``pad`` extra columns in
+    Y, C and S; the outputs start as NaN / -1, the workspace is exactly 24 T n bytes of ``fill`` between two guard bands
+    of the same fill, and the padding and the guard bands must come back untouched."""
+    torch = _t()
+    T, K = Y.shape
+    n = len(col)
+    ldy, ldc, lds = K + pad[0], n + pad[1], n + pad[2]
+    Yd = torch.full((T, ldy), float("nan"), dtype=torch.float32, device=ctx.device)
+    Yd[:, :K] = _dev(ctx, Y, np.float32)
+    Cd = torch.full((T, ldc), float("nan"), dtype=torch.float32, device=ctx.device) if "C" in want else None
+    Sd = torch.full((T, lds), float("nan"), dtype=torch.float32, device=ctx.device) if "S" in want else None
+    rd = torch.full((n,), float("nan"), dtype=torch.float64, device=ctx.device) if "R" in want else None
+    nd = torch.full((n,), -1, dtype=torch.int32, device=ctx.device) if "N" in want else None
+    nbytes = 24 * T * n
+    assert nbytes == ctx.lib.pmd_oasis_ar1_workspace_bytes(T, 2 * n) == DX.workspace_bytes(T, n, p=2)
+    ws = torch.full((GUARD + nbytes + GUARD,), fill, dtype=torch.uint8, device=ctx.device)
+    # named, so that the tables live until the call has run (a temporary's memory goes back to the allocator at once)
+    cold, pard = _dev(ctx, col, np.int32), _dev(ctx, par, np.float32)
+    rowd, tabd = _dev(ctx, tab_row, np.int32), _dev(ctx, tab, np.float32)
+    assert int(cold.min()) >= 0 and int(cold.max()) < K and par.shape == (n, 5)
+    assert int(rowd.min()) >= 0 and int(rowd.max()) + 3 <= tab.shape[0] and tab.shape[1] >= T + 2
+    ctx.call("pmd_oasis_ar2", P(Yd), ldy, T, n, P(cold), P(pard), P(rowd), P(tabd), tab.shape[1], P(Cd), ldc, P(Sd), lds,
+             P(rd), P(nd), C.c_void_p(ws.data_ptr() + GUARD), nbytes)
+    ctx.sync()
+    assert bool((ws[:GUARD] == fill).all().item()) and bool((ws[GUARD + nbytes:] == fill).all().item()), "guard band written"
+    assert bool((ws[GUARD + 20 * T * n:GUARD + nbytes] == fill).all().item()), "the spare word of the pools was written"
+    out = {}
+    for name, t in (("C", Cd), ("S", Sd)):
+        if t is not None:
+            assert bool(torch.isnan(t[:, n:]).all().item()), name + ": columns beyond n_prob were written"
+            out[name] = t[:, :n].cpu().numpy()
+    if rd is not None:
+        out["R"] = rd.cpu().numpy()
+    if nd is not None:
+        out["N"] = nd.cpu().numpy()
+    return out
+
+
+def _assert_same(got, ref, names="CSRN"):
+    Ce, Se, rss, npl = ref
+    if "N" in names:
+        assert np.array_equal(got["N"], npl), np.nonzero(got["N"] != npl)[0][:5]
+    if "C" in names:
+        assert np.array_equal(_bits(got["C"]), _bits(Ce)), "calcium: {} values differ".format(np.sum(_bits(got["C"]) != _bits(Ce)))
+    if "S" in names:
+        assert np.array_equal(_bits(got["S"]), _bits(Se)), "spikes: {} values differ".format(np.sum(_bits(got["S"]) != _bits(Se)))
+    if "R" in names:
+        assert np.array_equal(got["R"].view(np.int64), rss.view(np.int64)), (got["R"] - rss)
+
+
+@functools.lru_cache(maxsize=None)
+def _case(T, n_prob):
+    K = 9
+    Y = _ar2_traces(100 + T, T, K)
+    col, par = _problems(T * 1000 + n_prob, n_prob, K)
+    tab = _tables(_pairs(K), T, pad=3)
+    row = (3 * col).astype(np.int32)                 # columns with the same roots have table rows of their own all the same
+    return Y, col, par, row, tab, _emulate(Y, col, par, row, tab)
+
+
+# ---- pmd_oasis_ar2 --------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n_prob", [1, 63, 64, 65, 130])
+@pytest.mark.parametrize("T", [1, 2, 3, 4, 5, 63, 64, 65, 256, 257])
+def test_oasis2_bits(gpu_ctx, T, n_prob):
+    Y, col, par, row, tab, ref = _case(T, n_prob)
+    got = _device(gpu_ctx, Y, col, par, row, tab, pad=(3, 2, 5))
+    _assert_same(got, ref)
+    assert np.all(got["S"][0] == 0) and np.all(got["S"] >= 0)
+
+
+def test_oasis2_bits_with_shared_table_rows(gpu_ctx):
+    """Columns 0, 4 and 8 have the same roots: their problems read one set of rows, and get the bits they get from rows
+    of their own."""
+    Y, col, par, row, tab, ref = _case(65, 130)
+    shared = (3 * (col % 4)).astype(np.int32)
+    _assert_same(_device(gpu_ctx, Y, col, par, shared, tab), ref)
+
+
+def test_oasis2_bits_long(gpu_ctx):
+    Y, col, par, row, tab, ref = _case(1500, 20)
+    _assert_same(_device(gpu_ctx, Y, col, par, row, tab), ref)
+    assert ref[3].min() >= 1 and ref[3].max() > 100
+
+
+def test_oasis2_special_traces(gpu_ctx):
+    T = 300
+    t = np.arange(T)
+    rng = np.random.default_rng(8)
+    pairs = np.float32([[0.75, -0.125], [1.45, -0.475], [1.0, -0.25], [0.9, -0.0]])    # roots (.5, .25), (.95, .5), .5 twice, (.9, 0)
+    tab = _tables(pairs, T)
+    h = tab[0, 1:T + 1]
+    cols = {                                                       # name: (trace, pair)
+        "increasing": (0.1 + 0.1 * t, 1),                          # a ramp lies above every prediction: no merge, T pools
+        "decreasing": (10.0 * 0.2 ** t - 1e-3, 0),                 # every frame merges: one pool, back to frame 0
+        "zeros": (np.zeros(T), 1),                                 # ties: v = pred = 0 at every frame, nothing merges
+        "impulse": (np.where(t < 2, h, 1.0 + t), 0),               # y[1] = h_1 = pred exactly: a tie does not merge
+        "negative": (-1.0 - rng.random(T), 1),                     # c = 0, one pool
+        "negative_start": (np.where(t == 0, -3.0, _ar2_traces(6, T, 1)[:, 0]), 1),   # the bottom pool refits with its first sample
+        "double_root": (_ar2_traces(3, T, 1)[:, 0], 2),
+        "no_rise": (_ar2_traces(4, T, 3)[:, 2], 3),
+        "long_pool": (np.where(t == 0, 5.0, np.where(t < 200, -1.0, rng.random(T))), 0),   # 200 frames: H is 0 from 127 on
+        "denormal": (1e-38 * rng.standard_normal(T), 1),
+    }
+    names = list(cols)
+    Y = np.stack([cols[k][0] for k in names], axis=1).astype(np.float32)
+    col = np.arange(len(names), dtype=np.int32)
+    par = np.zeros((len(names), 5), dtype=np.float32)
+    par[:, :2] = pairs[[cols[k][1] for k in names]]
+    row = np.int32([3 * cols[k][1] for k in names])
+    ref = _emulate(Y, col, par, row, tab)
+    got = _device(gpu_ctx, Y, col, par, row, tab)
+    _assert_same(got, ref)
+    n = dict(zip(names, got["N"]))
+    assert n["increasing"] == T and n["decreasing"] == 1 and n["zeros"] == T and n["negative"] == 1
+    assert n["impulse"] == T
+    assert not got["C"][:, names.index("negative")].any() and not got["C"][:, names.index("zeros")].any()
+    assert 1 < n["double_root"] < T and 1 < n["no_rise"] < T
+    lp = got["C"][:, names.index("long_pool")]
+    assert np.all(lp[128:200] == 0) and lp[100] > 0
+    d = got["C"][:, names.index("denormal")]
+    assert np.any((d > 0) & (d < np.finfo(np.float32).tiny))     # denormals are kept
+
+
+def test_oasis2_nan_and_inf_samples(gpu_ctx):
+    """One NaN, +inf or -inf sample: the call returns and gives what the stated arithmetic gives (a NaN never compares
+    true, so it never merges).  The emulation is compared value for value with NaN equal to NaN: the sign and payload of
+    a NaN are not part of the statement.  Before the bad sample the bits are the emulation's."""
+    T = 120
+    base = _ar2_traces(5, T, 3)
+    for k, bad in enumerate((np.nan, np.inf, -np.inf)):
+        base[40, k] = bad
+    col = np.arange(3, dtype=np.int32)
+    par = np.float32([[1.45, -0.475, 0.2, 0, 0]] * 3)
+    tab = _tables(par[0, :2], T)
+    row = np.zeros(3, dtype=np.int32)
+    Ce, Se, rss, npl = _emulate(base, col, par, row, tab)
+    got = _device(gpu_ctx, base, col, par, row, tab)
+    np.testing.assert_array_equal(got["C"], Ce)
+    np.testing.assert_array_equal(got["S"], Se)
+    np.testing.assert_array_equal(got["R"], rss)
+    assert np.array_equal(got["N"], npl)
+    assert np.isnan(got["R"][0]) and np.isnan(got["C"][40, 0])
+    for k in range(3):
+        bad = np.nonzero(~np.isfinite(Ce[:, k]))[0]
+        first = int(bad[0]) if len(bad) else T
+        assert np.array_equal(_bits(got["C"][:first, k]), _bits(Ce[:first, k]))
+
+
+def test_oasis2_without_g2_is_the_ar1_kernel(gpu_ctx):
+    """g2 = 0 is the AR(1) problem: on the same data pmd_oasis_ar2 and pmd_oasis_ar1 agree to the sum of the two bounds
+    measured on the host for their emulations against float64 (4 x each measured value, as fractions of max |y|)."""
+    T, K = 400, 6
+    gs = np.float32([0.95, 0.9, 0.5])
+    Y = np.stack([R1.planted(60 + k, T=T, g=float(gs[k % 3]), sigma=SIGMA, rate=0.03)[0] for k in range(K)], axis=1)
+    Y[0] += 3.0                                                    # a positive start: no leading pools of negative value
+    col = np.arange(K, dtype=np.int32)
+    lam, b = np.float32([0, 0.3, 1.0, 0.5, 0, 0.2]), np.float32([0, 0.1, 0, -0.1, 0, 0])
+    par2 = np.stack([gs[col % 3], np.zeros(K, dtype=np.float32), lam, np.zeros(K, dtype=np.float32), b], axis=1)
+    tab = _tables(par2[:3, :2], T)
+    row = (3 * (col % 3)).astype(np.int32)
+    got = _device(gpu_ctx, Y, col, par2, row, tab)
+    _assert_same(got, _emulate(Y, col, par2, row, tab))
+    # the AR(1) kernel on the same columns
+    torch, ctx = _t(), gpu_ctx
+    par1 = np.ascontiguousarray(par2[:, [0, 2, 3, 4]])
+    pw = DX.power_table(gs, T)
+    Yd, cold, pard = _dev(ctx, Y, np.float32), _dev(ctx, col, np.int32), _dev(ctx, par1, np.float32)
+    rowd, pwd = _dev(ctx, col % 3, np.int32), _dev(ctx, pw, np.float32)
+    Cd = torch.empty((T, K), dtype=torch.float32, device=ctx.device)
+    Sd = torch.empty((T, K), dtype=torch.float32, device=ctx.device)
+    nd = torch.empty((K,), dtype=torch.int32, device=ctx.device)
+    ws = torch.empty(12 * T * K, dtype=torch.uint8, device=ctx.device)
+    ctx.call("pmd_oasis_ar1", P(Yd), K, T, K, P(cold), P(pard), P(rowd), P(pwd), T + 1, P(Cd), K, P(Sd), K, None, P(nd),
+             P(ws), ws.numel())
+    ctx.sync()
+    scale = np.abs(Y).max()
+    err = max(np.abs(got["C"] - Cd.cpu().numpy()).max(), np.abs(got["S"] - Sd.cpu().numpy()).max()) / scale
+    print("AR(2) kernel at g2 = 0 against the AR(1) kernel, / max|y|:", err)
+    assert err <= 4 * EMULATION_ERR2 + 4 * EMULATION_ERR1
+
+
+def test_oasis2_bits_do_not_depend_on_outputs_split_or_position(gpu_ctx):
+    Y, col, par, row, tab, ref = _case(257, 130)
+    ctx = gpu_ctx
+    for want in ("R", "N", "C", "S", "RN", "CS", "SR"):
+        _assert_same(_device(ctx, Y, col, par, row, tab, want=want), ref, want)
+    # two calls: problems 0 .. 69 and 70 .. 129
+    for sl in (slice(0, 70), slice(70, 130)):
+        part = tuple(r[..., sl] for r in ref)
+        _assert_same(_device(ctx, Y, col[sl], par[sl], row[sl], tab), part)
+    # the problems of one call embedded among others, in another order
+    rng = np.random.default_rng(3)
+    pick = rng.permutation(130)[:40]
+    other_col, other_par = _problems(77, 100, Y.shape[1])
+    where = np.sort(rng.choice(140, 40, replace=False))
+    col2, par2 = np.zeros(140, dtype=np.int32), np.zeros((140, 5), dtype=np.float32)
+    mask = np.zeros(140, dtype=bool)
+    mask[where] = True
+    col2[mask], par2[mask] = col[pick], par[pick]
+    col2[~mask], par2[~mask] = other_col, other_par
+    got = _device(ctx, Y, col2, par2, (3 * col2).astype(np.int32), tab, pad=(1, 0, 7))
+    sub = {k: v[..., where] for k, v in got.items()}
+    _assert_same(sub, tuple(r[..., pick] for r in ref))
+
+
+def test_oasis2_workspace_is_24_bytes_a_pool_between_guard_bands(gpu_ctx):
+    """The call takes exactly 24 T n_prob bytes; with 0xFF and with 0x00 in the workspace and around it the guard bands and
+    the spare word of every pool stay as they were (checked in _device) and the results have the same bits."""
+    Y, col, par, row, tab, ref = _case(65, 65)
+    for fill in (0xFF, 0x00):
+        _assert_same(_device(gpu_ctx, Y, col, par, row, tab, fill=fill), ref)
+
+
+def test_oasis2_rejects_bad_arguments(gpu_ctx):
+    torch, ctx = _t(), gpu_ctx
+    T, K, n = 20, 3, 5
+    Y = _dev(ctx, _ar2_traces(1, T, K), np.float32)
+    col = _dev(ctx, np.arange(n) % K, np.int32)
+    par = _dev(ctx, np.tile(np.float32([1.45, -0.475, 0.1, 0, 0]), (n, 1)), np.float32)
+    row = _dev(ctx, np.zeros(n), np.int32)
+    tab = _dev(ctx, _tables([1.45, -0.475], T), np.float32)
+    Cd = torch.full((T, n), float("nan"), dtype=torch.float32, device=ctx.device)
+    Sd = torch.full((T, n), float("nan"), dtype=torch.float32, device=ctx.device)
+    rd = torch.full((n,), float("nan"), dtype=torch.float64, device=ctx.device)
+    nd = torch.full((n,), -1, dtype=torch.int32, device=ctx.device)
+    nbytes = 24 * T * n
+    ws = torch.full((nbytes,), 0xFF, dtype=torch.uint8, device=ctx.device)
+    good = dict(Y=P(Y), ldy=K, T=T, n=n, col=P(col), par=P(par), row=P(row), tab=P(tab), ldtab=T + 2, C=P(Cd), ldc=n, S=P(Sd),
+                lds=n, rss=P(rd), np_=P(nd), ws=P(ws), wsb=nbytes)
+    null = C.c_void_p(0)
+
+    def rc(**change):
+        a = dict(good, **change)
+        return ctx.lib.pmd_oasis_ar2(ctx.handle, a["Y"], a["ldy"], a["T"], a["n"], a["col"], a["par"], a["row"], a["tab"],
+                                     a["ldtab"], a["C"], a["ldc"], a["S"], a["lds"], a["rss"], a["np_"], a["ws"], a["wsb"])
+
+    for change in (dict(T=0), dict(T=-3), dict(T=2 ** 31 - 1), dict(n=0), dict(n=-1), dict(ldy=0), dict(ldtab=T + 1),
+                   dict(ldc=n - 1), dict(lds=n - 1), dict(Y=null), dict(col=null), dict(par=null), dict(row=null),
+                   dict(tab=null), dict(C=null, S=null, rss=null, np_=null), dict(n=2 ** 37, ldc=2 ** 37, lds=2 ** 37)):
+        assert rc(**change) == PMD_ERR_ARG, change
+    for change in (dict(wsb=nbytes - 1), dict(ws=null), dict(wsb=12 * T * n), dict(wsb=0)):
+        assert rc(**change) == PMD_ERR_WORKSPACE, change
+    assert ctx.lib.pmd_oasis_ar2(None, *[good[k] for k in good]) == PMD_ERR_ARG
+    ctx.sync()
+    assert bool(torch.isnan(Cd).all()) and bool(torch.isnan(Sd).all()) and bool(torch.isnan(rd).all())   # nothing launched
+    assert bool((nd == -1).all()) and bool((ws == 0xFF).all())
+    assert rc(ldc=0, C=null, lds=0, S=null) == 0         # a leading dimension of an output that is not asked for is not read
+    ctx.sync()
+    assert not bool(torch.isnan(rd).any())
+
+
+# ---- deconvolve(p=2) ------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _five_traces():
+    y = np.stack([R2.planted2(20 + k, T=600, d=(0.9, 0.95)[k % 2], r=(0.3, 0.5)[k % 2], sigma=SIGMA, rate=0.02)[0]
+                  for k in range(5)])
+    y.setflags(write=False)
+    return y
+
+
+_FIVE = {}
+
+
+def _five_run(ctx):
+    """deconvolve(p=2) of the five traces with 3 rounds of 4 and the default cap, computed once."""
+    if "dc" not in _FIVE:
+        _FIVE["dc"] = localmd_amd.deconvolve(_five_traces(), search_rounds=3, search_points=4, ctx=ctx, p=2)
+    return _FIVE["dc"]
+
+
+FIELDS = ("calcium", "spikes", "lam", "rss", "n_pools", "evaluations")
+
+
+def _assert_result(dc, ref):
+    assert np.array_equal(_bits(dc.calcium), _bits(ref["calcium"]))
+    assert np.array_equal(_bits(dc.spikes), _bits(ref["spikes"]))
+    assert np.array_equal(_bits(dc.lam), _bits(ref["lam"]))
+    assert np.array_equal(dc.rss, ref["rss"])
+    assert np.array_equal(dc.n_pools, ref["n_pools"])
+    assert np.array_equal(dc.evaluations, ref["evaluations"])
+
+
+def test_deconvolve2_equals_the_reference(gpu_ctx):
+    y = _five_traces()
+    dc = _five_run(gpu_ctx)
+    assert dc.calcium.shape == y.shape and dc.calcium.dtype == np.float32 and dc.spikes.dtype == np.float32
+    assert dc.g.shape == (5, 2) and dc.g.dtype == np.float32 and dc.noise.dtype == np.float64 and dc.lam.dtype == np.float32
+    assert DX.ar2_violation(dc.g[:, 0], dc.g[:, 1]) is None
+    assert np.array_equal(dc.g, DX.estimate_ar2(y, dc.noise).astype(np.float32))
+    ref = R2.deconvolve_ref2(y, dc.g, dc.noise, rounds=3, points=4)
+    _assert_result(dc, ref)
+    print("g", dc.g.tolist(), "lam", dc.lam, "evaluations", dc.evaluations, "rss / target", dc.rss / (dc.noise ** 2 * 600))
+    assert np.all((dc.rss <= dc.noise ** 2 * 600) | (dc.lam == 0))
+    assert np.all(dc.spikes >= 0) and np.all(dc.spikes[:, 0] == 0)
+
+
+@pytest.mark.parametrize("launches", [1, 2, 20])
+def test_deconvolve2_bits_do_not_depend_on_the_workspace_cap(gpu_ctx, launches):
+    """The largest round has 5 x 4 = 20 problems of 24 x 600 bytes each: caps that force one, two and twenty launches."""
+    y = _five_traces()
+    cap = 24 * 600 * (20 // launches)
+    assert len(DX.launch_plan(20, 600, cap, p=2)) == launches
+    dc = localmd_amd.deconvolve(y, search_rounds=3, search_points=4, max_workspace_bytes=cap, ctx=gpu_ctx, p=2)
+    ref = _five_run(gpu_ctx)
+    _assert_result(dc, {k: getattr(ref, k) for k in FIELDS})
+    assert np.array_equal(dc.noise, ref.noise) and np.array_equal(dc.g, ref.g)
+
+
+def test_deconvolve2_fixed_penalty_and_single_trace(gpu_ctx):
+    y = _five_traces()
+    lam = np.float32([0.0, 0.5, 1.0, 2.0, 0.25])
+    g = np.stack([DX.ar2_from_roots(d, r) for d, r in ((0.9, 0.3), (0.95, 0.5), (0.9, 0.9), (0.95, 0.0), (0.5, 0.2))])
+    s_min, b = np.float32([0, 0.2, 0, 0.1, 0]), np.float32([0, 0.1, -0.1, 0, 0])
+    dc = localmd_amd.deconvolve(y, g=g, noise=SIGMA, lam=lam, s_min=s_min, baseline=b, ctx=gpu_ctx, p=2)
+    g32 = g.astype(np.float32)
+    assert dc.g.shape == (5, 2) and np.array_equal(dc.g, g32)
+    for k in range(5):
+        c, s, rss, npl = R2.oasis_ar2(y[k], g32[k, 0], g32[k, 1], lam[k], s_min[k], b[k])
+        assert np.array_equal(_bits(dc.calcium[k]), _bits(c)) and np.array_equal(_bits(dc.spikes[k]), _bits(s))
+        assert dc.rss[k] == rss and dc.n_pools[k] == npl
+    assert np.all(dc.evaluations == 1) and np.array_equal(dc.lam, lam) and np.all(dc.noise == SIGMA)
+    assert np.array_equal(dc.baseline, b)
+    # one pair for all traces
+    same = localmd_amd.deconvolve(y, g=(1.45, -0.475), noise=SIGMA, lam=0.5, ctx=gpu_ctx, p=2)
+    assert same.g.shape == (5, 2) and np.all(same.g == np.float32([1.45, -0.475]))
+    # K = 1: the trace alone gets the bits it gets among the five
+    ref = _five_run(gpu_ctx)
+    one = localmd_amd.deconvolve(y[2:3], search_rounds=3, search_points=4, ctx=gpu_ctx, p=2)
+    assert one.calcium.shape == (1, 600) and one.g.shape == (1, 2)
+    assert np.array_equal(one.noise, ref.noise[2:3]) and np.array_equal(one.g, ref.g[2:3])
+    _assert_result(one, {k: getattr(ref, k)[2:3] for k in FIELDS})
+
+
+def test_deconvolve_of_the_first_order_is_unchanged(gpu_ctx):
+    """p=1 is the call without p, bit for bit, and both are the AR(1) reference."""
+    y = _five_traces()
+    a = localmd_amd.deconvolve(y, search_rounds=3, search_points=4, ctx=gpu_ctx)
+    b = localmd_amd.deconvolve(y, search_rounds=3, search_points=4, ctx=gpu_ctx, p=1)
+    _assert_result(b, {k: getattr(a, k) for k in FIELDS})
+    assert a.g.shape == (5,) and np.array_equal(a.g, b.g) and np.array_equal(a.noise, b.noise)
+    _assert_result(a, R1.deconvolve_ref(y, a.g, a.noise, rounds=3, points=4))
+
+
+def test_device_memory_grows_by_the_resident_terms(gpu_ctx):
+    import torch
+
+    K, cap = 64, 24 * 4000 * 64          # one wave at T = 4000, a quarter of one at T = 16000; uncapped: 16 times that
+    traces = _ar2_traces(9, 16000, K).T
+    peak = {}
+    for T in (4000, 16000):
+        y = traces[:, :T]
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        base = torch.cuda.memory_allocated(gpu_ctx.device)
+        torch.cuda.reset_peak_memory_stats(gpu_ctx.device)
+        localmd_amd.deconvolve(y, g=(1.45, -0.475), noise=SIGMA, search_rounds=1, search_points=4, max_workspace_bytes=cap,
+                               ctx=gpu_ctx, p=2)
+        peak[T] = torch.cuda.max_memory_allocated(gpu_ctx.device) - base
+    slack = 1 << 20                        # the plan's allowance for the allocator's rounding of the small arrays
+    resident = lambda T: 12 * K * T + 12 * K * (T + 2)     # noqa: E731
+    print("peak", peak, "resident", resident(4000), resident(16000))
+    assert peak[16000] - peak[4000] <= resident(16000) - resident(4000) + slack, peak
+    plan = DX.deconvolve_device_bytes(K=K, T=16000, problems=4 * K, max_workspace_bytes=cap, p=2)
+    assert resident(16000) <= peak[16000] <= plan, (peak, plan)
+
+
+# ---- rows past 2^31 elements ---------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _strided_case():
+    """Five AR(2) problems of T = 2049 frames (planted2 traces), two pairs of roots, soft and hard threshold."""
+    T, n = B.OASIS_T, B.OASIS_N
+    Y = np.stack([R2.planted2(30 + p, T=T)[0] for p in range(n)], axis=1).astype(np.float32)
+    pairs = np.stack([DX.ar2_from_roots(0.95, 0.5), DX.ar2_from_roots(0.9, 0.3)]).astype(np.float32)
+    tab = _tables(pairs, T)
+    which = np.array([0, 1, 0, 1, 0])
+    par = np.array([[pairs[w, 0], pairs[w, 1], lam, s_min, b] for w, lam, s_min, b in
+                    zip(which, (0.5, 0.0, 1.0, 0.25, 0.5), (0.0, 0.0, 0.0, 0.3, 0.0), (0.0, 0.1, -0.2, 0.0, 0.05))], dtype=np.float32)
+    row = (3 * which).astype(np.int32)
+    return Y, par, row, tab, _emulate(Y, np.arange(n, dtype=np.int32), par, row, tab)
+
+
+@pytest.mark.parametrize("strided_arg", ["ldy", "ldc"])
+def test_oasis2_strides(gpu_ctx, big, strided_arg):
+    """pmd_oasis_ar2, time-major: T = 2049 frames of five problems with the rows of Y (ldy) or of C (ldc) 2^20 + 3 elements
+    apart, so frame 2048 lies past 2^31 elements.  The same bits as the emulation; with C in the buffer the places a
+    truncated offset would hit keep their sentinel."""
+    ctx, torch = gpu_ctx, _t()
+    geo = B.GEOMETRIES["oasis_f32"]
+    T, n, LD = B.OASIS_T, B.OASIS_N, B.OASIS_LD
+    Y, par, row, tab, (Ce, Se, rss, npl) = _strided_case()
+    Sd = torch.full((T, n + 1), float("nan"), device=ctx.device)
+    rd = torch.full((n,), float("nan"), dtype=torch.float64, device=ctx.device)
+    nd = torch.full((n,), -1, dtype=torch.int32, device=ctx.device)
+    if strided_arg == "ldy":
+        Yd, ldy = L.put_input(ctx, big, "float32", geo, Y), LD
+        Cd, ldc = torch.full((T, n + 1), float("nan"), device=ctx.device), n + 1
+    else:
+        Yd, ldy = _dev(ctx, Y, np.float32), n
+        Cd, ldc = L.put_sentinel(big, geo), LD
+    nbytes = 24 * T * n
+    ws = torch.full((nbytes,), 0xFF, dtype=torch.uint8, device=ctx.device)
+    cold, pard = _dev(ctx, np.arange(n), np.int32), _dev(ctx, par, np.float32)
+    rowd, tabd = _dev(ctx, row, np.int32), _dev(ctx, tab, np.float32)
+    ctx.call("pmd_oasis_ar2", P(Yd), ldy, T, n, P(cold), P(pard), P(rowd), P(tabd), tab.shape[1], P(Cd), ldc, P(Sd), n + 1,
+             P(rd), P(nd), P(ws), nbytes)
+    ctx.sync()
+    if strided_arg == "ldy":
+        c = Cd.cpu().numpy()
+        assert np.all(np.isnan(c[:, n])), "the column beyond n_prob was written"
+        got_c = c[:, :n]
+    else:
+        assert L.aliases_kept(big, geo), "a row of C was written at a truncated offset"
+        got_c = L.live_rows(Cd, geo)
+    assert np.array_equal(nd.cpu().numpy(), npl)
+    assert np.array_equal(got_c.view(np.int32), Ce.view(np.int32)), "calcium differs: a frame at a truncated offset"
+    assert np.array_equal(Sd.cpu().numpy()[:, :n].view(np.int32), Se.view(np.int32))
+    assert np.array_equal(rd.cpu().numpy().view(np.int64), rss.view(np.int64))
