@@ -5,11 +5,11 @@ share.  The device context of a PMDArray, how a source is read (host sources thr
 streamed decomposition, device tensors sliced in place), the 1024-frame reconstruction blocks, the walk over the
 blocks of a batch and the Vt columns of one, the uploaded statistics and R s, the host ring that results leave the
 device through, and the argument and device-memory checks the callers have in common (check_pmd, name_tuple,
-check_fit).  Rebuilding a block of the denoised or residual movie from these is _expand's, and so are the plan and the
-one block walk of the five consumers that keep per-pixel state (KindPlan, KindBlocks); where a pass that writes a movie
-puts its frames (destinations, sinks, and the scaffold that opens, finishes and aborts them, movie_pass) is _sink's,
-the module beside this one.  The movie sources, the frame-batch plan and the element types are _movie.py's, the layer
-below this one and below the decomposition driver.  No helper knows its caller.
+check_fit, _check_count, _is_int).  Rebuilding a block of the denoised or residual movie from these is _expand's, and
+so are the plan and the one block walk of the five consumers that keep per-pixel state (KindPlan, KindBlocks); where a
+pass that writes a movie puts its frames (destinations, sinks, and the scaffold that opens, finishes and aborts them,
+movie_pass) is _sink's, the module beside this one.  The movie sources, the frame-batch plan and the element types are
+_movie.py's, the layer below this one and below the decomposition driver.  No helper knows its caller.
 """
 import contextlib
 
@@ -47,10 +47,22 @@ def name_tuple(value, allowed, word, words):
     return value
 
 
-def check_fit(what, need, free):
+def check_fit(what, need, free, hint="; lower frame_batch_size"):
+    """ValueError when ``what`` needs more device bytes than are free; ``hint`` is the advice the message ends in, with
+    the punctuation that joins it on."""
     if need > free:
-        raise ValueError("{} needs about {:.2f} GB of device memory, {:.2f} GB are free; lower "
-                         "frame_batch_size".format(what, need / 1e9, free / 1e9))
+        raise ValueError("{} needs about {:.2f} GB of device memory, {:.2f} GB are free{}".format(
+            what, need / 1e9, free / 1e9, hint))
+
+
+def _is_int(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+
+
+def _check_count(value, name):
+    if not _is_int(value) or int(value) < 1:
+        raise ValueError("{} must be an integer >= 1, got {!r}".format(name, value))
+    return int(value)
 
 
 def batch_buffer_bytes(nb, D, esize, host_source, n_batches):

@@ -27,6 +27,7 @@ do not fit.
 """
 import numpy as np
 
+from . import _stream
 from ._expand import KindBlocks, KindPlan, expander_bytes
 from ._movie import _device_free_bytes
 from ._sink import HOST_SLOTS, _destination, check_bigtiff, device_index, movie_pass
@@ -133,10 +134,8 @@ def baseline_device_bytes(*, T, D, temporal_bin, nb, esize, kind, n_cols, rank, 
 
 
 def check_fit(what, need, free):
-    if need > free:
-        raise ValueError("{} needs about {:.2f} GB of device memory, {:.2f} GB are free; the knots grow with the "
-                         "movie's length: raise temporal_bin (or lower frame_batch_size)".format(what, need / 1e9,
-                                                                                                  free / 1e9))
+    _stream.check_fit(what, need, free, hint="; the knots grow with the movie's length: raise temporal_bin (or lower "
+                                             "frame_batch_size)")
 
 
 def _check_bin(temporal_bin):

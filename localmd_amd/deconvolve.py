@@ -28,18 +28,22 @@ Device memory (``deconvolve_device_bytes``): the traces, the two outputs and the
 problem in flight and are capped at ``max_workspace_bytes``: a round is split into launches that fit (``launch_plan``),
 and no bit depends on the split.
 
+Everything that differs between the two orders (entry point, pool and table layout, the ``par`` columns, the check and
+the estimate of g, the penalty ceiling) is one ``_Order`` record each in ``_ORDERS``; a further model is a further record
+there and nothing else in this module.
+
 Out of scope: joint optimisation of g or of the baseline, complex roots, and an exact AR(2) solve.
 """
+from typing import Callable, NamedTuple
+
 import numpy as np
 
+from . import _stream
 from ._movie import _device_free_bytes
-from ._stream import device_context
+from ._stream import _check_count, device_context
 
 LAGS = 5                    # autocovariance lags estimate_decay fits
 LAGS2 = 10                  # autocovariance lags estimate_ar2 fits
-POOL_BYTES = 12             # (v, w, t0) of one pool on a problem's stack
-POOL_BYTES2 = 24            # (v, w, N, M, t0) and a spare word: a pool of the AR(2) solver
-SMALL_BYTES = {1: 36, 2: 40}    # per problem of a launch: col, par, rss, n_pools (p = 2: and tab_row)
 MIN_NOISE_FRAMES = 256      # the Welch window: pmd_stats makes no estimate below it
 G_MAX = 0.9999              # the ceiling of an estimated decay
 FLT_MIN = float(np.finfo(np.float32).tiny)
@@ -201,15 +205,22 @@ def lambda_ceiling(y, g, b):
     d = np.asarray(y, dtype=np.float64) - np.asarray(b, dtype=np.float64)[:, None]
     g = np.asarray(g, dtype=np.float64)
     hi = np.maximum(0.0, d[:, -1])
-    if g.ndim == 2:
-        if d.shape[1] > 1:
-            w = 1.0 - g[:, 0]
-            hi = np.maximum(hi, np.where(w > 0, d[:, -2] / np.where(w > 0, w, 1.0), d[:, -2] + g[:, 0] * d[:, -1]))
-        if d.shape[1] > 2:
-            hi = np.maximum(hi, d[:, :-2].max(axis=1) / (1.0 - g[:, 0] - g[:, 1]))
-    elif d.shape[1] > 1:
+    return _ORDERS[2 if g.ndim == 2 else 1].ceiling(d, g, hi).astype(np.float32)
+
+
+def _ceiling_ar1(d, g, hi):
+    if d.shape[1] > 1:
         hi = np.maximum(hi, d[:, :-1].max(axis=1) / (1.0 - g))
-    return hi.astype(np.float32)
+    return hi
+
+
+def _ceiling_ar2(d, g, hi):
+    if d.shape[1] > 1:
+        w = 1.0 - g[:, 0]
+        hi = np.maximum(hi, np.where(w > 0, d[:, -2] / np.where(w > 0, w, 1.0), d[:, -2] + g[:, 0] * d[:, -1]))
+    if d.shape[1] > 2:
+        hi = np.maximum(hi, d[:, :-2].max(axis=1) / (1.0 - g[:, 0] - g[:, 1]))
+    return hi
 
 
 def _collapsed(lo, hi):
@@ -258,14 +269,15 @@ def search_lambda(solve, target, lam_hi, rounds=5, points=8):
 
 
 def _check_order(p):
+    """The _Order record of ``p``."""
     if isinstance(p, (bool, np.bool_)) or p not in (1, 2):
         raise ValueError("p must be 1 (AR(1)) or 2 (AR(2)), got {!r}".format(p))
-    return int(p)
+    return _ORDERS[int(p)]
 
 
 def workspace_bytes(T, n_prob, p=1):
     """pmd_oasis_ar1_workspace_bytes: the pool stacks of n_prob problems (p = 2: of pmd_oasis_ar2, 24 bytes a pool)."""
-    return (POOL_BYTES if _check_order(p) == 1 else POOL_BYTES2) * int(T) * int(n_prob)
+    return _check_order(p).pool_bytes * int(T) * int(n_prob)
 
 
 def launch_plan(n_prob, T, max_workspace_bytes, p=1):
@@ -287,17 +299,15 @@ def deconvolve_device_bytes(*, K, T, problems, max_workspace_bytes, stats_bytes=
     12 K (T + 2)) stay resident; the pool stacks of the largest launch of launch_plan and 36 (p = 2: 40) bytes of
     tables per problem of it come on top, and ``stats_bytes``, the workspace of pmd_stats with its two outputs, when the
     noise is estimated."""
-    K, T, p = int(K), int(T), _check_order(p)
+    K, T, order = int(K), int(T), _check_order(p)
     largest = max(p1 - p0 for p0, p1 in launch_plan(problems, T, max_workspace_bytes, p))
-    need = 12 * K * T + (4 * K * (T + 1) if p == 1 else 12 * K * (T + 2))
-    need += workspace_bytes(T, largest, p) + SMALL_BYTES[p] * largest
+    need = 12 * K * T + 4 * order.rows * K * order.ldtab(T)
+    need += workspace_bytes(T, largest, p) + order.small_bytes * largest
     return need + int(stats_bytes) + (1 << 20)     # the allocator's rounding of the small arrays
 
 
 def check_fit(need, free):
-    if need > free:
-        raise ValueError("deconvolve needs about {:.2f} GB of device memory, {:.2f} GB are free: lower "
-                         "max_workspace_bytes, or pass fewer traces at a time".format(need / 1e9, free / 1e9))
+    _stream.check_fit("deconvolve", need, free, hint=": lower max_workspace_bytes, or pass fewer traces at a time")
 
 
 def _per_trace(value, K, name, ok, rule):
@@ -314,11 +324,12 @@ def _per_trace(value, K, name, ok, rule):
     return a
 
 
-def _check_count(value, name):
-    good = isinstance(value, (int, np.integer)) and not isinstance(value, (bool, np.bool_))
-    if not good or int(value) < 1:
-        raise ValueError("{} must be an integer >= 1, got {!r}".format(name, value))
-    return int(value)
+def _check_decay(g, K):
+    """``g`` of deconvolve(p=1), a scalar or (K,), as a (K,) float64 array of decays below 1 in float32."""
+    g = _per_trace(g, K, "g", lambda v: (v >= 0) & (v < 1), "0 <= g < 1")
+    if np.any(g.astype(np.float32) >= 1):
+        raise ValueError("g must be below 1 in float32")
+    return g
 
 
 def _check_pairs(g, K):
@@ -338,10 +349,39 @@ def _check_pairs(g, K):
     return a
 
 
+class _Order(NamedTuple):
+    """What an AR order is to this module.  ``g`` is (K,) for p = 1 and (K, 2), the pairs (g1, g2), for p = 2."""
+    entry: str              # the C entry point
+    pool_bytes: int         # one pool on a problem's stack: (v, w, t0); p = 2: (v, w, N, M, t0) and a spare word
+    small_bytes: int        # per problem of a launch: col, par, rss, n_pools (p = 2: and tab_row)
+    rows: int               # table rows per trace
+    row_extra: int          # a table row has T + row_extra entries
+    tables: Callable        # (g fp32, T) -> the (rows K, T + row_extra) fp32 table
+    par: Callable           # (g[idx], lam, s_min[idx], b[idx]) -> the columns of the entry point's par, in its order
+    check_g: Callable       # (g as given, K) -> g float64, or ValueError
+    estimate: Callable      # (traces, noise) -> g float64
+    estimate_frames: int    # ... which needs T above this
+    ceiling: Callable       # the order's part of lambda_ceiling
+
+    def ldtab(self, T):
+        return T + self.row_extra
+
+
+_ORDERS = {
+    1: _Order(entry="pmd_oasis_ar1", pool_bytes=12, small_bytes=36, rows=1, row_extra=1, tables=power_table,
+              par=lambda g, lam, s_min, b: (g, lam, s_min, b),
+              check_g=_check_decay, estimate=estimate_decay, estimate_frames=LAGS, ceiling=_ceiling_ar1),
+    2: _Order(entry="pmd_oasis_ar2", pool_bytes=24, small_bytes=40, rows=3, row_extra=2,
+              tables=lambda g, T: ar2_tables(g[:, 0], g[:, 1], T).reshape(-1, T + 2),
+              par=lambda g, lam, s_min, b: (g[:, 0], g[:, 1], lam, s_min, b),
+              check_g=_check_pairs, estimate=estimate_ar2, estimate_frames=LAGS2 + 1, ceiling=_ceiling_ar2),
+}
+
+
 def check_arguments(traces, g, noise, lam, s_min, baseline, search_rounds, search_points, max_workspace_bytes, p=1):
     """The checked arguments of deconvolve, before any device work: (y (K, T) float32, g, noise, lam (each (K,) float64
     or None; g (K, 2) for p = 2), s_min, baseline ((K,) float32), rounds, points, max_workspace_bytes)."""
-    p = _check_order(p)
+    order = _check_order(p)
     a = np.asarray(traces)
     if a.ndim != 2 or a.dtype.kind not in "iuf" or a.shape[0] < 1 or a.shape[1] < 1:
         raise ValueError("traces must be a (K, T) array of numbers with K >= 1 and T >= 1")
@@ -353,12 +393,8 @@ def check_arguments(traces, g, noise, lam, s_min, baseline, search_rounds, searc
     if T >= 2 ** 31 - 1:
         raise ValueError("{} frames are too many: the solver counts frames in 32 bits".format(T))
     finite = np.isfinite
-    if g is not None and p == 2:
-        g = _check_pairs(g, K)
-    elif g is not None:
-        g = _per_trace(g, K, "g", lambda v: (v >= 0) & (v < 1), "0 <= g < 1")
-        if np.any(g.astype(np.float32) >= 1):
-            raise ValueError("g must be below 1 in float32")
+    if g is not None:
+        g = order.check_g(g, K)
     if noise is not None:
         noise = _per_trace(noise, K, "noise", lambda v: (v > 0) & finite(v), "noise > 0")
     if lam is not None:
@@ -371,7 +407,7 @@ def check_arguments(traces, g, noise, lam, s_min, baseline, search_rounds, searc
     if noise is None and T < MIN_NOISE_FRAMES:
         raise ValueError("the noise level cannot be estimated from {} frames (the Welch window is {}): pass "
                          "noise=".format(T, MIN_NOISE_FRAMES))
-    if g is None and T <= (LAGS if p == 1 else LAGS2 + 1):
+    if g is None and T <= order.estimate_frames:
         raise ValueError("the decay cannot be estimated from {} frames: pass g=".format(T))
     launch_plan(1, T, cap, p)
     return y, g, noise, lam, s_min.astype(np.float32), baseline.astype(np.float32), rounds, points, cap
@@ -385,16 +421,10 @@ class _Solver:
     def __init__(self, ctx, Y, g, s_min, b, cap, largest, p=1):
         import torch
 
-        self.ctx, self.Y, self.cap, self.p = ctx, Y, cap, p
+        self.ctx, self.Y, self.cap, self.p, self.order = ctx, Y, cap, p, _check_order(p)
         self.T, self.K = (int(x) for x in Y.shape)
         self.g, self.s_min, self.b = g, s_min, b
-        if p == 1:
-            self.entry, self.rows, self.ldtab = "pmd_oasis_ar1", 1, self.T + 1
-            tab = power_table(g, self.T)
-        else:
-            self.entry, self.rows, self.ldtab = "pmd_oasis_ar2", 3, self.T + 2
-            tab = ar2_tables(g[:, 0], g[:, 1], self.T).reshape(3 * self.K, self.T + 2)
-        self.pw = torch.from_numpy(tab).to(ctx.device)
+        self.pw = torch.from_numpy(self.order.tables(g, self.T)).to(ctx.device)
         n = max(p1 - p0 for p0, p1 in launch_plan(largest, self.T, cap, p))
         self.ws = torch.empty(workspace_bytes(self.T, n, p), dtype=torch.uint8, device=ctx.device)
 
@@ -405,25 +435,22 @@ class _Solver:
         import torch
         from ._lib import ptr
 
-        ctx, T = self.ctx, self.T
+        ctx, T, order = self.ctx, self.T, self.order
         idx = np.asarray(idx, dtype=np.int64)
         lam = np.asarray(lam, dtype=np.float32)
         n = len(idx)
         if n == 0 or idx.min() < 0 or idx.max() >= self.K:
             raise ValueError("problems must name traces 0 .. {}".format(self.K - 1))
-        if self.p == 1:
-            par = np.stack([self.g[idx], lam, self.s_min[idx], self.b[idx]], axis=1).astype(np.float32)
-        else:
-            par = np.stack([self.g[idx, 0], self.g[idx, 1], lam, self.s_min[idx], self.b[idx]], axis=1).astype(np.float32)
+        par = np.stack(order.par(self.g[idx], lam, self.s_min[idx], self.b[idx]), axis=1).astype(np.float32)
         rss, n_pools = np.empty(n, dtype=np.float64), np.empty(n, dtype=np.int32)
         at = lambda t, p0: None if t is None else ctypes.c_void_p(t.data_ptr() + 4 * p0)   # noqa: E731
         for p0, p1 in launch_plan(n, T, self.cap, self.p):
             col = torch.from_numpy(idx[p0:p1].astype(np.int32)).to(ctx.device)
-            row = col if self.rows == 1 else torch.from_numpy((self.rows * idx[p0:p1]).astype(np.int32)).to(ctx.device)
+            row = col if order.rows == 1 else torch.from_numpy((order.rows * idx[p0:p1]).astype(np.int32)).to(ctx.device)
             pr = torch.from_numpy(np.ascontiguousarray(par[p0:p1])).to(ctx.device)
             r = torch.empty(p1 - p0, dtype=torch.float64, device=ctx.device)
             npl = torch.empty(p1 - p0, dtype=torch.int32, device=ctx.device) if pools else None
-            ctx.call(self.entry, ptr(self.Y), self.K, T, p1 - p0, ptr(col), ptr(pr), ptr(row), ptr(self.pw), self.ldtab,
+            ctx.call(order.entry, ptr(self.Y), self.K, T, p1 - p0, ptr(col), ptr(pr), ptr(row), ptr(self.pw), order.ldtab(T),
                      at(C, p0), n, at(S, p0), n, ptr(r), ptr(npl), ptr(self.ws), self.ws.numel())
             rss[p0:p1] = r.cpu().numpy()
             if pools:
@@ -457,8 +484,9 @@ def deconvolve(traces, g=None, noise=None, lam=None, s_min=0.0, baseline=0.0, se
     real roots ``0 <= r <= d < 1`` of ``z^2 - g1 z - g2`` (``ar2_from_roots``, ``ar2_from_time_constants``), checked on
     the fp32 values; ``g=None`` estimates it (``estimate_ar2``, needs T > 11).  The solver pools greedily (Friedrich,
     Zhou & Paninski 2017, Alg. 3): on planted traces its objective lay within 0.4 % of the optimum for the roots
-    (0.9, 0.3), 1.1 % for (0.95, 0.5) and 4.5 % for (0.97, 0.8), and it equals the optimum for ``g2 = 0``.  ``Deconvolved.g`` is (K, 2); pool stacks take 24 T bytes per problem and
-    the tables 12 K (T + 2) bytes.  With ``p=1`` (the default) nothing differs from a call without ``p``.
+    (0.9, 0.3), 1.1 % for (0.95, 0.5) and 4.5 % for (0.97, 0.8), and it equals the optimum for ``g2 = 0``.
+    ``Deconvolved.g`` is (K, 2); pool stacks take 24 T bytes per problem and the tables 12 K (T + 2) bytes.  With ``p=1``
+    (the default) nothing differs from a call without ``p``.
 
     ``g`` (0 <= g < 1), ``noise`` (> 0), ``lam`` (>= 0), ``s_min`` (>= 0) and ``baseline`` are scalars or (K,) arrays.
     ``noise=None`` estimates the noise level of every trace as the decomposition does for a pixel (Welch, the upper half
@@ -485,7 +513,7 @@ def deconvolve(traces, g=None, noise=None, lam=None, s_min=0.0, baseline=0.0, se
         if noise is None:
             noise = _device_noise(ctx, Y)
         if g is None:
-            g = estimate_decay(y, noise) if p == 1 else estimate_ar2(y, noise)
+            g = _check_order(p).estimate(y, noise)
         g32 = g.astype(np.float32)
         solver = _Solver(ctx, Y, g32, s_min, b, cap, largest, p)
         every = np.arange(K, dtype=np.int64)

@@ -38,7 +38,7 @@ import numpy as np
 import scipy.sparse
 
 from ._movie import _device_free_bytes
-from ._stream import (BLOCK, VtBlocks, check_fit, check_pmd, device_context, factor_bytes, scaled_r,
+from ._stream import (BLOCK, VtBlocks, _check_count, check_fit, check_pmd, device_context, factor_bytes, scaled_r,
                       upload_f32)
 from .traces import denoised_factors, roi_weights
 
@@ -61,13 +61,6 @@ class Demixed:
 
 
 # ---- host side: tables, offsets, the plan (no device work) ----------------------------------------------------------
-def _check_count(value, name):
-    ok = isinstance(value, (int, np.integer)) and not isinstance(value, (bool, np.bool_))
-    if not ok or int(value) < 1:
-        raise ValueError("{} must be an integer >= 1, got {!r}".format(name, value))
-    return int(value)
-
-
 def cover_tables(W, max_cover=MAX_COVER):
     """The pixel-major view of the K x D CSR weight matrix ``W`` (roi_weights) for pmd_hals_pixels:
 

@@ -34,7 +34,7 @@ import numpy as np
 
 from ._movie import _ELEM, _device_elem, _device_free_bytes, _stream_dtype
 from ._sink import HOST_SLOTS, _destination, _optional_destination, check_bigtiff, device_index, movie_pass
-from ._stream import BLOCK, batch_buffer_bytes, block_plan, check_fit, device_context, each_block
+from ._stream import BLOCK, _is_int, batch_buffer_bytes, block_plan, check_fit, device_context, each_block
 from .dataset import lazy_data_loader
 from .spatial import SpatialFilter, as_filter, filter_image, run_filter
 
@@ -48,10 +48,6 @@ _OUT_DTYPES = ("float32", "uint16", "int16")
 
 
 # ---- host side: arguments, the template, the parabola, the tables, the host form of the apply step --------------------
-def _is_int(v):
-    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
-
-
 def check_max_shift(max_shift, d1, d2):
     """(my, mx) of ``max_shift`` (an int, or a pair) for d1 x d2 frames; each in 1 .. 31, the window at least 8 x 8."""
     if _is_int(max_shift):

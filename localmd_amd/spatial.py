@@ -28,16 +28,12 @@ import numpy as np
 
 from ._movie import _ELEM, _device_free_bytes
 from ._sink import HOST_SLOTS, _destination, check_bigtiff, device_index, movie_pass
-from ._stream import BLOCK, batch_buffer_bytes, block_plan, check_fit, device_context, each_block
+from ._stream import BLOCK, _is_int, batch_buffer_bytes, block_plan, check_fit, device_context, each_block
 
 MAX_RADIUS = 32              # PMD_FILTER_MAX_RADIUS
 MAX_DIM = 16384              # PMD_SHIFT_MAX_DIM
 KINDS = ("lowpass", "bandpass", "highpass")
 _OUT_DTYPES = ("float32", "uint16", "int16")
-
-
-def _is_int(v):
-    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
 
 
 def _is_number(v):

@@ -236,6 +236,70 @@ def test_checked_arguments_are_per_trace():
     assert (rounds, points, cap) == (5, 8, 1 << 20)
 
 
+# ---- the launch sequence (a context that records its calls; no device, no library) ----------------------------------
+def test_solver_launch_sequence():
+    """_Solver.solve on K = 3 traces of T = 7 frames with 5 problems, for both orders, under a cap that holds every
+    problem and under one that holds two: per launch the entry point, n_prob, the table's leading dimension, the ``par``
+    rows read back through the pointer (fp32, in the entry point's column order), the table rows (p = 1: the tensor of
+    the columns itself, no second upload; p = 2: three times the columns), the workspace of the largest launch, and
+    where in C and S the launch writes."""
+    import ctypes
+    import types
+    import torch
+
+    T, K, n = 7, 3, 5
+    idx, lam = np.int64([2, 0, 1, 1, 2]), np.float32([0.0, 0.5, 1.0, 1.5, 2.0])
+    s_min, b = np.float32([0.0, 0.1, 0.2]), np.float32([0.3, 0.0, -0.3])
+    g1 = np.float32([0.5, 0.9, 0.95])
+    g2 = np.float32([[1.45, -0.475], [0.75, -0.125], [0.9, 0.0]])
+    par1 = np.stack([g1[idx], lam, s_min[idx], b[idx]], axis=1)
+    par2 = np.stack([g2[idx, 0], g2[idx, 1], lam, s_min[idx], b[idx]], axis=1)
+
+    def read(p, ctype, count):
+        return np.ctypeslib.as_array((ctype * count).from_address(p.value)).copy()
+
+    for p, entry, g, par, ldtab, rows, pool in ((1, "pmd_oasis_ar1", g1, par1, 8, 1, 12),
+                                                (2, "pmd_oasis_ar2", g2, par2, 9, 3, 24)):
+        for cap, plan in ((1 << 30, [(0, 5)]), (2 * pool * T, [(0, 2), (2, 4), (4, 5)])):
+            calls = []
+
+            def call(name, *a):
+                (Y_, ldy, T_, n_prob, col, pr, row, tab, ld, C_, ldc, S_, lds, r, npl, ws, ws_bytes) = a
+                width = par.shape[1]
+                calls.append(dict(
+                    name=name, ints=(ldy, T_, n_prob, ld, ldc, lds, ws_bytes), col=read(col, ctypes.c_int32, n_prob),
+                    par=read(pr, ctypes.c_float, n_prob * width).reshape(n_prob, width), same=row.value == col.value,
+                    row=read(row, ctypes.c_int32, n_prob),
+                    ptrs=(Y_.value, tab.value, C_ and C_.value, S_ and S_.value, ws.value)))
+                ctypes.memmove(r.value, (100.0 * len(calls) + np.arange(n_prob, dtype=np.float64)).ctypes.data, 8 * n_prob)
+                if npl.value:
+                    ctypes.memmove(npl.value, (10 * len(calls) + np.arange(n_prob, dtype=np.int32)).ctypes.data, 4 * n_prob)
+
+            ctx = types.SimpleNamespace(device=torch.device("cpu"), call=call)
+            Y = torch.zeros((T, K), dtype=torch.float32)
+            solver = DX._Solver(ctx, Y, g, s_min, b, cap, n, p)
+            C, S = torch.zeros((T, n), dtype=torch.float32), torch.zeros((T, n), dtype=torch.float32)
+            rss, n_pools = solver.solve(idx, lam, C, S, pools=True)
+            largest = max(p1 - p0 for p0, p1 in plan)
+            assert [c["name"] for c in calls] == [entry] * len(plan)
+            want_rss, want_pools = [], []
+            for k, (c, (p0, p1)) in enumerate(zip(calls, plan)):
+                assert c["ints"] == (K, T, p1 - p0, ldtab, n, n, pool * T * largest), (p, cap, k)
+                assert np.array_equal(c["col"], idx[p0:p1])
+                assert c["par"].dtype == np.float32 and np.array_equal(c["par"], par[p0:p1])
+                assert c["same"] == (p == 1) and np.array_equal(c["row"], rows * idx[p0:p1])
+                assert c["ptrs"] == (Y.data_ptr(), solver.pw.data_ptr(), C.data_ptr() + 4 * p0, S.data_ptr() + 4 * p0,
+                                     solver.ws.data_ptr())
+                want_rss += list(100.0 * (k + 1) + np.arange(p1 - p0))
+                want_pools += list(10 * (k + 1) + np.arange(p1 - p0))
+            assert tuple(solver.pw.shape) == (rows * K, ldtab) and solver.ws.numel() == pool * T * largest
+            assert np.array_equal(rss, want_rss) and np.array_equal(n_pools, want_pools)
+            calls.clear()                                  # without C, S and n_pools: null pointers, the same launches
+            solver.solve(idx, lam)
+            assert [c["ints"][2] for c in calls] == [p1 - p0 for p0, p1 in plan]
+            assert all(c["ptrs"][2:4] == (None, None) for c in calls)
+
+
 # ---- the planted property ------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("seed,rate", PLANTED)
 def test_planted_events_are_found(seed, rate):

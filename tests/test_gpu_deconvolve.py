@@ -11,8 +11,10 @@ import numpy as np
 import pytest
 
 import localmd_amd
+from tests import oasis_device as OD
 from tests import oasis_ref as R
 from tests import prep_ref
+from tests.device_util import P, _t, dev as _dev
 
 DX = importlib.import_module("localmd_amd.deconvolve")     # the module: the package exports the function under the same name
 
@@ -23,26 +25,8 @@ SIGMA = 0.3
 PLANTED = ((1, 0.015), (2, 0.02), (3, 0.01))      # the seeds and rates of tests/test_deconvolve_host.py
 SIGMA_RTOL = 4 * 2.02e-7                          # pmd_stats against float64: the bound of tests/test_gpu_prep_stage.py
 GS = (0.0, 0.5, 0.95, 0.999)
-
-
-def _t():
-    import torch
-
-    return torch
-
-
-def P(t):
-    from localmd_amd._lib import ptr
-
-    return ptr(t)
-
-
-def _dev(ctx, a, dtype):
-    return _t().from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(ctx.device)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.int32)
+_bits, _assert_same, _assert_result = OD.bits, OD.assert_same, OD.assert_result
+_device = functools.partial(OD.launch, OD.AR1)     # pmd_oasis_ar1: (ctx, Y, col, par, pw_row, pw, want=, pad=)
 
 
 def _ar_traces(seed, T, K):
@@ -81,54 +65,6 @@ def _emulate(Y, col, par, pw_row, pw):
             seen[key] = R.oasis_ar1(Y[:, col[p]], par[p, 0], par[p, 1], par[p, 2], par[p, 3], np.float32, pw[pw_row[p]])
         Ce[:, p], Se[:, p], rss[p], npl[p] = seen[key]
     return Ce, Se, rss, npl
-
-
-def _device(ctx, Y, col, par, pw_row, pw, want="CSRN", pad=(0, 0, 0)):
-    """pmd_oasis_ar1 on the device with the outputs named in ``want`` (C, S, Rss, N_pools) and ``pad`` extra columns in
-    Y, C and S; the outputs start as NaN / -1 and the workspace as 0xFF, and the padding must come back untouched."""
-    torch = _t()
-    T, K = Y.shape
-    n = len(col)
-    ldy, ldc, lds = K + pad[0], n + pad[1], n + pad[2]
-    Yd = torch.full((T, ldy), float("nan"), dtype=torch.float32, device=ctx.device)
-    Yd[:, :K] = _dev(ctx, Y, np.float32)
-    Cd = torch.full((T, ldc), float("nan"), dtype=torch.float32, device=ctx.device) if "C" in want else None
-    Sd = torch.full((T, lds), float("nan"), dtype=torch.float32, device=ctx.device) if "S" in want else None
-    rd = torch.full((n,), float("nan"), dtype=torch.float64, device=ctx.device) if "R" in want else None
-    nd = torch.full((n,), -1, dtype=torch.int32, device=ctx.device) if "N" in want else None
-    nbytes = ctx.lib.pmd_oasis_ar1_workspace_bytes(T, n)
-    assert nbytes == 12 * T * n
-    ws = torch.full((nbytes,), 0xFF, dtype=torch.uint8, device=ctx.device)
-    # named, so that the tables live until the call has run (a temporary's memory goes back to the allocator at once)
-    cold, pard = _dev(ctx, col, np.int32), _dev(ctx, par, np.float32)
-    rowd, pwd = _dev(ctx, pw_row, np.int32), _dev(ctx, pw, np.float32)
-    assert int(cold.min()) >= 0 and int(cold.max()) < K and int(rowd.min()) >= 0 and int(rowd.max()) < pw.shape[0]
-    assert pw.shape[1] >= T + 1
-    ctx.call("pmd_oasis_ar1", P(Yd), ldy, T, n, P(cold), P(pard), P(rowd), P(pwd), pw.shape[1], P(Cd), ldc, P(Sd), lds,
-             P(rd), P(nd), P(ws), nbytes)
-    ctx.sync()
-    out = {}
-    for name, t in (("C", Cd), ("S", Sd)):
-        if t is not None:
-            assert bool(torch.isnan(t[:, n:]).all().item()), name + ": columns beyond n_prob were written"
-            out[name] = t[:, :n].cpu().numpy()
-    if rd is not None:
-        out["R"] = rd.cpu().numpy()
-    if nd is not None:
-        out["N"] = nd.cpu().numpy()
-    return out
-
-
-def _assert_same(got, ref, names="CSRN"):
-    Ce, Se, rss, npl = ref
-    if "N" in names:
-        assert np.array_equal(got["N"], npl), np.nonzero(got["N"] != npl)[0][:5]
-    if "C" in names:
-        assert np.array_equal(_bits(got["C"]), _bits(Ce)), "calcium: {} values differ".format(np.sum(_bits(got["C"]) != _bits(Ce)))
-    if "S" in names:
-        assert np.array_equal(_bits(got["S"]), _bits(Se)), "spikes: {} values differ".format(np.sum(_bits(got["S"]) != _bits(Se)))
-    if "R" in names:
-        assert np.array_equal(got["R"].view(np.int64), rss.view(np.int64)), (got["R"] - rss)
 
 
 @functools.lru_cache(maxsize=None)
@@ -282,23 +218,8 @@ def _five_traces():
     return y
 
 
-_FIVE = {}
-
-
 def _five_run(ctx):
-    """deconvolve of the five traces with 3 rounds of 4 and the default cap, computed once."""
-    if "dc" not in _FIVE:
-        _FIVE["dc"] = localmd_amd.deconvolve(_five_traces(), search_rounds=3, search_points=4, ctx=ctx)
-    return _FIVE["dc"]
-
-
-def _assert_result(dc, ref):
-    assert np.array_equal(_bits(dc.calcium), _bits(ref["calcium"]))
-    assert np.array_equal(_bits(dc.spikes), _bits(ref["spikes"]))
-    assert np.array_equal(_bits(dc.lam), _bits(ref["lam"]))
-    assert np.array_equal(dc.rss, ref["rss"])
-    assert np.array_equal(dc.n_pools, ref["n_pools"])
-    assert np.array_equal(dc.evaluations, ref["evaluations"])
+    return OD.five_run(ctx, _five_traces(), 1)
 
 
 def test_deconvolve_equals_the_reference(gpu_ctx):

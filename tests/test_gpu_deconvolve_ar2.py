@@ -14,8 +14,10 @@ import pytest
 import localmd_amd
 from tests import bigbuf as B
 from tests import oasis2_ref as R2
+from tests import oasis_device as OD
 from tests import oasis_ref as R1
 from tests import test_gpu_large_offsets as L
+from tests.device_util import P, _t, dev as _dev
 
 DX = importlib.import_module("localmd_amd.deconvolve")     # the module: the package exports the function under the same name
 
@@ -25,29 +27,11 @@ big = L.big                                       # the module-scoped 8.6 GB buf
 PMD_ERR_ARG, PMD_ERR_WORKSPACE = -2, -3
 SIGMA = 0.3
 ROOTS = ((0.95, 0.5), (0.9, 0.3), (0.5, 0.0), (0.97, 0.8))     # (d, r) of column k: ROOTS[k % 4]
-GUARD = 512                                       # bytes of guard band on either side of the workspace
 EMULATION_ERR2 = 4.71e-7                          # fp32 against float64, the value measured in tests/test_deconvolve_ar2_host.py
 EMULATION_ERR1 = 4.18e-7                          # the same of the AR(1) solver, tests/test_deconvolve_host.py
-
-
-def _t():
-    import torch
-
-    return torch
-
-
-def P(t):
-    from localmd_amd._lib import ptr
-
-    return ptr(t)
-
-
-def _dev(ctx, a, dtype):
-    return _t().from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(ctx.device)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.int32)
+FIELDS = OD.FIELDS
+_bits, _assert_same, _assert_result = OD.bits, OD.assert_same, OD.assert_result
+_device = functools.partial(OD.launch, OD.AR2)     # pmd_oasis_ar2: (ctx, Y, col, par, tab_row, tab, want=, pad=, fill=)
 
 
 def _pairs(K):
@@ -100,57 +84,6 @@ def _emulate(Y, col, par, tab_row, tab):
             seen[key] = R2.oasis_ar2(Y[:, col[p]], par[p, 0], par[p, 1], par[p, 2], par[p, 3], par[p, 4], np.float32, rows)
         Ce[:, p], Se[:, p], rss[p], npl[p] = seen[key]
     return Ce, Se, rss, npl
-
-
-def _device(ctx, Y, col, par, tab_row, tab, want="CSRN", pad=(0, 0, 0), fill=0xFF):
-    """pmd_oasis_ar2 on the device with the outputs named in ``want`` (C, S, Rss, N_pools) and ``pad`` extra columns in
-    Y, C and S; the outputs start as NaN / -1, the workspace is exactly 24 T n bytes of ``fill`` between two guard bands
-    of the same fill, and the padding and the guard bands must come back untouched."""
-    torch = _t()
-    T, K = Y.shape
-    n = len(col)
-    ldy, ldc, lds = K + pad[0], n + pad[1], n + pad[2]
-    Yd = torch.full((T, ldy), float("nan"), dtype=torch.float32, device=ctx.device)
-    Yd[:, :K] = _dev(ctx, Y, np.float32)
-    Cd = torch.full((T, ldc), float("nan"), dtype=torch.float32, device=ctx.device) if "C" in want else None
-    Sd = torch.full((T, lds), float("nan"), dtype=torch.float32, device=ctx.device) if "S" in want else None
-    rd = torch.full((n,), float("nan"), dtype=torch.float64, device=ctx.device) if "R" in want else None
-    nd = torch.full((n,), -1, dtype=torch.int32, device=ctx.device) if "N" in want else None
-    nbytes = 24 * T * n
-    assert nbytes == ctx.lib.pmd_oasis_ar1_workspace_bytes(T, 2 * n) == DX.workspace_bytes(T, n, p=2)
-    ws = torch.full((GUARD + nbytes + GUARD,), fill, dtype=torch.uint8, device=ctx.device)
-    # named, so that the tables live until the call has run (a temporary's memory goes back to the allocator at once)
-    cold, pard = _dev(ctx, col, np.int32), _dev(ctx, par, np.float32)
-    rowd, tabd = _dev(ctx, tab_row, np.int32), _dev(ctx, tab, np.float32)
-    assert int(cold.min()) >= 0 and int(cold.max()) < K and par.shape == (n, 5)
-    assert int(rowd.min()) >= 0 and int(rowd.max()) + 3 <= tab.shape[0] and tab.shape[1] >= T + 2
-    ctx.call("pmd_oasis_ar2", P(Yd), ldy, T, n, P(cold), P(pard), P(rowd), P(tabd), tab.shape[1], P(Cd), ldc, P(Sd), lds,
-             P(rd), P(nd), C.c_void_p(ws.data_ptr() + GUARD), nbytes)
-    ctx.sync()
-    assert bool((ws[:GUARD] == fill).all().item()) and bool((ws[GUARD + nbytes:] == fill).all().item()), "guard band written"
-    assert bool((ws[GUARD + 20 * T * n:GUARD + nbytes] == fill).all().item()), "the spare word of the pools was written"
-    out = {}
-    for name, t in (("C", Cd), ("S", Sd)):
-        if t is not None:
-            assert bool(torch.isnan(t[:, n:]).all().item()), name + ": columns beyond n_prob were written"
-            out[name] = t[:, :n].cpu().numpy()
-    if rd is not None:
-        out["R"] = rd.cpu().numpy()
-    if nd is not None:
-        out["N"] = nd.cpu().numpy()
-    return out
-
-
-def _assert_same(got, ref, names="CSRN"):
-    Ce, Se, rss, npl = ref
-    if "N" in names:
-        assert np.array_equal(got["N"], npl), np.nonzero(got["N"] != npl)[0][:5]
-    if "C" in names:
-        assert np.array_equal(_bits(got["C"]), _bits(Ce)), "calcium: {} values differ".format(np.sum(_bits(got["C"]) != _bits(Ce)))
-    if "S" in names:
-        assert np.array_equal(_bits(got["S"]), _bits(Se)), "spikes: {} values differ".format(np.sum(_bits(got["S"]) != _bits(Se)))
-    if "R" in names:
-        assert np.array_equal(got["R"].view(np.int64), rss.view(np.int64)), (got["R"] - rss)
 
 
 @functools.lru_cache(maxsize=None)
@@ -363,26 +296,8 @@ def _five_traces():
     return y
 
 
-_FIVE = {}
-
-
 def _five_run(ctx):
-    """deconvolve(p=2) of the five traces with 3 rounds of 4 and the default cap, computed once."""
-    if "dc" not in _FIVE:
-        _FIVE["dc"] = localmd_amd.deconvolve(_five_traces(), search_rounds=3, search_points=4, ctx=ctx, p=2)
-    return _FIVE["dc"]
-
-
-FIELDS = ("calcium", "spikes", "lam", "rss", "n_pools", "evaluations")
-
-
-def _assert_result(dc, ref):
-    assert np.array_equal(_bits(dc.calcium), _bits(ref["calcium"]))
-    assert np.array_equal(_bits(dc.spikes), _bits(ref["spikes"]))
-    assert np.array_equal(_bits(dc.lam), _bits(ref["lam"]))
-    assert np.array_equal(dc.rss, ref["rss"])
-    assert np.array_equal(dc.n_pools, ref["n_pools"])
-    assert np.array_equal(dc.evaluations, ref["evaluations"])
+    return OD.five_run(ctx, _five_traces(), 2)
 
 
 def test_deconvolve2_equals_the_reference(gpu_ctx):
