@@ -350,6 +350,29 @@ int pmd_threshold_moments_accumulate(pmd_ctx* ctx, const void* Y, int elem, long
 size_t pmd_grid_components_workspace_bytes(int d1, int d2);
 int pmd_grid_components(pmd_ctx* ctx, int d1, int d2, const uint8_t* edges, int* label, void* ws, size_t ws_bytes);
 
+/* Growing ROI supports (localmd_amd/grow.py, csrc/roigrow.hip): per (pixel, ROI) pair of every ROI's window, the moments
+ * of the movie, with the other ROIs of that pixel taken out, against the ROI's trace.
+ *
+ * pmd_roi_window_moments_accumulate: X is a frames-first batch of element type elem (converted to fp32 exactly), frame f
+ *   of the call at X + f ldx elements, ldx >= D; any n >= 1 (no block discipline).  Ct holds the traces frames-first: the
+ *   K values of frame f at Ct + f ldct, ldct >= K.  Pair i < n_pairs is pixel pair_px[i] (0 <= pair_px[i] < D) and ROI
+ *   pair_k[i] (0 <= pair_k[i] < K); its others are the entries q in [oth_ptr[i], oth_ptr[i + 1]), ROI oth_k[q] with the
+ *   footprint value oth_a[q] on that pixel, any number of them (demix allows PMD_HALS_MAX_COVER ROIs on a pixel).  Per
+ *   pair and frame, every fp32 operation rounded on its own (no contraction), in this order: y = (float) X[f][pair_px[i]];
+ *   for q in stored order y = fl32(y - fl32(oth_a[q] * Ct[f][oth_k[q]])); c = Ct[f][pair_k[i]].  mom is double
+ *   [3][n_pairs] and is added to: mom[0][i] += sum_f y, mom[1][i] += sum_f y^2, mom[2][i] += sum_f y c.  Both products are
+ *   formed in fp64 from fp32 values and are exact; every sum is one fp64 chain per pair over the frames in ascending
+ *   order, continued from the stored value.  The bits of pair i therefore depend on its pixel's column, the trace rows
+ *   it names, its oth_a and the previous state only: not on how the frames are split over calls, on ldx or ldct, on the
+ *   element type holding the same values, on the pair's position in the table, nor on what other pairs are present.  The
+ *   tables are trusted (the caller validates them).  One owner per pair: no atomics, no workspace, no synchronisation, no
+ *   allocation.  n_pairs == 0 does nothing.
+ *   Errors (PMD_ERR_ARG, nothing is launched, mom untouched): n < 1, K < 1, D < 1, ldx < D, ldct < K, n_pairs < 0,
+ *   unknown elem, a NULL pointer with n_pairs > 0, more than (2^31 - 1) * 256 pairs. */
+int pmd_roi_window_moments_accumulate(pmd_ctx* ctx, const void* X, int elem, long ldx, long D, int n, const float* Ct,
+                                      long ldct, int K, long n_pairs, const int* pair_px, const int* pair_k,
+                                      const int64_t* oth_ptr, const int* oth_k, const float* oth_a, double* mom);
+
 /* Spike inference (localmd_amd/deconvolve.py, csrc/oasis.hip): OASIS for an AR(1) model, n_prob independent problems in
  * one launch.  Y is frames-first (frame t at Y + t ldy elements); problem p reads column col[p] (0 <= col[p] < ldy), its
  * parameters par[4 p .. 4 p + 3] = g, lam, s_min, b, and the table row pw + pw_row[p] ldpw, whose entry l = 0 .. T is g^l

@@ -16,6 +16,7 @@ from .quantiles import quantile_images
 from .baseline import Baseline, rolling_baseline, dff_movie, trace_baseline
 from .demix import Demixed, demix
 from .superpixels import Superpixels, superpixels
+from .grow import Grown, Merged, Refined, grow_rois, merge_rois, refine_demix
 from .deconvolve import (Deconvolved, deconvolve, estimate_decay, estimate_ar2, ar2_from_roots,
                          ar2_from_time_constants)
 from .register import Registration, RegisteredMovie, register_movie, apply_shifts, subpixel_peak
@@ -30,7 +31,7 @@ __all__ = [
     "project_movie", "make_pmd_diagnostic_images", "export_movie", "extract_traces",
     "regressor_maps", "event_regressors", "summary_images", "quantile_images",
     "Baseline", "rolling_baseline", "dff_movie", "trace_baseline", "Demixed", "demix",
-    "Superpixels", "superpixels", "Deconvolved", "deconvolve", "estimate_decay",
+    "Superpixels", "superpixels", "Grown", "Merged", "Refined", "grow_rois", "merge_rois", "refine_demix", "Deconvolved", "deconvolve", "estimate_decay",
     "estimate_ar2", "ar2_from_roots", "ar2_from_time_constants",
     "Registration", "RegisteredMovie", "register_movie", "apply_shifts", "subpixel_peak",
     "PiecewiseRegistration", "WarpedMovie", "register_piecewise", "apply_field", "warp_frames",

@@ -59,6 +59,8 @@ SIGNATURES = {
     "pmd_threshold_moments_accumulate": (c_i, [c_p, c_p, c_i, c_l, c_i, c_i, c_i, c_p, c_p]),
     "pmd_grid_components_workspace_bytes": (c_sz, [c_i, c_i]),
     "pmd_grid_components": (c_i, [c_p, c_i, c_i, c_p, c_p, c_p, c_sz]),
+    "pmd_roi_window_moments_accumulate": (c_i, [c_p, c_p, c_i, c_l, c_l, c_i, c_p, c_l, c_i, c_l, c_p, c_p, c_p, c_p, c_p,
+                                                c_p]),
     "pmd_oasis_ar1_workspace_bytes": (c_sz, [c_l, c_l]),
     "pmd_oasis_ar1": (c_i, [c_p, c_p, c_l, c_l, c_l, c_p, c_p, c_p, c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_p, c_p, c_sz]),
     "pmd_oasis_ar2": (c_i, [c_p, c_p, c_l, c_l, c_l, c_p, c_p, c_p, c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_p, c_p, c_sz]),

@@ -5,7 +5,7 @@
 set -e
 cd "$(dirname "$0")"
 OUT=../libpmd_hip.so
-SRCS="capi.hip rng.hip prep.hip tile_gemm.hip small_la.hip wide.hip pipeline.hip gram.hip global.hip chol.hip gemm_f16x2.hip sytrd.hip sytrd2.hip expand.hip diag.hip comm.hip project.hip diag_fused.hip expand_fused.hip roi.hip regress.hip stats.hip quantile.hip baseline.hip hals.hip superpixel.hip oasis.hip oasis2.hip register.hip piecewise.hip spatial.hip"
+SRCS="capi.hip rng.hip prep.hip tile_gemm.hip small_la.hip wide.hip pipeline.hip gram.hip global.hip chol.hip gemm_f16x2.hip sytrd.hip sytrd2.hip expand.hip diag.hip comm.hip project.hip diag_fused.hip expand_fused.hip roi.hip regress.hip stats.hip quantile.hip baseline.hip hals.hip superpixel.hip roigrow.hip oasis.hip oasis2.hip register.hip piecewise.hip spatial.hip"
 OBJS=""
 PIDS=()
 NAMES=()

@@ -201,6 +201,19 @@ class PMDArray:
 
         return superpixels(self, movie, **kw)
 
+    def grow_rois(self, demixed, movie=None, **kw):
+        """New supports and footprint values for the ROIs of a Demixed: per ROI the connected region where the movie,
+        with the other ROIs taken out, correlates with its trace, computed on the GPU (grow.grow_rois; same keywords)."""
+        from .grow import grow_rois
+
+        return grow_rois(self, demixed, movie, **kw)
+
+    def refine_demix(self, rois, movie=None, **kw):
+        """demix, then rounds of grow_rois, merge_rois and demix again (grow.refine_demix; same keywords)."""
+        from .grow import refine_demix
+
+        return refine_demix(self, rois, movie, **kw)
+
     @property
     def _combined_temporal(self):
         """(R * s) V, built on first use and cached: __getitem__ is then one sparse-dense product
