@@ -89,6 +89,11 @@ class PMDArray:
             return out.reshape((nf,) + fov).squeeze()
         rcols, rp = dv["rs"].shape
         T = dv["v"].shape[1]
+        if rcols == 0 or rp == 0 or dv["data"].numel() == 0:
+            # a U without columns or entries, or factors of rank 0: the denoised movie is the mean image in every frame
+            # (the host expansion adds var_img * 0), and there is nothing the kernels could be given pointers to
+            out[:] = np.ascontiguousarray(self.mean_img[k0, k1], dtype=np.float32).reshape(1, -1)
+            return out.reshape((nf,) + fov).squeeze()
         sel_dev = torch.from_numpy(sel).to(dev)
         scale = torch.from_numpy(np.ascontiguousarray(self.var_img[k0, k1], dtype=np.float32).reshape(-1)).to(dev)
         shift = torch.from_numpy(np.ascontiguousarray(self.mean_img[k0, k1], dtype=np.float32).reshape(-1)).to(dev)

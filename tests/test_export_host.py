@@ -142,6 +142,8 @@ def _random_tiled_u(d1, d2, b1, b2, order, K, seed, merged=False, empty_rows=Fal
         if empty_rows:
             rows = rows[(rows % 11) != 3]
         cols.append((rows, rng.standard_normal(rows.size)))
+    if not cols:                                   # no tile drew a column and K == 0: a U without columns
+        return scipy.sparse.csr_matrix((D, 0))
     r = np.concatenate([c[0] for c in cols])
     c = np.concatenate([np.full(len(x[0]), k) for k, x in enumerate(cols)])
     v = np.concatenate([x[1] for x in cols])

@@ -14,6 +14,7 @@ from localmd_amd._lib import PMDLibraryError, ptr
 from localmd_amd.pmdarray import PMDArray
 from localmd_amd.traces import roi_weights
 from tests import hals_ref as HR
+from tests.consumer_fuzz import REF32, rel as _rel        # REF32: the fp32 emulation against float64 on this case
 from tests.test_demix_host import _expand64
 from tests.test_export_host import _random_tiled_u
 from tests.test_traces_host import _disc, _forms
@@ -272,17 +273,9 @@ def e2e(gpu_ctx):
     return pmd, rois, X, ref, localmd_amd.demix(pmd, rois, ctx=gpu_ctx)
 
 
-# demix_ref with dtype=float32 (the emulations) against demix_ref in float64 on this case, measured on the CPU: the largest
-# difference relative to the largest reference value of each output.  The device is allowed 4 x that for the differing
-# GEMM summation orders: traces 1.56e-6, footprints 7.49e-6, background 1.59e-7, objective 1.05e-6.
-REF32 = {"traces": 3.90e-7, "footprints": 1.87e-6, "background": 3.97e-8, "objective": 2.61e-7}
 # the same measurement for the two traces-only calls of test_traces_only (allowed: 4 x)
 REF32_FIXED = {"traces": 4.56e-7, "objective": 5.15e-7}      # outer_iters=3, sweeps=2, update_footprints=False
 REF32_UNBOUNDED = {"traces": 6.13e-7}                        # outer_iters=1, sweeps=2, fixed footprints, nonneg_traces=False
-
-
-def _rel(got, want):
-    return float(np.abs(np.asarray(got, np.float64) - want).max() / np.abs(want).max())
 
 
 def test_demix_against_the_float64_reference(e2e):

@@ -17,6 +17,7 @@ from localmd_amd._minitiff import write_tiff
 from localmd_amd.dataset import TiffArray, lazy_data_loader
 from localmd_amd.pmdarray import PMDArray, load_npz, save_npz
 from localmd_amd.synthetic import make_movie
+from tests.consumer_fuzz import recon64 as _recon64
 from tests.test_export_host import _random_tiled_u
 from tests.util import degenerate_pmds
 
@@ -196,14 +197,6 @@ def test_kernel_rejects_bad_arguments(gpu_ctx):
 # ---- end to end ----------------------------------------------------------------------------------------------------
 def _panel(a, k, d2=D2):
     return a[:, :, k * d2:(k + 1) * d2]
-
-
-def _recon64(pmd):
-    d1, d2 = pmd.shape[1:]
-    uc = pmd.u.astype(np.float64).toarray()[pmd.row_indices.reshape(-1)]
-    x = (uc @ (pmd.r.astype(np.float64) * pmd.s.astype(np.float64)[None, :]) @ pmd.v.astype(np.float64)).T
-    return (np.asarray(pmd.mean_img, np.float64).reshape(-1) + np.asarray(pmd.var_img, np.float64).reshape(-1) * x
-            ).reshape(-1, d1, d2)
 
 
 @pytest.mark.parametrize("order", ["F", "C"])

@@ -16,6 +16,7 @@ from localmd_amd._minitiff import write_tiff
 from localmd_amd.dataset import TiffArray
 from tests import bigbuf as B
 from tests import grow_ref as GR
+from tests.consumer_fuzz import grown_bytes as _bytes, grown_equal_reference as _check_against_reference
 from tests.test_gpu_demix import _pmd, _rois, _same
 from tests.test_gpu_large_offsets import big, put_input  # noqa: F401  (big: the module's own 8.6 GB buffer)
 from tests.test_gpu_maps import _CountingU16, _long_pmd
@@ -248,33 +249,6 @@ def e2e(gpu_ctx):
     return pmd, X, _raw_movie(X), pmd.demix(_rois(), ctx=gpu_ctx)
 
 
-def _check_against_reference(g, ref, dm, d1, d2, corr_th, key):
-    K = len(dm.labels)
-    print(key, "status", ref["status"], "added", ref["added"], "removed", ref["removed"], "threshold", ref["threshold"],
-          "smallest |rho - corr_th|", ref["margin"])
-    assert ref["margin"] >= 1e-9, key                 # a property of the input: choose another seed if this ever fails
-    assert list(g.status) == ref["status"], key
-    assert np.array_equal(g.threshold, ref["threshold"]) and g.threshold.dtype == np.float64, key
-    assert np.array_equal(g.added, ref["added"]) and np.array_equal(g.removed, ref["removed"]), key
-    assert list(g.source) == sorted(ref["rows"]) and np.array_equal(g.labels, np.asarray(dm.labels)[g.source]), key
-    assert g.rois.dtype == np.float32 and g.rois.shape == (len(g.source), d1 * d2) and g.rois.has_sorted_indices, key
-    for row, k in enumerate(g.source):
-        idx, val = ref["rows"][k]
-        s, e = g.rois.indptr[row], g.rois.indptr[row + 1]
-        assert np.array_equal(g.rois.indices[s:e], idx), (key, k)
-        assert g.rois.data[s:e].tobytes() == val.tobytes(), (key, k)
-    assert g.correlation.shape == (K, d1 * d2) and g.correlation.dtype == np.float32
-    for k in range(K):
-        s, e = g.correlation.indptr[k], g.correlation.indptr[k + 1]
-        if k not in ref["rho"]:
-            assert s == e, (key, k)
-            continue
-        i0, i1, j0, j1 = ref["win"][k]
-        want_px = (np.arange(i0, i1)[:, None] * d2 + np.arange(j0, j1)[None, :]).reshape(-1)
-        assert np.array_equal(g.correlation.indices[s:e], want_px), (key, k)
-        assert g.correlation.data[s:e].tobytes() == ref["rho"][k].astype(np.float32).tobytes(), (key, k)
-
-
 @pytest.mark.parametrize("kind", ["denoised", "raw"])
 def test_grow_rois_equal_the_reference_on_the_exported_movie(gpu_ctx, e2e, kind):
     """Four discs, two of them overlapping, under a full-field ROI whose window (480 pixels) is above max_window: it stays
@@ -304,12 +278,6 @@ def test_grow_rois_equal_the_reference_on_the_exported_movie(gpu_ctx, e2e, kind)
     assert g0.status[4] == "empty" and list(g0.source) == [0, 1, 2, 3]
     assert np.array_equal(g0.correlation.indices, g.correlation.indices)
     assert g0.correlation.data.tobytes() != g.correlation.data.tobytes()
-
-
-def _bytes(g):
-    return b"".join(np.ascontiguousarray(a).tobytes() for a in (
-        g.rois.data, g.rois.indices, g.rois.indptr, g.source, g.correlation.data, g.correlation.indices,
-        g.correlation.indptr, g.threshold, g.added, g.removed)) + " ".join(g.status).encode()
 
 
 def test_invariance_over_batches_sources_residency_and_order(gpu_ctx, tmp_path):

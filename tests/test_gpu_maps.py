@@ -16,6 +16,8 @@ from localmd_amd._minitiff import write_tiff
 from localmd_amd.dataset import TiffArray, lazy_data_loader
 from localmd_amd.pmdarray import PMDArray, load_npz, save_npz
 from localmd_amd.synthetic import make_movie
+from tests.consumer_fuzz import check_sums, corr_bound as _corr_bound, den64 as _den64, factors64 as _factors64  # noqa: F401
+from tests.consumer_fuzz import pearson64 as _pearson64, sum_bounds as _sum_bounds  # noqa: F401
 from tests.test_export_host import _random_tiled_u
 from tests.util import degenerate_pmds
 
@@ -38,21 +40,6 @@ def _decompose(ctx, mov, order, background_rank=1):
     np.random.seed(0)
     return localmd_amd.localmd_decomposition(mov, (20, 20), 1000, max_components=4, background_rank=background_rank,
                                              seed=3, sim_iters=5, order=order, ctx=ctx)
-
-
-def _factors64(pmd):
-    """(mean, std, U in C pixel order, R diag(s), Vt) in float64."""
-    uc = pmd.u.astype(np.float64).toarray()[pmd.row_indices.reshape(-1)]
-    rs = pmd.r.astype(np.float64) * pmd.s.astype(np.float64)[None, :]
-    return (np.asarray(pmd.mean_img, np.float64).reshape(-1), np.asarray(pmd.var_img, np.float64).reshape(-1), uc, rs,
-            pmd.v.astype(np.float64))
-
-
-def _den64(pmd):
-    """(X64, |X| bound) of the denoised movie, (D, T) float64, pixels in C order."""
-    mean, std, uc, rs, vt = _factors64(pmd)
-    return (mean[:, None] + std[:, None] * (uc @ rs @ vt),
-            np.abs(mean)[:, None] + std[:, None] * (np.abs(uc) @ np.abs(rs) @ np.abs(vt)))
 
 
 @pytest.fixture(scope="module")
@@ -231,33 +218,8 @@ def test_kernel_rejects_bad_arguments(gpu_ctx):
 
 
 # ---- end to end: sums and means ------------------------------------------------------------------------------------
-def _sum_bounds(X64, Y64, X64den, absX, mean32):
-    """(raw64, raw bound, den64, den bound) of the "sum" maps, (K, D) float64.  The raw bound is the one the feature was
-    specified with, in terms of the mean image, and is kept in that form although the device centres by
-    maps.centring_vector (the mean rounded to a dyadic grid, within std / 16 of it): a bound in the device's own
-    centring would follow the implementation, this one is independent of it."""
-    raw64 = X64 @ Y64
-    rb = GAMMA * (np.abs(X64) @ np.abs(Y64 - mean32[None, :])) + 2.0 ** -22 * np.abs(raw64)
-    den64 = X64 @ X64den.T
-    db = 1e-5 * (np.abs(X64) @ absX.T) + 1e-6
-    return raw64, rb, den64, db
-
-
 def _check_sums(m, X64, Y64, X64den, absX, mean32, stat):
-    raw64, rb, den64, db = _sum_bounds(X64, Y64, X64den, absX, mean32)
-    if stat == "mean":
-        sx = X64.sum(axis=1)[:, None]
-        raw64, den64 = raw64 / sx, den64 / sx
-        rb = GAMMA * (np.abs(X64) @ np.abs(Y64 - mean32[None, :])) / np.abs(sx) + 2.0 ** -22 * np.abs(raw64)
-        db = 1e-5 * (np.abs(X64) @ absX.T) / np.abs(sx) + 1e-6
-    K = X64.shape[0]
-    for a in (m.denoised, m.raw, m.residual):
-        assert a.shape == (K, D1, D2) and a.dtype == np.float32
-    er, ed = np.abs(m.raw.reshape(K, D) - raw64), np.abs(m.denoised.reshape(K, D) - den64)
-    print(stat, "raw: max error / bound", (er / rb).max(), "denoised:", (ed / db).max())
-    assert np.all(er <= rb)
-    assert np.all(ed <= db)
-    assert np.array_equal(m.residual, m.raw - m.denoised)
+    check_sums(m, X64, Y64, X64den, absX, mean32, stat, D1, D2)
 
 
 @pytest.mark.parametrize("stat", ["sum", "mean"])
@@ -308,33 +270,6 @@ def test_background_rank_zero(gpu_ctx, case):
 
 
 # ---- end to end: correlation ---------------------------------------------------------------------------------------
-def _pearson64(x, Z):
-    """(r, kappa): float64 Pearson correlation of the rows of x (K, T) with the columns of Z (T, P), and
-    kappa_p = |z_p| / |z_p - mean z_p|."""
-    xc = x - x.mean(axis=1, keepdims=True)
-    zc = Z - Z.mean(axis=0, keepdims=True)
-    nz = np.sqrt((zc * zc).sum(axis=0))
-    with np.errstate(divide="ignore", invalid="ignore"):       # a pixel without variance: r is NaN, kappa infinite
-        r = (xc @ zc) / (np.sqrt((xc * xc).sum(axis=1))[:, None] * nz[None, :])
-        return r, np.sqrt((Z * Z).sum(axis=0)) / nz
-
-
-def _corr_bound(kappa):
-    """Forward bound of the device correlation against the float64 Pearson correlation of the same fp32-valued inputs,
-    from the bounds of the kernel test: with g = GAMMA = 1032 2^-24 every block sum is known to g times its sum of
-    magnitudes, so, by Cauchy-Schwarz and |x^| = 1,
-        |d S_xz| <= g |x^| |z| = g |z|,  |d S_z| <= g sqrt(T) |z|,  |d S_zz| <= g |z|^2.
-    With s_z = |z - mean z| = |z| / kappa the numerator N = S_xz - S_x S_z / T (|S_x| <= T 2^-25 max |x^| for the rounded,
-    centred x^: its term is of second order) is off by g |z|, which is g kappa in r.  The variance V = S_zz - S_z^2 / T is
-    off by |d S_zz| + 2 |S_z| |d S_z| / T <= g |z|^2 (1 + 2 sqrt(1 - kappa^-2)), since |S_z| / sqrt(T) = |mean z| sqrt(T) =
-    |z| sqrt(1 - kappa^-2); relative to V = |z|^2 / kappa^2 and halved by the square root that is
-    g kappa^2 (1/2 + sqrt(1 - kappa^-2)) in r (|r| <= 1).  Together
-        |r - r64| <= g kappa + g kappa^2 (1/2 + sqrt(1 - kappa^-2)) + 2^-23,
-    the last term covering the one rounding to float32 (2^-25) and the terms of second order in g.  For every kappa this
-    is at most 2.5 g kappa^2; near kappa = 1, as on this movie, it is about 1.6 g."""
-    return GAMMA * kappa + GAMMA * kappa * kappa * (0.5 + np.sqrt(np.maximum(0.0, 1.0 - kappa ** -2.0))) + 2.0 ** -23
-
-
 @pytest.mark.parametrize("order", ["F", "C"])
 def test_correlation_against_fp64_pearson(gpu_ctx, case, order):
     mov, pmds = case

@@ -711,6 +711,38 @@ def test_pmdarray_device_expansion_matches_host(gpu_ctx, order):
         pmd[3, 5:5, :]
 
 
+@pytest.mark.parametrize("which", ["no_columns", "rank_zero", "no_entries"])
+def test_pmdarray_device_expansion_without_columns_rank_or_entries(gpu_ctx, which):
+    """A U without columns (found by tests/test_gpu_consumer_fuzz.py on a 23 x 37 field: pmd_csr_rows_spmm refused the
+    null pointers of the empty device arrays), factors of rank 0, and a U whose columns hold no entry: pmd[...] after
+    to_device() is the mean image in every frame, as on the host."""
+    import scipy.sparse
+    from localmd_amd.pmdarray import PMDArray
+    from tests.util import degenerate_pmds
+
+    T, d1, d2 = 12, 5, 7
+    rng = np.random.default_rng(3)
+    f32 = np.float32
+    full = PMDArray(scipy.sparse.random(d1 * d2, 4, density=0.4, random_state=1, format="csr", dtype=f32),
+                    rng.standard_normal((4, 2)).astype(f32), np.ones(2, f32), rng.standard_normal((2, T)).astype(f32), (T, d1, d2),
+                    "F", rng.uniform(500, 1500, (d1, d2)).astype(f32), rng.uniform(2, 10, (d1, d2)).astype(f32))
+    if which == "no_entries":
+        pmd = PMDArray(scipy.sparse.csr_matrix((d1 * d2, 4), dtype=f32), full.r, full.s, full.v, (T, d1, d2), "F", full.mean_img,
+                       full.var_img)
+    else:
+        pmd = degenerate_pmds(full)[which]
+    keys = [slice(None), 5, (slice(2, 9), slice(1, 4), slice(0, 7, 2)), ([3, 1, 11], 2, 6)]
+    host = [pmd[k] for k in keys]
+    assert np.array_equal(host[1], pmd.mean_img)
+    pmd.to_device(ctx=gpu_ctx)
+    try:
+        for k, h in zip(keys, host):
+            g = pmd[k]
+            assert g.shape == h.shape and g.dtype == h.dtype == np.float32 and np.array_equal(g, h), k
+    finally:
+        pmd.to_host()
+
+
 def _check_structure_and_fit(pmd, diag, ref, mov):
     """For inputs whose kept noise component is an arbitrary vector of a nearly degenerate noise subspace (very short
     movies): everything that is well posed - tile ranks, CSR structure, statistics images, orthonormality, and how

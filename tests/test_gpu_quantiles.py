@@ -16,6 +16,7 @@ from localmd_amd import quantiles as QT
 from localmd_amd._lib import PMDLibraryError, ptr
 from localmd_amd._minitiff import write_tiff
 from localmd_amd.dataset import TiffArray, lazy_data_loader
+from tests.consumer_fuzz import exported as _exported, mad_reference as _mad_reference, quantile_reference as _reference
 from tests.test_gpu_maps import _CountingU16, _decompose, _int_movie, _long_pmd
 from tests.util import degenerate_pmds
 
@@ -247,14 +248,6 @@ def case(gpu_ctx):
     return mov, pmds
 
 
-def _exported(ctx, pmd, mov):
-    """{kind: (T, D) float32} of export_movie, the fp32 frames the kernel sees."""
-    out = np.empty((T, D1, 3 * D2), np.float32)
-    localmd_amd.export_movie(pmd, out, mov, panels=("raw", "denoised", "residual"), dtype="float32", ctx=ctx)
-    return {k: np.ascontiguousarray(out[:, :, j * D2:(j + 1) * D2]).reshape(T, D)
-            for j, k in enumerate(("raw", "denoised", "residual"))}
-
-
 @pytest.fixture(scope="module")
 def sorted_panels(gpu_ctx, case):
     mov, pmds = case
@@ -264,27 +257,6 @@ def sorted_panels(gpu_ctx, case):
         assert np.array_equal(panels["raw"], mov.reshape(T, D))
         out[o] = (panels, {k: np.sort(v, axis=0) for k, v in panels.items()})
     return out
-
-
-def _reference(S, q, interpolation):
-    """(Q, D) float32 from the sorted (T, D) float32 values S, by the rules of the feature, written out here: h = q (T - 1)
-    in float64; lower floor(h), higher ceil(h), nearest round-half-even(h); linear
-    float32(lo + (hi - lo) (h - floor(h))) in float64."""
-    n = S.shape[0]
-    rows = []
-    for x in q:
-        h = np.float64(x) * (n - 1)
-        lo, hi = int(np.floor(h)), int(np.ceil(h))
-        if interpolation == "lower":
-            rows.append(S[lo])
-        elif interpolation == "higher":
-            rows.append(S[hi])
-        elif interpolation == "nearest":
-            rows.append(S[int(np.rint(h))])
-        else:
-            lo64, hi64 = S[lo].astype(np.float64), S[hi].astype(np.float64)
-            rows.append((lo64 + (hi64 - lo64) * (h - np.floor(h))).astype(np.float32))
-    return np.stack(rows)
 
 
 @pytest.mark.parametrize("order", ["F", "C"])
@@ -311,13 +283,6 @@ def test_every_kind_position_and_interpolation_against_np_sort(gpu_ctx, case, so
     for kind in ALL:
         assert getattr(ends, kind)[0].tobytes() == getattr(s, kind)["min"].tobytes(), kind
         assert getattr(ends, kind)[1].tobytes() == getattr(s, kind)["max"].tobytes(), kind
-
-
-def _mad_reference(panel, S):
-    m = _reference(S, (0.5,), "linear")[0]
-    dev = np.abs(panel - m[None, :])                                  # one fp32 subtraction per element
-    assert dev.dtype == np.float32
-    return _reference(np.sort(dev, axis=0), (0.5,), "linear")[0]
 
 
 def test_mad_against_np_sort(gpu_ctx, case, sorted_panels):

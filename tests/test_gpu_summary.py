@@ -16,6 +16,8 @@ from localmd_amd._lib import PMDLibraryError, ptr
 from localmd_amd._minitiff import write_tiff
 from localmd_amd.dataset import TiffArray, lazy_data_loader
 from localmd_amd.pmdarray import load_npz, save_npz
+from tests.consumer_fuzz import check_moments as _check_moments, check_pnr, exported as _exported, extrema_equal_export
+from tests.consumer_fuzz import kinds64 as _kinds64, moment_bounds as _moment_bounds  # noqa: F401
 from tests.test_gpu_maps import _CountingU16, _decompose, _den64, _int_movie, _long_pmd
 from tests.test_summary_host import emulate_bins
 from tests.util import degenerate_pmds
@@ -287,14 +289,6 @@ def case(gpu_ctx):
     return mov, {o: _decompose(gpu_ctx, mov, o) for o in ("F", "C")}
 
 
-def _exported(ctx, pmd, mov):
-    """{kind: (T, D) float32} of export_movie, the fp32 frames the kernel sees."""
-    out = np.empty((T, D1, 3 * D2), np.float32)
-    localmd_amd.export_movie(pmd, out, mov, panels=("raw", "denoised", "residual"), dtype="float32", ctx=ctx)
-    return {k: np.ascontiguousarray(out[:, :, j * D2:(j + 1) * D2]).reshape(T, D)
-            for j, k in enumerate(("raw", "denoised", "residual"))}
-
-
 def _check_extrema_against_export(ctx, pmd, mov):
     panels = _exported(ctx, pmd, mov)
     assert np.array_equal(panels["raw"], mov.reshape(T, D))
@@ -302,14 +296,8 @@ def _check_extrema_against_export(ctx, pmd, mov):
                                    ctx=ctx)
     assert s.stats == ("min", "max", "argmin", "argmax") and s.temporal_bin == 1
     for kind in ALL:
-        img, Yk = getattr(s, kind), panels[kind]
-        assert sorted(img) == ["argmax", "argmin", "max", "min"]
-        for k in ("min", "max"):
-            assert img[k].shape == (D1, D2) and img[k].dtype == np.float32
-            assert img["arg" + k].shape == (D1, D2) and img["arg" + k].dtype == np.int32
-        assert img["min"].tobytes() == Yk.min(axis=0).tobytes() and img["max"].tobytes() == Yk.max(axis=0).tobytes(), kind
-        assert np.array_equal(img["argmin"].reshape(-1), Yk.argmin(axis=0)), kind
-        assert np.array_equal(img["argmax"].reshape(-1), Yk.argmax(axis=0)), kind
+        assert sorted(getattr(s, kind)) == ["argmax", "argmin", "max", "min"]
+    extrema_equal_export({k: getattr(s, k) for k in ALL}, panels, D1, D2)
     assert np.array_equal(s.raw["max"], mov.max(axis=0)) and np.array_equal(s.raw["argmax"], mov.argmax(axis=0))
     return s
 
@@ -360,91 +348,14 @@ def test_decomposition_without_columns_or_rank(gpu_ctx, case, which):
     assert np.array_equal(m["mean"], mean32) and not m["std"].any()
 
 
-def _moment_bounds(Z):
-    """(reference, bound) per stat for the (T, N) float64 values Z = y - centre (the mean is that of Z; add the centre).
-
-    The kernel bound (test_kernel_float_data_within_the_forward_bound), summed over the blocks: the device sums S_p are
-    within g A_p of the exact ones, g = GAMMA, A_p = sum |z|^p.  With a_p = S_p / T, alpha_p = A_p / T the finishing
-    formulas of summary.finish_moments give, to first order in g,
-        mean  = centre + a_1:                          |d mean| <= g alpha_1
-        m_2   = a_2 - a_1^2:                           |d m_2| <= e_2 = g (alpha_2 + 2 |a_1| alpha_1)
-        m_3   = a_3 - 3 a_1 a_2 + 2 a_1^3:             |d m_3| <= e_3 = g (alpha_3 + 3 |a_1| alpha_2 + (3 |a_2| + 6 a_1^2) alpha_1)
-        m_4   = a_4 - 4 a_1 a_3 + 6 a_1^2 a_2 - 3 a_1^4:
-                |d m_4| <= e_4 = g (alpha_4 + 4 |a_1| alpha_3 + 6 a_1^2 alpha_2 + (4 |a_3| + 12 |a_1| |a_2| + 12 |a_1|^3) alpha_1)
-        std   = m_2^(1/2):                             |d std|  <= e_2 / (2 std)
-        skew  = m_3 m_2^(-3/2):                        |d skew| <= e_3 / m_2^(3/2) + (3/2) |skew| e_2 / m_2
-        kurt  = m_4 / m_2^2 - 3:                       |d kurt| <= e_4 / m_2^2 + 2 (kurt + 3) e_2 / m_2.
-    Each is doubled for the dropped terms of second order, and 2^-24 |value| is added for the one rounding of the image to
-    float32."""
-    n = Z.shape[0]
-    a1, a2, a3, a4 = ((Z ** p).sum(axis=0) / n for p in (1, 2, 3, 4))
-    A = np.abs(Z)
-    l1, l2, l3, l4 = ((A ** p).sum(axis=0) / n for p in (1, 2, 3, 4))
-    d = Z - a1[None, :]
-    m2, m3, m4 = ((d ** p).mean(axis=0) for p in (2, 3, 4))
-    g = GAMMA
-    e2 = g * (l2 + 2 * np.abs(a1) * l1)
-    e3 = g * (l3 + 3 * np.abs(a1) * l2 + (3 * np.abs(a2) + 6 * a1 * a1) * l1)
-    e4 = g * (l4 + 4 * np.abs(a1) * l3 + 6 * a1 * a1 * l2 + (4 * np.abs(a3) + 12 * np.abs(a1 * a2) + 12 * np.abs(a1) ** 3) * l1)
-    std, skew, kurt = np.sqrt(m2), m3 / m2 ** 1.5, m4 / m2 ** 2 - 3.0
-    ref = {"mean": a1, "std": std, "skewness": skew, "kurtosis": kurt}
-    bound = {"mean": 2 * g * l1, "std": 2 * e2 / (2 * std), "skewness": 2 * (e3 / m2 ** 1.5 + 1.5 * np.abs(skew) * e2 / m2),
-             "kurtosis": 2 * (e4 / m2 ** 2 + 2 * (kurt + 3.0) * e2 / m2)}
-    floor_margin = (n * m2) / (3 * GAMMA * n * a2)         # > 1: the pixel is above the variance floor
-    return ref, bound, floor_margin
-
-
-def _kinds64(pmd, mov):
-    """{kind: ((T, D) float64 values, the (D,) centring vector the device uses)}: the movie, the float64 reconstruction
-    and their difference, pixels in C order."""
-    X64 = _den64(pmd)[0].T
-    Y64 = mov.reshape(T, D).astype(np.float64)
-    mean32 = np.asarray(pmd.mean_img, np.float32).reshape(-1).astype(np.float64)
-    return {"raw": (Y64, MP.centring_vector(pmd).astype(np.float64)), "denoised": (X64, mean32),
-            "residual": (Y64 - X64, np.zeros(D))}
-
-
-def _check_moments(s, pmd, mov):
-    """mean / std / skewness / kurtosis of every kind against float64 NumPy: on the movie, on the float64 reconstruction
-    and on their difference."""
-    vals = _kinds64(pmd, mov)
-    for kind in ALL:
-        Yk, centre = vals[kind]
-        ref, bound, margin = _moment_bounds(Yk - centre[None, :])
-        ref["mean"] = ref["mean"] + centre
-        print(kind, "variance / floor, smallest", margin.min())
-        assert margin.min() > 1.0, kind                                  # no pixel at the floor: it hides nothing here
-        for stat in _MOMENTS:
-            got = getattr(s, kind)[stat]
-            assert got.shape == (D1, D2) and got.dtype == np.float32
-            b = bound[stat] + U24 * np.abs(ref[stat])
-            err = np.abs(got.reshape(-1).astype(np.float64) - ref[stat])
-            print(kind, stat, "max error / bound", (err / b).max(), "max error", err.max())
-            assert np.all(err <= b), (kind, stat)
-
-
 @pytest.mark.parametrize("order", ["F", "C"])
 def test_moments_against_fp64_and_pnr(gpu_ctx, case, order):
     mov, pmds = case
     pmd = pmds[order]
     s = localmd_amd.summary_images(pmd, mov, kinds=ALL, stats=_MOMENTS + ("max", "pnr"), frame_batch_size=2048, ctx=gpu_ctx)
     _check_moments(s, pmd, mov)
-    # pnr: (max - mean) / noise in float64 from the returned float32 max and the float64 mean, rounded once: 2^-23
-    # relative.  The raw sums of this integer movie about the dyadic centring vector are exact, so the float64 mean of
-    # NumPy is the one the host finished with; under the other kinds the device mean is within 2 GAMMA mean |z| of
-    # NumPy's (_moment_bounds), which enters the ratio divided by the noise.
-    noise = np.asarray(pmd.var_img, np.float64).reshape(-1)
-    assert np.all(np.isfinite(noise)) and np.all(noise > 0)
-    for kind, (Yk, centre) in _kinds64(pmd, mov).items():
-        img = getattr(s, kind)
-        assert img["pnr"].shape == (D1, D2) and img["pnr"].dtype == np.float32
-        want = (img["max"].reshape(-1).astype(np.float64) - Yk.mean(axis=0)) / noise
-        tol = 2.0 ** -23 * np.abs(want)
-        if kind != "raw":
-            tol = tol + 2 * GAMMA * np.abs(Yk - centre[None, :]).mean(axis=0) / noise
-        err = np.abs(img["pnr"].reshape(-1) - want)
-        print(kind, "pnr: max error / tolerance", (err / tol).max())
-        assert np.all(err <= tol), kind
+    # pnr: (max - mean) / noise in float64 from the returned float32 max and the float64 mean, rounded once
+    check_pnr(s, pmd, mov)
     import copy
 
     # where the noise image is unusable the ratio is 0

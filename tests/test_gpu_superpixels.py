@@ -17,6 +17,7 @@ from localmd_amd._minitiff import write_tiff
 from localmd_amd.dataset import TiffArray, lazy_data_loader
 from localmd_amd.pmdarray import PMDArray
 from tests import superpixel_ref as SR
+from tests.consumer_fuzz import superpixels_equal_reference as _check_against_reference
 from tests.test_gpu_demix import _pmd
 from tests.test_gpu_maps import _CountingU16, _long_pmd
 from tests.test_traces_host import _disc
@@ -348,18 +349,6 @@ def e2e(gpu_ctx):
     pmd = _pmd("F")
     X = _exported(gpu_ctx, pmd)
     return pmd, X, _raw_movie(X)
-
-
-def _check_against_reference(sp, ref, cut_off, key):
-    margin = np.abs(ref["rho"][ref["rho"] != 0] - cut_off).min()
-    print(key, "K", len(ref["sizes"]), "of", ref["n_components"], "smallest |rho - cut_off|", margin)
-    assert margin >= 1e-9, key                    # a property of the input: choose another seed if this ever fails
-    assert sp.threshold.dtype == np.float32 and sp.threshold.tobytes() == ref["threshold"].tobytes(), key
-    assert np.array_equal(sp.edges, ref["edges"]), key
-    assert sp.labels.dtype == np.int32 and np.array_equal(sp.labels, ref["labels"]), key
-    assert sp.sizes.dtype == np.int64 and np.array_equal(sp.sizes, ref["sizes"]), key
-    assert sp.n_components == ref["n_components"], key
-    assert sp.correlation.dtype == np.float32 and np.abs(sp.correlation - ref["correlation"]).max() <= 1e-6, key
 
 
 @pytest.mark.parametrize("kind", ["denoised", "raw"])

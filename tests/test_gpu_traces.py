@@ -19,6 +19,7 @@ from localmd_amd._minitiff import write_tiff
 from localmd_amd.dataset import TiffArray, lazy_data_loader
 from localmd_amd.pmdarray import PMDArray, load_npz, save_npz
 from localmd_amd.synthetic import make_movie
+from tests.consumer_fuzz import U24, factors64 as _factors64, raw_bound as _raw_bound, w64 as _w64
 from tests.test_export_host import _random_tiled_u
 from tests.test_traces_host import _disc, _forms, _roi_set
 
@@ -27,7 +28,6 @@ Dm.QUIET = True
 T, D1, D2 = 2500, 40, 44
 D = D1 * D2
 ALL = ("denoised", "raw", "residual")
-U24 = 2.0 ** -24
 
 
 def _int_movie(seed):
@@ -51,18 +51,6 @@ def _float_weights(seed=5):
     """The ROI set of the host tests with weights that are not exactly representable in fp32."""
     w = _roi_set(D1, D2, False)
     return w * np.random.default_rng(seed).uniform(0.1, 2.0, w.shape)
-
-
-def _w64(w, reduce):
-    W = w.reshape(w.shape[0], -1).astype(np.float64)
-    return W / W.sum(axis=1, keepdims=True) if reduce == "mean" else W
-
-
-def _raw_bound(W64, Y64):
-    """(p + 4) 2^-24 (|W| |Y|): one rounding per product and per addition of a p-term chain plus the segment adds,
-    plus the weight's own rounding."""
-    p = (W64 != 0).sum(axis=1)
-    return (p + 4)[:, None] * U24 * (np.abs(W64) @ np.abs(Y64))
 
 
 # ---- the kernel through the C ABI ----------------------------------------------------------------------------------
@@ -168,14 +156,6 @@ def test_kernel_rejects_bad_arguments(gpu_ctx):
 
 
 # ---- end to end ----------------------------------------------------------------------------------------------------
-def _factors64(pmd):
-    """(mean, std, U in C pixel order, R diag(s), Vt) in float64."""
-    uc = pmd.u.astype(np.float64).toarray()[pmd.row_indices.reshape(-1)]
-    rs = pmd.r.astype(np.float64) * pmd.s.astype(np.float64)[None, :]
-    return (np.asarray(pmd.mean_img, np.float64).reshape(-1), np.asarray(pmd.var_img, np.float64).reshape(-1), uc, rs,
-            pmd.v.astype(np.float64))
-
-
 @pytest.mark.parametrize("reduce", ["sum", "mean"])
 @pytest.mark.parametrize("order", ["F", "C"])
 def test_traces_against_fp64(gpu_ctx, case, order, reduce):
